@@ -12,6 +12,12 @@ running under a launcher. Bands shard across ranks (`--shard bands`, config 4) o
 contiguous ranges (`--shard frames`, config 5); there is no data-path collective either way, the scan configuration is
 broadcast once from rank 0.
 
+A plain run sets up, warms up, times exactly --steps steps and prints the line: the contract's keys, `config` and `roofline_chain`
+(figures of the timed region itself; `roofline` without kernel figures). `--full` adds what takes work of its own beside that: the
+kernel timing behind the timed region, the live PMC passes, the `also` runs and drop-in lines, the CPU baseline and the parity
+sample (below). `--dump-outputs DIR` writes what the last timed step handed out — the dB plane (and the rel / avg planes with
+--planes) and the candidate lists — as DIR/<name>.npy; the timed steps read the same seeded inputs in the same order in every run.
+
 Prints ONE JSON line on rank 0 — a compact form of a few KB (compact_line: the contract's keys, roofline, cpu_baseline, a parity verdict
 and one short record per `also` entry); everything below in full goes to bench_full.json beside this file:
   value / ms_per_step   whole-job throughput, barrier + device sync on both sides of exactly --steps steps, max over ranks (a rank's interval:
@@ -471,8 +477,8 @@ def rank_plan(rank: int, local_rank: int, world: int, ndev: int, args, n: int) -
     """Which device a rank takes and which of the side legs of the line it runs. One process per GPU: rank r of a node works on device
     LOCAL_RANK (modulo the device count only where a box has fewer GPUs than ranks — ranks then share devices over gloo and the line
     says so). The legs beside the timed region — CPU baseline, live PMC passes, the `also` runs, the parity sample — are rank 0's, at
-    N = 1 only: at N > 1 the timed region is all a rank does (tests/test_dist_gloo.py pins this on the CPU)."""
-    single = world == 1 and rank == 0
+    N = 1 only and with --full: at N > 1, and in a plain run, the timed region is all a rank does (tests/test_dist_gloo.py pins this on the CPU)."""
+    single = world == 1 and rank == 0 and args.full
     default2 = (args.config or 2) == 2 and n == 8192
     return {"device_index": local_rank % max(ndev, 1), "shares_device": world > max(ndev, 1),
             "cpu_baseline": single and not args.no_cpu_baseline,
@@ -538,6 +544,10 @@ def parse_args(argv):
     ap.add_argument("--sub", action="store_true", help="(internal) this process is one of the `also` runs of another bench.py")
     ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic stays null: do not run the two short rocprofv3 --pmc passes of this command line behind the timed region (default line of config 2 at N = 1 only)")
     ap.add_argument("--no-parity", action="store_true", help="no parity sample beside the numbers (the `also` runs carry one each unless told otherwise)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: the kernel timing behind the timed region (roofline), the live PMC passes, "
+                    "the `also` runs, the drop-in lines, the CPU baseline and the parity sample (a plain run only sets up, warms up and times the steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step handed out as DIR/<name>.npy (float32 / float64, "
+                    "at most 64 MB: a fixed, seeded sample of frames of the planes beyond that)")
     args = ap.parse_args(argv)
     preset = dict(CONFIGS.get(args.config or 2, {}))
     args.cpu_only = bool(preset.pop("cpu_only", False))
@@ -668,7 +678,7 @@ def also_lines(all_sizes: bool = False):
         runs.insert(5, (5, 40, ["--frames", "64"], None))
     for cfg_no, steps, extra, variant in runs:
         cmd = [sys.executable, os.path.abspath(__file__), "--config", str(cfg_no), "--gpus", "1", "--steps", str(steps), "--warmup", "5",
-               "--preheat-ms", "150", "--no-cpu-baseline", "--sub", *extra]
+               "--preheat-ms", "150", "--no-cpu-baseline", "--sub", "--full", *extra]
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
@@ -788,6 +798,31 @@ def emit_line(full: dict, sub: bool = False) -> None:
             except OSError:
                 pass
     print(json.dumps(compact_line(full)), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(dirname: str, planes: dict, lists: dict, limit: int = DUMP_LIMIT_BYTES, seed: int = 0) -> dict:
+    """--dump-outputs: what a caller of the timed path receives from its last step, as DIR/<name>.npy. `lists` (the candidate lists:
+    cand_off, cand_idx, cand_avg) go whole, integers as float64 (exact), floats as float32; `planes` ({name: [frames, N]}) go whole
+    when everything fits in `limit` bytes, else the same fixed, seeded sample of frames of every plane, ascending, whose indices
+    go to plane_frames.npy. Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    out = {k: np.asarray(v, np.float64 if np.issubdtype(np.asarray(v).dtype, np.integer) else np.float32) for k, v in lists.items()}
+    planes = {k: np.asarray(v, np.float32) for k, v in planes.items()}
+    room = limit - sum(a.nbytes for a in out.values())
+    if planes and sum(p.nbytes for p in planes.values()) > room:
+        nf, row_bytes = next(iter(planes.values())).shape[0], sum(p[0].nbytes for p in planes.values())
+        keep = max(1, min(nf, (room - 8 * nf) // row_bytes))
+        rows = np.sort(np.random.default_rng(seed).choice(nf, keep, replace=False))
+        out["plane_frames"] = rows.astype(np.float64)
+        planes = {k: p[rows] for k, p in planes.items()}
+    out.update(planes)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+    return {k: a.shape for k, a in out.items()}
 
 
 
@@ -976,6 +1011,9 @@ def run(args):
             step()
         eng.sync()
         preheat_steps += 50
+    while preheat_steps % nsets:  # whole rotations: the timed steps read the same input sets in the same order in every run
+        step()
+        preheat_steps += 1
     _probe("learned")
     for _ in range(max(args.warmup, 1)):
         step()
@@ -1009,6 +1047,12 @@ def run(args):
     t1 = time.perf_counter()
     gc.enable()
     eng.sync()  # (settles the library's own bookkeeping; nothing left to wait for)
+    if args.dump_outputs and rank == 0:  # before anything else writes an output set
+        o = outs[(counter[0] - 1) % nout]
+        planes = {name: o[key].cpu().numpy() for name, key in (("psd", "psd"), ("rel", "rel_plane"), ("avg", "avg_plane")) if o[key] is not None}
+        off = o["off"].cpu().numpy()
+        held = min(int(off[-1]), int(o["idx"].numel()))
+        dump_outputs(args.dump_outputs, planes, {"cand_off": off, "cand_idx": o["idx"][:held].cpu().numpy(), "cand_avg": o["avg"][:held].cpu().numpy()})
     kern_ms, launches, slots = 0.0, 0, {}
     if every:
         slots = eng.kernel_timing_read_frames()  # {slot: (ms, launches, frames those launches covered)}
@@ -1017,7 +1061,7 @@ def run(args):
     # Right behind the timed region — same clocks, same working set, nothing of it inside — 32 more steps with every 4th call's launches
     # timed give eight samples per kernel of the chain; they are what roofline.kernel_us is made of.
     kern_after = None
-    if not args.no_kernel_timing and not every:
+    if args.full and not args.no_kernel_timing and not every:
         eng.kernel_timing(4)
         for _ in range(32):
             step()
@@ -1127,7 +1171,7 @@ def run(args):
                                "pmc_bytes_per_sample_from_profiles": round(sum(pmc_chain) / (nb * n), 2) if pmc_chain else None},
         }
         if plan["live_pmc"] and dom:
-            sub_argv = ["--gpus", "1", "--steps", "30", "--warmup", "5", "--preheat-ms", "0", "--no-cpu-baseline", "--no-also", "--no-parity", "--no-live-pmc", "--sub"]
+            sub_argv = ["--gpus", "1", "--steps", "30", "--warmup", "5", "--preheat-ms", "0", "--no-cpu-baseline", "--no-also", "--no-parity", "--no-live-pmc", "--sub", "--full"]
             try:
                 live, why = live_pmc_traffic(sub_argv, "k_scan_step", (nb + 20 + nb // 8 + 4) * 512)
             except Exception as e:  # (the line must come out whatever the profiler does)

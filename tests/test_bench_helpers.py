@@ -58,9 +58,9 @@ def test_chain_kernels_and_their_bytes():
 
 def test_ranks_take_their_own_device_and_only_rank_zero_of_one_runs_the_side_legs():
     """bench.py at N > 1 (the driver's 2 / 4 / 8-GPU runs, which no round could try on hardware): rank r works on device LOCAL_RANK,
-    and the legs beside the timed region — CPU baseline, live PMC passes, `also`, the parity sample — run at N = 1 only."""
+    and the legs beside the timed region — CPU baseline, live PMC passes, `also`, the parity sample — run at N = 1 with --full only."""
     b = _bench()
-    args = b.parse_args([])
+    args = b.parse_args(["--full"])
     for world in (2, 4, 8):
         seen = set()
         for r in range(world):
@@ -73,9 +73,13 @@ def test_ranks_take_their_own_device_and_only_rank_zero_of_one_runs_the_side_leg
     assert p["device_index"] == 0 and p["cpu_baseline"] and p["live_pmc"] and p["also"] and p["parity"]
     p = b.rank_plan(3, 3, 4, 1, args, 8192)  # a one-GPU box asked for four ranks (gloo, functional only): they share device 0 and say so
     assert p["device_index"] == 0 and p["shares_device"]
-    sub = b.parse_args(["--config", "3", "--gpus", "1", "--sub", "--no-cpu-baseline"])
+    sub = b.parse_args(["--config", "3", "--gpus", "1", "--sub", "--no-cpu-baseline", "--full"])
     p = b.rank_plan(0, 0, 1, 1, sub, 65536)
     assert p["parity"] and not (p["cpu_baseline"] or p["live_pmc"] or p["also"])  # an `also` run: its own parity sample, nothing else
+    for argv in ([], ["--gpus", "1", "--steps", "20", "--warmup", "5"], ["--config", "3", "--gpus", "1"]):  # a plain run: the timed region only
+        plain = b.parse_args(argv)
+        p = b.rank_plan(0, 0, 1, 1, plain, plain.fft)
+        assert not plain.full and not (p["cpu_baseline"] or p["live_pmc"] or p["also"] or p["parity"]), (argv, p)
 
 
 def test_kernel_tally_is_per_launch():
@@ -143,3 +147,30 @@ def test_the_line_the_driver_parses_is_a_few_kb_whatever_the_run_measured():
     assert len(json.dumps(b.compact_line(fat))) < 6500
     # a CPU-only line (config 1) and a multi-rank line (no side legs) go through as well
     assert b.compact_line({"metric": "m", "value": 1.0, "roofline": None, "cpu_baseline": None, "config": {"workload": "x"}})["roofline"] is None
+
+
+def test_dumped_outputs_are_float_within_the_limit_and_the_same_every_time(tmp_path):
+    """--dump-outputs: the candidate lists whole (integers exactly, as float64), the planes whole while everything fits in the
+    limit and otherwise the same seeded sample of frames of every plane, with the frames' indices beside them."""
+    import numpy as np
+    b = _bench()
+    a = b.parse_args(["--dump-outputs", str(tmp_path)])
+    assert a.dump_outputs == str(tmp_path) and b.parse_args([]).dump_outputs is None
+    rng = np.random.default_rng(1)
+    psd = rng.standard_normal((64, 256)).astype(np.float32)
+    off = np.arange(65, dtype=np.int32) * 3
+    idx = rng.integers(0, 256, off[-1], dtype=np.int32)
+    lists = {"cand_off": off, "cand_idx": idx, "cand_avg": rng.standard_normal(off[-1]).astype(np.float32)}
+    shapes = b.dump_outputs(str(tmp_path / "whole"), {"psd": psd}, lists)
+    assert shapes == {"cand_off": (65,), "cand_idx": (192,), "cand_avg": (192,), "psd": (64, 256)}
+    got = {k: np.load(tmp_path / "whole" / f"{k}.npy") for k in shapes}
+    assert got["cand_off"].dtype == np.float64 and np.array_equal(got["cand_off"], off) and np.array_equal(got["cand_idx"], idx)
+    assert got["cand_avg"].dtype == np.float32 and got["psd"].dtype == np.float32 and np.array_equal(got["psd"], psd)
+    limit = 40 * 1024
+    for d in ("s1", "s2"):
+        shapes = b.dump_outputs(str(tmp_path / d), {"psd": psd, "rel": psd + 1}, lists, limit=limit)
+        assert sum(os.path.getsize(tmp_path / d / f"{k}.npy") for k in shapes) <= limit + 128 * len(shapes)  # (+ the .npy headers)
+    rows = np.load(tmp_path / "s1" / "plane_frames.npy")
+    assert 0 < rows.size < 64 and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.load(tmp_path / "s2" / "plane_frames.npy"))
+    r = rows.astype(int)
+    assert np.array_equal(np.load(tmp_path / "s1" / "psd.npy"), psd[r]) and np.array_equal(np.load(tmp_path / "s1" / "rel.npy"), psd[r] + 1)

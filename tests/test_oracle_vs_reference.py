@@ -1,7 +1,8 @@
 """Pin the C oracle (oracle/specscan_oracle.c) on the whole chain:
   * against committed golden vectors produced by the reference's own compiled sources
     (tests/golden/make_golden.py -> oracle/_ref), bit for bit;
-  * live against oracle/_ref where it is built, on further seeds / sizes, bit for bit.
+  * against oracle/_ref on further seeds / sizes, bit for bit: live where it is built, its recorded results
+    (tests/golden/reference/, refrecords.py) otherwise.
 Both sides use the same restated fft_v (the FFT itself lives in GNU Radio/FFTW, un-vendored), so every
 difference would come from the reference-owned stages: PSD, NoiseLearner, Averager, average(),
 candidate predicate."""
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 
 import rtl_sdr_scanner_cpp_amd as pkg
+from refrecords import assert_same, reference
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "ref_chain_*.npz")))
 
@@ -63,29 +65,31 @@ def test_oracle_matches_golden(oracle_mod, path, chunk):
 
 
 @pytest.mark.parametrize("n,fs,seed", [(64, 16000, 11), (512, 128000, 12), (2048, 2048000 // 4, 13)])
-def test_oracle_matches_live_reference(ref_mod, n, fs, seed):
-    O = ref_mod
+def test_oracle_matches_live_reference(oracle_mod, n, fs, seed):
+    O = oracle_mod
     center = 433_000_000
     nframes = 150
     band = pkg.synth.SyntheticBand(n, seed=seed, on_frame=70, off_frame=130, comb_width=16)
     iq = band.frames_cf32(nframes)
     t = (5_000 + 40 * np.arange(nframes)).astype(np.int64)
-    O.ref().orc_set_fft_backend(0)
-    ref = O.RefChain(n, fs, center - fs // 2, center + fs // 2)
-    r = ref.process(iq, t)
+
+    def live():
+        O.ref().orc_set_fft_backend(0)
+        return O.RefChain(n, fs, center - fs // 2, center + fs // 2).process(iq, t)
+    r = reference(O, f"chain_live_{n}_{fs}_{seed}", live, keep=("psd", "rel", "avg", "cands"))
     psd, rel, avg, off, idx, _ = _run_oracle(O, iq, t, n, fs, center, (), None, 32)
-    np.testing.assert_array_equal(psd, r["psd"])
-    np.testing.assert_array_equal(rel, r["rel"])
-    np.testing.assert_array_equal(avg, r["avg"])
+    assert_same(psd, r["psd"])
+    assert_same(rel, r["rel"])
+    assert_same(avg, r["avg"])
     for f in range(nframes):
         np.testing.assert_array_equal(idx[off[f]:off[f + 1]], r["cands"][f])
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("SS_ORACLE_SEEDS", "8"))))
-def test_oracle_matches_live_reference_on_random_runs(ref_mod, seed):
+def test_oracle_matches_live_reference_on_random_runs(oracle_mod, seed):
     """Random size, frame period, ignored ranges, call sizes and a retune with reset at a random frame: the restated chain
     against the reference's own compiled PSD / NoiseLearner / Transmission, bit for bit, frame by frame."""
-    O = ref_mod
+    O = oracle_mod
     rng = np.random.default_rng(300 + seed)
     n = int(rng.choice([64, 128, 256, 512, 1024]))
     fs = n * int(rng.choice([125, 250, 500]))
@@ -101,22 +105,27 @@ def test_oracle_matches_live_reference_on_random_runs(ref_mod, seed):
         ignored = (lo, lo + fs // 16)
     retune_at = int(rng.integers(nframes // 2, nframes - 40)) if rng.random() < 0.5 else None
     chunk = int(rng.choice([1, 5, 33, 64]))
-    O.ref().orc_set_fft_backend(0)
-    ref = O.RefChain(n, fs, center - fs // 2, center + fs // 2, ignored=ignored)
-    parts = []
-    if retune_at is None:
-        parts.append(ref.process(iq, t))
-    else:
-        parts.append(ref.process(iq[:retune_at], t[:retune_at]))
-        ref.set_range(center + fs - fs // 2, center + fs + fs // 2)  # SdrDevice::setFrequencyRange + Transmission::resetBuffers
-        ref.reset()
-        parts.append(ref.process(iq[retune_at:], t[retune_at:]))
-    r = {k: np.concatenate([p_[k] for p_ in parts]) for k in ("psd", "rel", "avg")}
-    cands = [c for p_ in parts for c in p_["cands"]]
+
+    def live():
+        O.ref().orc_set_fft_backend(0)
+        ref = O.RefChain(n, fs, center - fs // 2, center + fs // 2, ignored=ignored)
+        parts = []
+        if retune_at is None:
+            parts.append(ref.process(iq, t))
+        else:
+            parts.append(ref.process(iq[:retune_at], t[:retune_at]))
+            ref.set_range(center + fs - fs // 2, center + fs + fs // 2)  # SdrDevice::setFrequencyRange + Transmission::resetBuffers
+            ref.reset()
+            parts.append(ref.process(iq[retune_at:], t[retune_at:]))
+        r = {k: np.concatenate([p_[k] for p_ in parts]) for k in ("psd", "rel", "avg")}
+        r["cands"] = [c for p_ in parts for c in p_["cands"]]
+        return r
+    r = reference(O, f"chain_random_{seed}", live)
+    cands = r["cands"]
     psd, rel, avg, off, idx, _ = _run_oracle(O, iq, t, n, fs, center, ignored, retune_at, chunk)
-    np.testing.assert_array_equal(psd, r["psd"])
-    np.testing.assert_array_equal(rel, r["rel"])
-    np.testing.assert_array_equal(avg, r["avg"])
+    assert_same(psd, r["psd"])
+    assert_same(rel, r["rel"])
+    assert_same(avg, r["avg"])
     for f in range(nframes):
         np.testing.assert_array_equal(idx[off[f]:off[f + 1]], cands[f], err_msg=f"seed {seed} frame {f}")
 

@@ -1,5 +1,6 @@
 """Host-side signal tracker (host/signal_tracker.cpp) against the reference's own Transmission / Signal code
-(oracle/_ref, compiled in place from /root/reference/sources): the list handed to Notification::notify
+(oracle/_ref, compiled in place from the reference's sources; its results recorded under tests/golden/reference/ where
+that library is not built): the list handed to Notification::notify
 (transmission.cpp:67) — tuned frequency shifts and flush flags, strongest first — and the tracked signal keys
 must be identical, frame by frame. Integer work: bit-exact. Runs on the CPU: the tracker takes planes and
 candidates from whoever produced them (here the oracle, whose planes equal the reference's bit for bit)."""
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 import rtl_sdr_scanner_cpp_amd as pkg
+from refrecords import reference
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "ref_tracker_*.npz")))
 
@@ -29,14 +31,16 @@ def _track(O, iq, t, n, fs, center, **tk):
 
 
 @pytest.mark.parametrize("n,fs,seed,min_ms,timeout_ms", [(256, 64_000, 31, 2000, 2000), (1024, 256_000, 32, 400, 600), (512, 128_000, 33, 0, 40)])
-def test_tracker_matches_reference_live(ref_mod, n, fs, seed, min_ms, timeout_ms):
-    O = ref_mod
+def test_tracker_matches_reference_live(oracle_mod, n, fs, seed, min_ms, timeout_ms):
+    O = oracle_mod
     center, nframes, dt = 145_000_000, 330, 40
     iq, t = _scenario(n, fs, seed, nframes, on=70, off=190, dt=dt)
-    O.ref().orc_set_fft_backend(0)
+
+    def live():
+        O.ref().orc_set_fft_backend(0)
+        return O.RefChain(n, fs, center - fs // 2, center + fs // 2, min_time_ms=min_ms, timeout_ms=timeout_ms).process(iq, t)
+    want = reference(O, f"tracker_live_{n}_{fs}_{seed}", live, keep=("tx", "signals"))
     O.lib().orc_set_fft_backend(0)
-    ref = O.RefChain(n, fs, center - fs // 2, center + fs // 2, min_time_ms=min_ms, timeout_ms=timeout_ms)
-    want = ref.process(iq, t)
     got = _track(O, iq, t, n, fs, center, min_time_ms=min_ms, timeout_ms=timeout_ms)
     seen_tx = seen_flush = 0
     for f in range(nframes):
@@ -76,11 +80,11 @@ def test_reset_clears_signals_and_ring(oracle_mod):
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("SS_TRACKER_SEEDS", "10"))))
-def test_tracker_matches_reference_on_random_traffic(ref_mod, seed):
+def test_tracker_matches_reference_on_random_traffic(oracle_mod, seed):
     """Random bursts (position, width, level, start, duration — overlapping, adjacent, re-appearing inside the margin of an
     old signal), random frame period, timeouts, tuning step and recording bandwidth: the tracker against the reference's own
     compiled Transmission/Signal on every frame."""
-    O = ref_mod
+    O = oracle_mod
     rng = np.random.default_rng(600 + seed)
     n = int(rng.choice([256, 512, 1024]))
     fs = n * 250
@@ -107,10 +111,13 @@ def test_tracker_matches_reference_on_random_traffic(ref_mod, seed):
             x[f] += level * tone
     iq = x.astype(np.complex64)
     t = (5_000 + dt * np.arange(nframes)).astype(np.int64)
-    O.ref().orc_set_fft_backend(0)
+
+    def live():
+        O.ref().orc_set_fft_backend(0)
+        return O.RefChain(n, fs, center - fs // 2, center + fs // 2, min_time_ms=min_ms, timeout_ms=timeout_ms, tuning_step=step,
+                          bandwidth=bandwidth).process(iq, t)
+    want = reference(O, f"tracker_random_{seed}", live, keep=("tx", "signals"))
     O.lib().orc_set_fft_backend(0)
-    ref = O.RefChain(n, fs, center - fs // 2, center + fs // 2, min_time_ms=min_ms, timeout_ms=timeout_ms, tuning_step=step, bandwidth=bandwidth)
-    want = ref.process(iq, t)
     ch = O.oracle_chain(fs, center, fft_size=n, decim=1, max_batch=nframes)
     r = ch.process(iq, t_ms=t)
     tr = pkg.tracker.SignalTracker(n, fs, min_time_ms=min_ms, timeout_ms=timeout_ms, tuning_step=step, bandwidth=bandwidth)
