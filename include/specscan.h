@@ -47,13 +47,19 @@ typedef enum ss_status {
 } ss_status;
 
 /* Sample format of the IQ stream handed to ss_process. The reference always asks SoapySDR for CF32
- * (sources/radio/blocks/sdr_source.cpp:52,75); CS8/CU8 are what RTL-SDR/HackRF produce natively, and
- * the engine converts them in the FFT kernel's load stage: cf32 = (int8 - offset) * int_scale. */
+ * (sources/radio/blocks/sdr_source.cpp:52,75); CS8/CU8 are what RTL-SDR/HackRF produce natively, CS16 what
+ * most other SoapySDR devices do, and the engine converts them in the FFT kernel's load stage:
+ * cf32 = (int - offset) * int_scale. CS16's default scale 1/32768 is a power of two, so every int16 converts
+ * exactly; a 12-bit device (PlutoSDR) may pass 1/2048 for full scale 1.0. */
 typedef enum ss_format {
   SS_FMT_CF32 = 0, /* interleaved float re,im  (gr_complex)            8 B/sample */
   SS_FMT_CS8 = 1,  /* interleaved int8  re,im  (HackRF)                2 B/sample */
-  SS_FMT_CU8 = 2   /* interleaved uint8 re,im, offset 127.5 (RTL-SDR)  2 B/sample */
+  SS_FMT_CU8 = 2,  /* interleaved uint8 re,im, offset 127.5 (RTL-SDR)  2 B/sample */
+  SS_FMT_CS16 = 3  /* interleaved int16 re,im, little-endian (SDRplay, Airspy, LimeSDR, USRP, Pluto), 4 B/sample */
 } ss_format;
+
+/* Bytes per IQ sample of an ss_format. */
+#define SS_FMT_BYTES(fmt) ((fmt) == SS_FMT_CF32 ? 8 : (fmt) == SS_FMT_CS16 ? 4 : 2)
 
 /* Which per-bin plane ss_read_window returns. */
 typedef enum ss_plane {
@@ -98,7 +104,8 @@ typedef struct ss_config {
   int32_t decim;       /* D >= 1: an input item is N*D samples and only the first N are used
                           (sdr_device.cpp:152, decimator.h:15-22)                              */
   int32_t in_format;   /* ss_format */
-  float int_scale;     /* CS8/CU8 -> float scale; 0 selects 1/128 (CS8) or 1/127.5 (CU8)       */
+  float int_scale;     /* CS8/CU8/CS16 -> float scale; 0 selects 1/128 (CS8), 1/127.5 (CU8) or
+                          1/32768 (CS16)                                                       */
   const float* window; /* N taps, or NULL for gr::fft::window::hamming(N) (sdr_device.cpp:164)  */
   int32_t grouping_x;  /* bins averaged in frequency, odd; GROUPING_X = 21 (config.h:28)        */
   int32_t grouping_y;  /* frames averaged in time;       GROUPING_Y = 21 (config.h:29)          */

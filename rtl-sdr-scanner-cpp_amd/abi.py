@@ -9,7 +9,8 @@ import numpy as np
 
 SS_ABI_VERSION = 3
 SS_OK, SS_ERR_INVALID, SS_ERR_NO_DEVICE, SS_ERR_HIP, SS_ERR_BATCH, SS_ERR_CAND_OVERFLOW, SS_ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6
-SS_FMT_CF32, SS_FMT_CS8, SS_FMT_CU8 = 0, 1, 2
+SS_FMT_CF32, SS_FMT_CS8, SS_FMT_CU8, SS_FMT_CS16 = 0, 1, 2, 3
+SS_FMT_BYTES = {SS_FMT_CF32: 8, SS_FMT_CS8: 2, SS_FMT_CU8: 2, SS_FMT_CS16: 4}  # bytes per IQ sample (SS_FMT_BYTES in specscan.h)
 SS_PLANE_PSD, SS_PLANE_REL, SS_PLANE_AVG = 0, 1, 2
 SS_FLAG_KEEP_PLANES = 1
 SS_FLAG_SPECTROGRAM = 2
@@ -150,10 +151,10 @@ class Chain:
             pass
 
     def _iq_bytes_per_item(self):
-        return self.item * (8 if self.cfg.in_format == SS_FMT_CF32 else 2)
+        return self.item * SS_FMT_BYTES[self.cfg.in_format]
 
     def process(self, iq: np.ndarray, t_ms=None, want=("psd", "rel", "avg"), cand_cap=None):
-        """iq: [nframes, N*D] complex64, or [nframes, N*D, 2] int8/uint8. Returns a dict with the
+        """iq: [nframes, N*D] complex64, or [nframes, N*D, 2] int8/uint8/int16. Returns a dict with the
         requested planes [nframes, N], ``cand_off`` [nframes+1], ``cand_idx``, ``cand_avg``."""
         iq = np.ascontiguousarray(iq)
         nframes = 0 if iq.size == 0 else iq.shape[0]

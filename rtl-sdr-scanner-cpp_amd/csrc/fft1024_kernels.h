@@ -125,7 +125,7 @@ __device__ __forceinline__ void fft_cols1024_tile(const ColsArgs& g, int block, 
   // first half: sub-sequence q of column c, butterfly j of its 256-point FFT — sample n1 = 4 (j + 16 r) + q of column c0 + c
   const int sub = t & (NSUB - 1), j = t >> (LOGC + 2);
   const int c = sub & (COLS - 1), q = sub >> LOGC;
-  constexpr int kIn = FMT == FMT_CF32 ? 8 : 2;
+  constexpr int kIn = fmt_bytes(FMT);
   const uint32_t tn = ((uint32_t)(4 * j + q) << 10) + (uint32_t)(c0 + c);
   const __amdgpu_buffer_rsrc_t rin = buffer_of(reinterpret_cast<const char*>(g.iq) + (size_t)f * (size_t)g.item_stride * kIn, (1 << 20) * kIn);
   // The window taps come in THIS kernel's order (fft1024_window_order, built once per context from whatever taps the context has):
@@ -152,7 +152,10 @@ __device__ __forceinline__ void fft_cols1024_tile(const ColsArgs& g, int block, 
     float2 x;
     if constexpr (FMT == FMT_CF32) {
       x = buffer_load_f2<2>(rin, (int)(tn * 8u), r * (65536 * 8));
+    } else if constexpr (FMT == FMT_CS16) {
+      x = cs16_to_f2((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rin, (int)(tn * 4u), r * (65536 * 4), 2), g.scale);
     } else {
+      static_assert(fmt_int8(FMT), "input format");
       const unsigned short raw = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rin, (int)(tn * 2u), r * (65536 * 2), 2);
       if constexpr (FMT == FMT_CS8) x = make_float2((float)(signed char)(raw & 0xff) * g.scale, (float)(signed char)(raw >> 8) * g.scale);
       else x = make_float2(((float)(raw & 0xff) - 127.5f) * g.scale, ((float)(raw >> 8) - 127.5f) * g.scale);

@@ -504,7 +504,7 @@ __device__ __forceinline__ void fft8192_v2_frame(const Fft8192Args& g, size_t fr
     (void)scale;
     (void)in_base;
   } else {
-    constexpr int kSample = FMT == FMT_CF32 ? 8 : 2;  // bytes per IQ sample
+    constexpr int kSample = fmt_bytes(FMT);  // bytes per IQ sample
     const __amdgpu_buffer_rsrc_t rin = buffer_of(reinterpret_cast<const char*>(iq) + in_base * kSample, 8192 * kSample);
     const __amdgpu_buffer_rsrc_t rwin = buffer_of(win, 8192 * 4);
 #pragma unroll
@@ -512,7 +512,10 @@ __device__ __forceinline__ void fft8192_v2_frame(const Fft8192Args& g, size_t fr
       float2 x;
       if constexpr (FMT == FMT_CF32) {
         x = buffer_load_f2<SS_AUX_IQ>(rin, t * 8, 4096 * r);
+      } else if constexpr (FMT == FMT_CS16) {
+        x = cs16_to_f2((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rin, t * 4, 2048 * r, SS_AUX_IQ), scale);
       } else {
+        static_assert(fmt_int8(FMT), "input format");
         const unsigned short raw = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rin, t * 2, 1024 * r, SS_AUX_IQ);
         if constexpr (FMT == FMT_CS8) x = make_float2((float)(signed char)(raw & 0xff) * scale, (float)(signed char)(raw >> 8) * scale);
         else x = make_float2(((float)(raw & 0xff) - 127.5f) * scale, ((float)(raw >> 8) - 127.5f) * scale);

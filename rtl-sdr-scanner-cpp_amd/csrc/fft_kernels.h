@@ -16,7 +16,17 @@ namespace ss {
 
 constexpr int kFftThreads = 256;
 
-enum { FMT_CF32 = 0, FMT_CS8 = 1, FMT_CU8 = 2 };
+enum { FMT_CF32 = 0, FMT_CS8 = 1, FMT_CU8 = 2, FMT_CS16 = 3 };  // (= ss_format)
+
+// Bytes per IQ sample of an input format, and whether it is one of the two-byte (int8) formats — the only ones the radix-8/16
+// fold (fft65536_dif8.h) reads: CS16 takes CF32's path everywhere and differs from it in the load stage alone.
+__host__ __device__ constexpr int fmt_bytes(int fmt) { return fmt == FMT_CF32 ? 8 : fmt == FMT_CS16 ? 4 : 2; }
+__host__ __device__ constexpr bool fmt_int8(int fmt) { return fmt == FMT_CS8 || fmt == FMT_CU8; }
+
+// One CS16 sample as the 32-bit word it arrives in (little-endian: I in the low half, Q in the high half), sign-extended.
+__device__ __forceinline__ float2 cs16_to_f2(uint32_t raw, float scale) {
+  return make_float2((float)(short)(raw & 0xffffu) * scale, (float)((int)raw >> 16) * scale);
+}
 
 // The fused form is spelled out: left to -ffp-contract the compiler picks which of the two products goes into the FMA per
 // call site, and two copies of the same butterfly (the unrolled halves of k_fft256xR_psd<3>) then round differently — a
@@ -36,7 +46,10 @@ __device__ __forceinline__ float2 load_iq(const void* __restrict__ base, size_t 
   } else if constexpr (FMT == FMT_CS8) {
     const char2 c = reinterpret_cast<const char2*>(base)[idx];
     return make_float2((float)c.x * scale, (float)c.y * scale);
+  } else if constexpr (FMT == FMT_CS16) {
+    return cs16_to_f2(reinterpret_cast<const uint32_t*>(base)[idx], scale);
   } else {
+    static_assert(FMT == FMT_CU8, "input format");
     const uchar2 c = reinterpret_cast<const uchar2*>(base)[idx];
     return make_float2(((float)c.x - 127.5f) * scale, ((float)c.y - 127.5f) * scale);
   }

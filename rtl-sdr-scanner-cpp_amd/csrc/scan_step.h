@@ -261,7 +261,7 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
     // ---- FFT role, long transforms: one tile of 32 columns x 256 rows (KIND 3: 8 columns x 1024 rows of a 2^20-point frame) ----
     if constexpr (KIND == 5) return;  // (the drain of a 2^20-point context: launches without an FFT role only)
     else if constexpr (KIND == 8) {  // a residue of a 65536-point frame: fold + 8192-point transform + dB -> the ring's rows
-      if constexpr (FMT != FMT_CF32) {
+      if constexpr (fmt_int8(FMT)) {
         int f, r, hdr;
         dif8_item<SS_DIF8_W>(item, a.dif.nframes, &f, &r);  // (W = 4: residues r and r + 4 by this workgroup)
 #ifdef SS_DIAG
@@ -271,14 +271,14 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
       }
     }
     else if constexpr (KIND == 11) {  // a 65536-point frame's residue r alone: eight workgroups per frame (short calls, round 6)
-      if constexpr (FMT != FMT_CF32) {
+      if constexpr (fmt_int8(FMT)) {
         int f, r, hdr;
         dif8_item<8>(item, a.dif.nframes, &f, &r);
         fft8192_v2_frame<FMT, 2, true, false, 2>(a.fft, (size_t)(8 * (f - a.dif.first_hist) + r), smem_raw, tid, &hdr, &a.dif, (size_t)f, r);
       }
     }
     else if constexpr (KIND == 9) {  // 131072 points, radix 16: residues r (< 8) and r + 8 of a frame, eight workgroups per frame
-      if constexpr (FMT != FMT_CF32) {
+      if constexpr (fmt_int8(FMT)) {
         int f, r, hdr;
         dif8_item<8>(item, a.dif.nframes, &f, &r);
         fft8192_v2_frame<FMT, 2, true, false, SS_DIF8_BFLY ? 6 : 4>(a.fft, (size_t)(16 * (f - a.dif.first_hist) + r), smem_raw, tid, &hdr, &a.dif, (size_t)f, r);

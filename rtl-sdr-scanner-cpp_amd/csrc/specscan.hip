@@ -589,7 +589,8 @@ hipError_t stream_wait(hipStream_t stream) {
   return hipStreamSynchronize(stream);
 }
 
-size_t in_bytes_per_sample(int fmt) { return fmt == SS_FMT_CF32 ? 8 : 2; }
+static_assert(ss::FMT_CF32 == SS_FMT_CF32 && ss::FMT_CS8 == SS_FMT_CS8 && ss::FMT_CU8 == SS_FMT_CU8 && ss::FMT_CS16 == SS_FMT_CS16, "ss_format");
+size_t in_bytes_per_sample(int fmt) { return (size_t)ss::fmt_bytes(fmt); }
 
 // getFft — sources/utils/radio_utils.cpp:98-104
 int get_fft(int32_t sample_rate, int32_t max_step) {
@@ -739,12 +740,14 @@ void launch_cols1024_fmt(ss_ctx* c, const void* d_iq, long long item_stride, int
   else go(ss::k_fft_cols1024<FMT, 3>, 128, 512, ss::kFft1024ColsLdsBytes);
 }
 void launch_cols1024(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, int frame0 = 0) {
-  const size_t sample = c->cfg.in_format == SS_FMT_CF32 ? 8 : 2;
+  const size_t sample = in_bytes_per_sample(c->cfg.in_format);
   const void* iq = static_cast<const char*>(d_iq) + (size_t)frame0 * (size_t)item_stride * sample;
   switch (c->cfg.in_format) {
     case SS_FMT_CF32: return launch_cols1024_fmt<ss::FMT_CF32>(c, iq, item_stride, nframes, frame0);
     case SS_FMT_CS8: return launch_cols1024_fmt<ss::FMT_CS8>(c, iq, item_stride, nframes, frame0);
-    default: return launch_cols1024_fmt<ss::FMT_CU8>(c, iq, item_stride, nframes, frame0);
+    case SS_FMT_CU8: return launch_cols1024_fmt<ss::FMT_CU8>(c, iq, item_stride, nframes, frame0);
+    case SS_FMT_CS16: return launch_cols1024_fmt<ss::FMT_CS16>(c, iq, item_stride, nframes, frame0);
+    default: fail(c, SS_ERR_INVALID, "in_format %d", c->cfg.in_format); return;
   }
 }
 ss::Rows1024Args rows1024_args(ss_ctx* c, float* d_psd, const ss::RowsExtra& rx) {
@@ -952,7 +955,7 @@ void launch_step_variant(ss_ctx* c, const ss::StepArgs& a, hipEvent_t e0, hipEve
   // (KIND 5: a launch without an FFT role — the drain — whose detect workgroups share the plan's list out in a loop)
   if (c->two_pass && a.list_loop) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, 5>);
   if (c->two_pass) return c->diag.cols1024_wide ? go(ss::k_scan_step<FMT, SPEC, 2, true, false, 4>) : go(ss::k_scan_step<FMT, SPEC, 2, true, false, 3>);
-  if constexpr (FMT != ss::FMT_CF32 && !SPEC) {  // (the fold's launches, and the drains of the stages that wait behind them: their tiles read the fold's rows)
+  if constexpr (ss::fmt_int8(FMT) && !SPEC) {  // (the fold's launches, and the drains of the stages that wait behind them: their tiles read the fold's rows)
 #ifdef SS_DIAG
     if (!c->use_fft8192 && c->ring_perm8 && c->dif_logq == 3 && (c->diag.prio_fft || c->diag.prio_other)) return go(ss::k_scan_step<FMT, SPEC, 2, true, true, 8>);
 #endif
@@ -1097,7 +1100,9 @@ void launch_step(ss_ctx* c, const FftRole* fft, const ss::DetectArgs* det, int n
   switch (c->cfg.in_format) {
     case SS_FMT_CF32: sp ? launch_step_variant<ss::FMT_CF32, true>(c, a, e0, e1, stream) : launch_step_variant<ss::FMT_CF32, false>(c, a, e0, e1, stream); break;
     case SS_FMT_CS8: sp ? launch_step_variant<ss::FMT_CS8, true>(c, a, e0, e1, stream) : launch_step_variant<ss::FMT_CS8, false>(c, a, e0, e1, stream); break;
-    default: sp ? launch_step_variant<ss::FMT_CU8, true>(c, a, e0, e1, stream) : launch_step_variant<ss::FMT_CU8, false>(c, a, e0, e1, stream); break;
+    case SS_FMT_CU8: sp ? launch_step_variant<ss::FMT_CU8, true>(c, a, e0, e1, stream) : launch_step_variant<ss::FMT_CU8, false>(c, a, e0, e1, stream); break;
+    case SS_FMT_CS16: sp ? launch_step_variant<ss::FMT_CS16, true>(c, a, e0, e1, stream) : launch_step_variant<ss::FMT_CS16, false>(c, a, e0, e1, stream); break;
+    default: fail(c, SS_ERR_INVALID, "in_format %d", c->cfg.in_format); break;
   }
 #ifdef SS_DIAG
   if (dump_stamps) {
@@ -1387,7 +1392,9 @@ int launch_fft(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, 
   switch (c->cfg.in_format) {
     case SS_FMT_CF32: return launch_fft_fmt<ss::FMT_CF32>(c, d_iq, item_stride, nframes, d_psd);
     case SS_FMT_CS8: return launch_fft_fmt<ss::FMT_CS8>(c, d_iq, item_stride, nframes, d_psd);
-    default: return launch_fft_fmt<ss::FMT_CU8>(c, d_iq, item_stride, nframes, d_psd);
+    case SS_FMT_CU8: return launch_fft_fmt<ss::FMT_CU8>(c, d_iq, item_stride, nframes, d_psd);
+    case SS_FMT_CS16: return launch_fft_fmt<ss::FMT_CS16>(c, d_iq, item_stride, nframes, d_psd);
+    default: return fail(c, SS_ERR_INVALID, "in_format %d", c->cfg.in_format);
   }
 }
 
@@ -2071,7 +2078,7 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
       // A call of many frames goes through in chunks of 256 (a chunk's work buffer: 128 MiB, still in the Infinity Cache when its row
       // half reads it: the row half of a 512-frame call took 0.206 us per frame against 0.132, profiles/r04/s28_summary.txt); the
       // deferred stages ride on the first chunk's launches.
-      const size_t sample = c->cfg.in_format == SS_FMT_CF32 ? 8 : 2;
+      const size_t sample = in_bytes_per_sample(c->cfg.in_format);
       const int chunk = (c->diag.chunk_65536 > 0 && nframes > c->diag.chunk_65536) ? c->diag.chunk_65536 : nframes;
       for (int f0 = 0; f0 < nframes; f0 += chunk) {
         const int nf = std::min(chunk, nframes - f0);
@@ -2099,7 +2106,7 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
       // 262144 points (round 6): the 65536-point two-launch pipeline — the column launch of call k (256-point column tiles as k_scan_step's
       // FFT role) carries the plan of call k - 1, detect(k - 2) on the tiles that plan listed and emit(k - 3); the row half is a launch of
       // k_fft_rows1024_psd<8> that carries nothing. Calls of more than 64 frames go through in chunks (a chunk's work buffer: 128 MiB).
-      const size_t sample = c->cfg.in_format == SS_FMT_CF32 ? 8 : 2;
+      const size_t sample = in_bytes_per_sample(c->cfg.in_format);
       const int chunk = std::min(nframes, 64);
       for (int f0 = 0; f0 < nframes; f0 += chunk) {
         const int nf = std::min(chunk, nframes - f0);
@@ -2458,7 +2465,7 @@ int ss_create(const ss_config* cfg, ss_ctx** out) {
     return fail(nullptr, SS_ERR_INVALID, "fft_size %d must be a power of two in [64, 2^20]", cfg->fft_size);
   if (cfg->sample_rate <= 0 || cfg->decim < 1 || cfg->max_batch < 1 || cfg->n_ignored < 0 || cfg->learn_frames < 1 ||
       cfg->grouping_y < 1 || cfg->grouping_x < 1 || (cfg->grouping_x & 1) == 0 || cfg->grouping_x > 1025 ||
-      cfg->in_format < SS_FMT_CF32 || cfg->in_format > SS_FMT_CU8 || (cfg->n_ignored > 0 && !cfg->ignored))
+      cfg->in_format < SS_FMT_CF32 || cfg->in_format > SS_FMT_CS16 || (cfg->n_ignored > 0 && !cfg->ignored))
     return fail(nullptr, SS_ERR_INVALID, "invalid ss_config field");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, SS_ERR_NO_DEVICE, "no HIP device available");
@@ -2475,7 +2482,7 @@ int ss_create(const ss_config* cfg, ss_ctx** out) {
   c->range_lo = cfg->range_lo;
   c->range_hi = cfg->range_hi;
   c->ignored.assign(cfg->ignored, cfg->ignored + 2 * (size_t)cfg->n_ignored);
-  if (c->cfg.int_scale == 0.0f) c->cfg.int_scale = cfg->in_format == SS_FMT_CU8 ? 1.0f / 127.5f : 1.0f / 128.0f;
+  if (c->cfg.int_scale == 0.0f) c->cfg.int_scale = cfg->in_format == SS_FMT_CU8 ? 1.0f / 127.5f : cfg->in_format == SS_FMT_CS16 ? 1.0f / 32768.0f : 1.0f / 128.0f;
 
   const int n = c->n;
   const int G = cfg->grouping_y;

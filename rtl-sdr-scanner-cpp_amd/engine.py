@@ -207,7 +207,7 @@ class Feed:
         self._h = h
         cfg = engine.cfg
         self._shape = (cfg.max_batch, cfg.fft_size) if cfg.in_format == abi.SS_FMT_CF32 else (cfg.max_batch, cfg.fft_size, 2)
-        self._dtype = {abi.SS_FMT_CF32: np.complex64, abi.SS_FMT_CS8: np.int8, abi.SS_FMT_CU8: np.uint8}[cfg.in_format]
+        self._dtype = {abi.SS_FMT_CF32: np.complex64, abi.SS_FMT_CS8: np.int8, abi.SS_FMT_CU8: np.uint8, abi.SS_FMT_CS16: np.int16}[cfg.in_format]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -225,7 +225,7 @@ class Feed:
         return int(self._lib.ss_feed_pending(self._h))
 
     def acquire(self) -> np.ndarray:
-        """[max_batch, N] complex64 (or [max_batch, N, 2] int8/uint8) view of the next free pinned slot: frames
+        """[max_batch, N] complex64 (or [max_batch, N, 2] int8/uint8/int16) view of the next free pinned slot: frames
         already decimated (the first N samples of each N*D item)."""
         p = C.c_void_p()
         self._e._check(self._lib.ss_feed_acquire(self._h, C.byref(p)))

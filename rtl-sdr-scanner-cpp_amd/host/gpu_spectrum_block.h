@@ -4,7 +4,8 @@
 // through the C ABI of include/specscan.h. Header-only, C++17, depends on GNU Radio's sync_block only
 // (tests compile it against oracle/stubs/gnuradio/sync_block.h).
 //
-//   input  0: items of N*D gr_complex  (what stream_to_vector + Blocker deliver, sdr_device.cpp:161-162)
+//   input  0: items of N*D samples in config.in_format: gr_complex (what stream_to_vector + Blocker deliver,
+//             sdr_device.cpp:161-162), or 4-byte int16 pairs for SS_FMT_CS16, 2-byte int8 pairs for CS8/CU8
 //   output 0: items of N float, the raw PSD in dB (what PSD::work produced, psd.cpp:18-20) — feeds the
 //             Spectrogram side branch (sdr_device.cpp:170-171) unchanged
 //   candidates: per frame, the bins passing transmission.cpp:91 and their avg power, handed to a callback
@@ -47,7 +48,7 @@ class GpuSpectrum : virtual public gr::sync_block {
   using CandidateCallback = std::function<void(int frame, const int32_t* bins, const float* avg_db, int count)>;
 
   GpuSpectrum(const ss_config& config, CandidateCallback on_candidates)
-      : gr::sync_block("GpuSpectrum", gr::io_signature::make(1, 1, sizeof(gr_complex) * config.fft_size * config.decim),
+      : gr::sync_block("GpuSpectrum", gr::io_signature::make(1, 1, inputItemBytes(config)),
                        gr::io_signature::make(1, 1, sizeof(float) * config.fft_size)),
         m_config(config),
         m_onCandidates(std::move(on_candidates)) {
@@ -63,6 +64,12 @@ class GpuSpectrum : virtual public gr::sync_block {
   }
 
   ~GpuSpectrum() override { ss_destroy(m_ctx); }
+
+  // Bytes of one input item: N*D samples of the config's in_format (sizeof(gr_complex) each for CF32).
+  static int inputItemBytes(const ss_config& config) {
+    const int sample = config.in_format == SS_FMT_CF32 ? static_cast<int>(sizeof(gr_complex)) : SS_FMT_BYTES(config.in_format);
+    return sample * config.fft_size * config.decim;
+  }
 
   GpuSpectrum(const GpuSpectrum&) = delete;
   GpuSpectrum& operator=(const GpuSpectrum&) = delete;

@@ -66,7 +66,7 @@ int srf_sink_work(void* sink, const void* items, int nitems) {
 }
 
 void* srf_reader_open(const char* path, int kind, int fft_size, int decim) {
-  if (!path || fft_size <= 0 || kind < 0 || kind > 2) return nullptr;
+  if (!path || fft_size <= 0 || kind < 0 || kind > 4 || kind == (int)RawKind::F32) return nullptr;
   try {
     return new RawIqReader(path, (RawKind)kind, fft_size, decim);
   } catch (const std::exception&) {

@@ -29,7 +29,7 @@
 
 namespace specscan {
 
-enum class RawKind { CF32 = 0, CS8 = 1, CU8 = 2, F32 = 3 };
+enum class RawKind { CF32 = 0, CS8 = 1, CU8 = 2, F32 = 3, CS16 = 4 };
 
 struct RawFileInfo {
   std::string label;      // "full" or "recording"
@@ -57,7 +57,8 @@ inline std::string makeRawFileName(const char* label, const char* extension, int
 
 // The inverse. Accepts what getRawFileName writes and what converter.py accepts: the base name is split at '_' and
 // '.', fields are <label> <date> <time> <frequency> <rate> <extension...>; a `cs8` / `cu8` suffix or name ending
-// selects int8 IQ (converter.py:32-35), `power` selects float rows (converter.py:42-51 default), anything else cf32.
+// selects int8 IQ (converter.py:32-35), `cs16` interleaved little-endian int16 IQ (the native stream of most SoapySDR
+// devices; converter.py has no such case), `power` selects float rows (converter.py:42-51 default), anything else cf32.
 inline bool parseRawFileName(const std::string& path, RawFileInfo* out) {
   const size_t slash = path.find_last_of('/');
   const std::string base = slash == std::string::npos ? path : path.substr(slash + 1);
@@ -101,6 +102,7 @@ inline bool parseRawFileName(const std::string& path, RawFileInfo* out) {
   };
   if (last == "cs8" || has("cs8")) info.kind = RawKind::CS8;
   else if (last == "cu8" || has("cu8")) info.kind = RawKind::CU8;
+  else if (last == "cs16" || has("cs16")) info.kind = RawKind::CS16;
   else if (has("power")) info.kind = RawKind::F32;
   else info.kind = RawKind::CF32;
   *out = info;
@@ -112,6 +114,7 @@ inline size_t rawBytesPerValue(RawKind kind) {
     case RawKind::CF32: return 8;  // one complex sample
     case RawKind::CS8:
     case RawKind::CU8: return 2;
+    case RawKind::CS16: return 4;  // one int16 complex sample
     default: return 4;  // one float
   }
 }
@@ -259,7 +262,7 @@ extern "C" {
 // C binding (libspecscan_host.so). Strings are caller-owned buffers; returns are 0 / counts on success, <0 on error.
 int srf_make_name(const char* label, const char* extension, int32_t frequency, int32_t sample_rate, int year, int month, int day, int hour,
                   int minute, int second, char* out, int out_cap);
-// kind: 0 cf32, 1 cs8, 2 cu8, 3 f32 rows. label/extension buffers of at least 64 bytes.
+// kind: 0 cf32, 1 cs8, 2 cu8, 3 f32 rows, 4 cs16. label/extension buffers of at least 64 bytes.
 int srf_parse_name(const char* path, int32_t* frequency, int32_t* sample_rate, int* kind, int* ymdhms /*6 ints*/, char* label, char* extension);
 void* srf_sink_create(int64_t item_bytes);
 void srf_sink_destroy(void* sink);

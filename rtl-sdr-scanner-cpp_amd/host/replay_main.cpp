@@ -1,5 +1,5 @@
 // specscan_replay — a C++ host on the C ABI alone (include/specscan.h + host/raw_file.h), no Python, no GNU Radio:
-// streams one of the reference's raw IQ dumps (`full_<date>_<time>_<centre>_<rate>_fc.raw`, or .cs8 / .cu8;
+// streams one of the reference's raw IQ dumps (`full_<date>_<time>_<centre>_<rate>_fc.raw`, or .cs8 / .cu8 / .cs16;
 // sources/utils/radio_utils.cpp:78-84, scripts/converter.py:30-38) through the scan chain the way SdrDevice drives
 // it (sources/radio/sdr_device.cpp:148-168), with the pipelined feed: a reader thread fills pinned slots while
 // earlier batches cross PCIe and run. Optionally writes the raw PSD rows as the reference's DEBUG_SAVE_FULL_POWER
@@ -67,7 +67,7 @@ int main(int argc, char** argv) {
   }
   specscan::RawFileInfo info;
   if (!specscan::parseRawFileName(opt.path, &info) || info.kind == specscan::RawKind::F32) {
-    fprintf(stderr, "%s: not a raw IQ dump name (<label>_<date>_<time>_<centre>_<rate>_fc.raw | .cs8 | .cu8)\n", opt.path.c_str());
+    fprintf(stderr, "%s: not a raw IQ dump name (<label>_<date>_<time>_<centre>_<rate>_fc.raw | .cs8 | .cu8 | .cs16)\n", opt.path.c_str());
     return 2;
   }
   ss_config cfg;
@@ -79,6 +79,9 @@ int main(int argc, char** argv) {
   if (info.kind == specscan::RawKind::CS8 || info.kind == specscan::RawKind::CU8) {
     cfg.in_format = info.kind == specscan::RawKind::CS8 ? SS_FMT_CS8 : SS_FMT_CU8;
     cfg.int_scale = 1.0f / 127.5f;  // converter.py:33
+  } else if (info.kind == specscan::RawKind::CS16) {
+    cfg.in_format = SS_FMT_CS16;
+    cfg.int_scale = 1.0f / 32768.0f;
   }
   ss_ctx* ctx = nullptr;
   if (ss_create(&cfg, &ctx) != SS_OK) {

@@ -4,7 +4,7 @@
   and its inverse, with the field convention of the reference's own reader (scripts/converter.py:58-59);
 * ``RawFileSink`` — FileSink<T>(itemSize, flushable=false) (sources/radio/blocks/file_sink.h): what the reference
   attaches to its source (``_fc.raw``) and to PSD (``_power.raw``) at sources/radio/sdr_device.cpp:173-181;
-* ``RawIqReader`` — re-frames a ``_fc.raw`` / ``.cs8`` / ``.cu8`` dump into the frames the chain takes;
+* ``RawIqReader`` — re-frames a ``_fc.raw`` / ``.cs8`` / ``.cu8`` / ``.cs16`` dump into the frames the chain takes;
 * ``replay_file`` — a reader thread fills the engine's pinned slots while earlier batches cross PCIe and run
   (ss_feed_*, include/specscan.h); yields the per-batch results in order, and the end-to-end (file + PCIe inclusive)
   rate in ``ReplayStats``.
@@ -23,8 +23,10 @@ import numpy as np
 from . import abi
 from .tracker import load_host_library
 
-KIND_CF32, KIND_CS8, KIND_CU8, KIND_F32 = 0, 1, 2, 3
+KIND_CF32, KIND_CS8, KIND_CU8, KIND_F32, KIND_CS16 = 0, 1, 2, 3, 4
 CS8_FILE_SCALE = 1.0 / 127.5  # converter.py:33: np.int8 -> complex64 / 127.5
+CS16_FILE_SCALE = 1.0 / 32768  # int16 full scale (a power of two: every value converts exactly)
+_KIND_FMT = {KIND_CF32: abi.SS_FMT_CF32, KIND_CS8: abi.SS_FMT_CS8, KIND_CU8: abi.SS_FMT_CU8, KIND_CS16: abi.SS_FMT_CS16}
 
 
 def _lib():
@@ -141,7 +143,7 @@ class RawIqReader:
 
     def read(self, max_frames: int) -> np.ndarray:
         out = np.empty((max_frames, self.n), np.complex64) if self.kind == KIND_CF32 else \
-            np.empty((max_frames, self.n, 2), np.int8 if self.kind == KIND_CS8 else np.uint8)
+            np.empty((max_frames, self.n, 2), {KIND_CS8: np.int8, KIND_CU8: np.uint8, KIND_CS16: np.int16}[self.kind])
         return out[: self.read_into(out, max_frames)]
 
     def close(self):
@@ -175,6 +177,8 @@ def engine_overrides_for(info: RawFileInfo) -> dict:
         return {"in_format": abi.SS_FMT_CS8, "int_scale": CS8_FILE_SCALE}
     if info.kind == KIND_CU8:
         return {"in_format": abi.SS_FMT_CU8, "int_scale": CS8_FILE_SCALE}
+    if info.kind == KIND_CS16:
+        return {"in_format": abi.SS_FMT_CS16, "int_scale": CS16_FILE_SCALE}
     if info.kind == KIND_CF32:
         return {"in_format": abi.SS_FMT_CF32}
     raise ValueError("a _power.raw file holds spectra, not IQ")
@@ -191,7 +195,7 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
     cfg = engine.cfg
     if kind is None:
         kind = parse_raw_file_name(path).kind
-    want_fmt = {KIND_CF32: abi.SS_FMT_CF32, KIND_CS8: abi.SS_FMT_CS8, KIND_CU8: abi.SS_FMT_CU8}[kind]
+    want_fmt = _KIND_FMT[kind]
     if cfg.in_format != want_fmt:
         raise ValueError("engine in_format does not match the file (see engine_overrides_for)")
     batch = int(batch or cfg.max_batch)
@@ -200,7 +204,7 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
     reader = RawIqReader(path, kind, cfg.fft_size, cfg.decim)
     feed = engine.feed(depth=depth, cand_cap=cand_cap, want_psd=want_psd)
     st = stats if stats is not None else ReplayStats()
-    frame_bytes = cfg.fft_size * (8 if kind == KIND_CF32 else 2)
+    frame_bytes = cfg.fft_size * abi.SS_FMT_BYTES[want_fmt]
     submitted: queue.Queue = queue.Queue()
     free = threading.Semaphore(depth)  # a slot is free again once its batch has been collected
     err: list = []

@@ -73,6 +73,12 @@ class SyntheticBand:
         y = np.stack([x.real, x.imag], axis=-1) * (128.0 / full_scale)
         return np.clip(np.rint(y), -128, 127).astype(np.int8)
 
+    def frames_cs16(self, nframes: int, full_scale: float = 0.5) -> np.ndarray:
+        """[nframes, fft_size*decim, 2] int16 (SDRplay/Airspy/LimeSDR-shaped): cf32 * 32768/full_scale rounded and clipped."""
+        x = self.frames_cf32(nframes)
+        y = np.stack([x.real, x.imag], axis=-1).astype(np.float64) * (32768.0 / full_scale)
+        return np.clip(np.rint(y), -32768, 32767).astype(np.int16)
+
     def frames_cu8(self, nframes: int, full_scale: float = 0.5) -> np.ndarray:
         x = self.frames_cf32(nframes)
         y = np.stack([x.real, x.imag], axis=-1) * (127.5 / full_scale) + 127.5
