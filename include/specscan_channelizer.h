@@ -63,12 +63,23 @@ int sc_start(sc_ctx* ctx, int32_t channel, int32_t shift_hz);
 int sc_stop(sc_ctx* ctx, int32_t channel);
 int sc_is_recording(const sc_ctx* ctx, int32_t channel);
 
-/* One work() pass over nsamples CF32 samples (interleaved re,im) of the device stream.
+/* Sample format of the stream sc_process / sc_process_device read from the next call on: an ss_format
+ * (SS_FMT_CF32, SS_FMT_CS8, SS_FMT_CU8, SS_FMT_CS16) with ss_config.int_scale's meaning and defaults
+ * (0 -> 1/128, 1/127.5, 1/32768). Phase and filter histories are kept (they hold converted, rotated floats).
+ * A context starts in CF32. SS_ERR_INVALID for an unknown format or an int_scale that is negative or not finite.
+ * The integers convert exactly as in the scan chain: cf32 = (int - offset) * int_scale. */
+int sc_set_input_format(sc_ctx* ctx, int32_t in_format, float int_scale);
+
+/* One work() pass over nsamples samples of the device stream, interleaved re,im in the context's input format
+ * (sc_set_input_format; CF32 unless set): SS_FMT_BYTES(format) * nsamples bytes.
  *   out_i8   [channels][cap][2] int8 (re,im) — what complex_to_interleaved_char emits;   nullable
  *   out_cf32 [channels][cap][2] float — the last resampler's output (DEBUG_SAVE_RECORDING_RAW_IQ tap, recorder.cpp:42-45); nullable
  *   counts   [channels] samples produced per channel (0 for idle slots)
  * sc_process takes host pointers and is synchronous; sc_process_device takes device pointers, is asynchronous on the
- * context's stream (sc_sync), and returns counts (host array) immediately — they do not depend on the data. */
+ * context's stream (sc_sync), and returns counts (host array) immediately — they do not depend on the data.
+ * sc_process_device refuses (SS_ERR_INVALID) an integer-format d_iq that is not aligned to the sample size. It only reads
+ * d_iq, as ss_process_device does: one device upload of the receiver's native stream, nframes items of N*D samples in
+ * the same format, may feed both ss_process_device and sc_process_device (nframes * N * D samples) at once. */
 int sc_process(sc_ctx* ctx, const void* iq, int32_t nsamples, int8_t* out_i8, float* out_cf32, int32_t* counts, int32_t cap);
 int sc_process_device(sc_ctx* ctx, const void* d_iq, int32_t nsamples, int8_t* d_out_i8, float* d_out_cf32, int32_t* counts, int32_t cap);
 int sc_sync(sc_ctx* ctx);

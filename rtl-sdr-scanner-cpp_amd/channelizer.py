@@ -7,6 +7,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import abi
 from .abi import SpecscanError
 from .engine import load_library
 
@@ -15,7 +16,10 @@ SC_MAX_CHANNELS = 16
 
 EXPORTS = ("sc_default_config", "sc_create", "sc_destroy", "sc_last_error", "sc_stage_count", "sc_stage_info", "sc_stage_taps",
            "sc_output_capacity", "sc_start", "sc_stop", "sc_is_recording", "sc_process", "sc_process_device", "sc_sync",
-           "sc_transmission_payload")
+           "sc_transmission_payload", "sc_set_input_format")
+
+# what process() / process_device() take for each input format (ss_format): integers interleaved re,im
+_NP_DTYPE = {abi.SS_FMT_CS8: np.int8, abi.SS_FMT_CU8: np.uint8, abi.SS_FMT_CS16: np.int16}
 
 
 class ScConfig(C.Structure):  # sc_config
@@ -45,6 +49,7 @@ def _bind(lib):
     lib.sc_process.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, i32p, C.c_int32]
     lib.sc_process_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, i32p, C.c_int32]
     lib.sc_sync.argtypes = [C.c_void_p]
+    lib.sc_set_input_format.argtypes = [C.c_void_p, C.c_int32, C.c_float]
     lib.sc_transmission_payload.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
     lib._sc_bound = True
     return lib
@@ -65,7 +70,7 @@ def transmission_payload(time_ms: int, frequency: int, sample_rate: int, iq_i8: 
 class Channelizer:
     """All recording slots of one device (Recorder x recordersCount, reference sources/radio/sdr_device.cpp:39-41)."""
 
-    def __init__(self, sample_rate: int, bandwidth: int, **overrides):
+    def __init__(self, sample_rate: int, bandwidth: int, in_format: int = abi.SS_FMT_CF32, int_scale: float = 0.0, **overrides):
         self._lib = _bind(load_library())
         cfg = ScConfig()
         self._lib.sc_default_config(C.byref(cfg), int(sample_rate), int(bandwidth))
@@ -84,6 +89,13 @@ class Channelizer:
             i, d, t = C.c_int32(), C.c_int32(), C.c_int32()
             self._lib.sc_stage_info(h, s, C.byref(i), C.byref(d), C.byref(t))
             self.stages.append((i.value, d.value, t.value))
+        self.in_format = abi.SS_FMT_CF32
+        self.set_input_format(in_format, int_scale)
+
+    def set_input_format(self, fmt: int, scale: float = 0.0):
+        """sc_set_input_format: the ss_format of the stream from the next call on (0 scale: the format's full-scale default)."""
+        self._check(self._lib.sc_set_input_format(self._h, int(fmt), float(scale)))
+        self.in_format = int(fmt)
 
     def _check(self, st):
         if st != 0:
@@ -117,21 +129,46 @@ class Channelizer:
     def is_recording(self, channel: int) -> bool:
         return bool(self._lib.sc_is_recording(self._h, int(channel)))
 
+    def _host_input(self, iq) -> tuple:
+        """The stream as the library reads it, and its sample count. An integer dtype must be the format's own: bytes are never
+        reinterpreted and integers never converted here."""
+        want = _NP_DTYPE.get(self.in_format)
+        dt = np.asarray(iq).dtype
+        if want is None:
+            if dt.kind in "iu":
+                raise TypeError(f"{dt} samples given to a CF32 channeliser (set_input_format first)")
+            x = np.ascontiguousarray(iq, dtype=np.complex64)
+            return x, x.size
+        if dt != want:
+            raise TypeError(f"input format {self.in_format} takes interleaved {np.dtype(want)} (re, im), not {dt}")
+        x = np.ascontiguousarray(iq)
+        if x.size % 2 or (x.ndim > 1 and x.shape[-1] != 2):
+            raise ValueError("integer samples are (n, 2) or flat interleaved re, im")
+        return x, x.size // 2
+
     def process(self, iq: np.ndarray, want_cf32: bool = True):
-        """iq: complex64 [n] (the device stream). Returns {channel: (int8 [m, 2], complex64 [m] or None)} for the active slots."""
-        x = np.ascontiguousarray(iq, dtype=np.complex64)
-        cap = max(self.output_capacity(x.size), 1)
+        """iq: the device stream — complex64 [n] (CF32), or int8 / uint8 / int16 [n, 2] or flat interleaved [2n] for CS8 / CU8 /
+        CS16. Returns {channel: (int8 [m, 2], complex64 [m] or None)} for the active slots."""
+        x, nsamples = self._host_input(iq)
+        cap = max(self.output_capacity(nsamples), 1)
         nch = self.cfg.channels
         i8 = np.zeros((nch, cap, 2), np.int8)
         cf = np.zeros((nch, cap), np.complex64) if want_cf32 else None
         counts = np.zeros(nch, np.int32)
-        self._check(self._lib.sc_process(self._h, x.ctypes.data, x.size, i8.ctypes.data, cf.ctypes.data if want_cf32 else None,
+        self._check(self._lib.sc_process(self._h, x.ctypes.data, nsamples, i8.ctypes.data, cf.ctypes.data if want_cf32 else None,
                                          counts.ctypes.data_as(C.POINTER(C.c_int32)), cap))
         return {ch: (i8[ch, :counts[ch]].copy(), cf[ch, :counts[ch]].copy() if want_cf32 else None)
                 for ch in range(nch) if self.is_recording(ch)}
 
     def process_device(self, iq, nsamples: int, out_i8=None, out_cf32=None, cap: int = 0):
-        """torch tensors on this context's device (plain HBM allocations). Returns the per-channel counts (numpy); async: call sync()."""
+        """torch tensors on this context's device (plain HBM allocations); iq in the context's format: float32 / complex64 (CF32),
+        int8 (CS8), uint8 (CU8), int16 (CS16), interleaved re, im. Returns the per-channel counts (numpy); async: call sync()."""
+        if iq is not None:
+            import torch
+            want = {abi.SS_FMT_CS8: (torch.int8,), abi.SS_FMT_CU8: (torch.uint8,), abi.SS_FMT_CS16: (torch.int16,)}.get(
+                self.in_format, (torch.float32, torch.complex64))
+            if iq.dtype not in want:
+                raise TypeError(f"input format {self.in_format} takes a {want[0]} tensor, not {iq.dtype}")
         counts = np.zeros(self.cfg.channels, np.int32)
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         self._check(self._lib.sc_process_device(self._h, p(iq), int(nsamples), p(out_i8), p(out_cf32),

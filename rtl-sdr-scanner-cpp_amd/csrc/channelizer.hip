@@ -16,6 +16,9 @@
 //                  drift and no dependence on how the stream is cut into calls (the reference's recurrence renormalises
 //                  every 512 samples and at the end of every work() call).
 // Bound: fp32 FMA issue and LDS reads (≈33 taps x 2 FMA per input sample per slot); HBM traffic is the input once.
+//   input:         the device stream in any ss_format (sc_set_input_format). Only the first stage reads it: its loads hold
+//                  one raw word per sample (float2, or one dword / ushort for CS16 / CS8 / CU8) and convert it exactly as
+//                  the scan chain's load_iq does, in front of the rotator; every later stage and the LDS tile see float2.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -171,6 +174,8 @@ struct sc_ctx {
   sc_config cfg{};
   std::mutex mtx;
   char err[512] = "";
+  int32_t in_format = SS_FMT_CF32;  // sc_set_input_format
+  float in_scale = 1.0f;            // resolved int_scale (unused by CF32)
   hipStream_t stream = nullptr;
   std::vector<Stage> stages;
   Slot slots[SC_MAX_CHANNELS];
@@ -207,7 +212,8 @@ int sc_fail(sc_ctx* c, int code, const char* fmt, ...) {
 // ---------------------------------------------------------------------------------------------------------------
 
 struct ChanArgs {
-  const float2* in_raw;  // ROTATE: the device stream, n_in new samples, shared by all slots
+  const void* in_raw;    // ROTATE: the device stream, n_in new samples in the context's ss_format, shared by all slots
+  float in_scale;        // ROTATE: integer formats -> float (ss_config.int_scale's meaning)
   const float2* hist0;   // ROTATE: per slot, the newest nt-1 rotated samples before this call
   long long hist0_stride;
   const float2* in_buf;  // !ROTATE: per slot [hist (nt-1) | new]
@@ -243,13 +249,40 @@ __device__ __forceinline__ float2 rotate(float2 x, float2 p) {  // in * phase (r
   return make_float2(x.x * p.x - x.y * p.y, x.x * p.y + x.y * p.x);
 }
 
+// One sample of the raw stream as it is loaded: the whole sample in one word, so that a first stage holding many loads in
+// flight spends one VGPR on an integer sample (two on CF32). raw_to_f2 is the scan chain's conversion (load_iq, cs16_to_f2 in
+// fft_kernels.h): CS8 c * s, CU8 (c - 127.5) * s, CS16 the sign-extended halves * s.
+template <int FMT> struct RawIq { using T = float2; };
+template <> struct RawIq<SS_FMT_CS16> { using T = uint32_t; };
+template <> struct RawIq<SS_FMT_CS8> { using T = uint16_t; };
+template <> struct RawIq<SS_FMT_CU8> { using T = uint16_t; };
+
+template <int FMT>
+__device__ __forceinline__ float2 raw_to_f2(typename RawIq<FMT>::T r, float s) {
+  if constexpr (FMT == SS_FMT_CF32) {
+    return r;
+  } else if constexpr (FMT == SS_FMT_CS16) {
+    return make_float2((float)(short)(r & 0xffffu) * s, (float)((int)r >> 16) * s);
+  } else if constexpr (FMT == SS_FMT_CS8) {
+    return make_float2((float)(signed char)(r & 0xffu) * s, (float)(signed char)(r >> 8) * s);
+  } else {
+    static_assert(FMT == SS_FMT_CU8, "input format");
+    return make_float2(((float)(r & 0xffu) - 127.5f) * s, ((float)(r >> 8) - 127.5f) * s);
+  }
+}
+
+template <int FMT>
+__device__ __forceinline__ float2 load_raw(const ChanArgs& a, int n) {
+  return raw_to_f2<FMT>(static_cast<const typename RawIq<FMT>::T*>(a.in_raw)[n], a.in_scale);
+}
+
 // volk_32f_s32f_convert_8i: r = in * scalar; saturate to [-128, 127]; rintf (round to nearest even)
 __device__ __forceinline__ int8_t to_i8(float v, float scale) {
   const float r = v * scale;
   return r > 127.0f ? (int8_t)127 : (r < -128.0f ? (int8_t)-128 : (int8_t)rintf(r));
 }
 
-template <bool ROTATE>
+template <bool ROTATE, int FMT>
 __global__ __launch_bounds__(256) void k_chan_stage(ChanArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char chan_smem[];
   float2* lds = reinterpret_cast<float2*>(chan_smem);
@@ -278,7 +311,7 @@ __global__ __launch_bounds__(256) void k_chan_stage(ChanArgs a) {
     float2 v;
     if (ROTATE) {
       if (n < 0) v = a.hist0[(size_t)slot * a.hist0_stride + (h + n)];
-      else v = rotate(a.in_raw[n], phase_of(a.f0[s], a.df[s], n));
+      else v = rotate(load_raw<FMT>(a, n), phase_of(a.f0[s], a.df[s], n));
     } else {
       v = a.in_buf[(size_t)slot * a.in_stride + (h + n)];
     }
@@ -357,7 +390,7 @@ __global__ void k_chan_ptab(float2* __restrict__ tab, int n, double df) {
 // produce a full set of outputs — straight-line staging and LDS reads at fixed offsets, nothing clamped; the other one
 // takes the few that start in the slot's history (tiles 0..2 at most: three tiles cover more than the filter) or end
 // ragged (the last one).
-template <int LOGG, int PASSES, bool FULL>
+template <int FMT, int LOGG, int PASSES, bool FULL>
 __device__ __forceinline__ void chan_dec_tile(const ChanArgs& a, float2* __restrict__ lds, int block_x) {
   constexpr int GL = 1 << LOGG, G = 64 / GL, A = kDecA, R = kDecR, W = A - 1 + R;
   const int s = blockIdx.y;
@@ -393,39 +426,40 @@ __device__ __forceinline__ void chan_dec_tile(const ChanArgs& a, float2* __restr
   {
     // Up to 24 independent, unconditional loads per thread in flight (the whole span of a 64-output tile at D = 64), all
     // on legal addresses — a load, its arithmetic and its store per loop trip would serialise on the memory latency.
+    // They hold raw samples (RawIq: one VGPR per integer sample), converted at the LDS store in front of the rotator.
     // Phase of sample idx = TPB u + tid: (P0 T[tid]) T[TPB u], the second factor block-uniform (scalar loads), so the
     // table costs one vector load per thread instead of one per sample. Tiles that begin before this call's input
-    // (edge instantiation only) take those samples, already rotated, from the slot's history; before that, zeros.
+    // (edge instantiation only) take those samples, already rotated, from the slot's history in a pass of their own;
+    // before that, zeros.
+    using Raw = typename RawIq<FMT>::T;
     constexpr int U = LOGG == 6 ? 24 : 12;  // smaller tiles keep four waves per SIMD: fewer registers
     const int TPB = (int)blockDim.x;  // 64, 128 or 256: as many waves as the span leaves LDS for
-    const float2* src = a.in_raw + n_lo;
-    const float2* hist = a.hist0 + (size_t)slot * a.hist0_stride + h + n_lo;  // hist[idx] = stream sample n_lo + idx < 0
+    const Raw* src = static_cast<const Raw*>(a.in_raw) + n_lo;
     const float2 q = cmulf(P0, ptab[threadIdx.x]);
     if (FULL && span == U * TPB) {
       // the span of a full tile at D = 64 is exactly 24 samples per thread: no clamps, no predicates
-      float2 xv[U];
+      Raw xv[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) xv[u] = src[u * TPB + (int)threadIdx.x];
 #pragma unroll
-      for (int u = 0; u < U; ++u) lds[u * TPB + (int)threadIdx.x] = rotate(xv[u], cmulf(q, ptab[u * TPB]));
+      for (int u = 0; u < U; ++u) lds[u * TPB + (int)threadIdx.x] = rotate(raw_to_f2<FMT>(xv[u], a.in_scale), cmulf(q, ptab[u * TPB]));
     } else {
+      const int first_new = FULL ? 0 : max(-n_lo, 0);  // span index of this call's first sample (<= span - 1: p_last >= 0)
       for (int base = 0; base < span; base += U * TPB) {
-        float2 xv[U];
+        Raw xv[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int idx = min(base + u * TPB + (int)threadIdx.x, span - 1);
-          const float2* p = src + idx;
-          if (!FULL && n_lo + idx < 0) p = hist + max(idx, -(h + n_lo));
-          xv[u] = *p;
-        }
+        for (int u = 0; u < U; ++u) xv[u] = src[max(min(base + u * TPB + (int)threadIdx.x, span - 1), first_new)];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int idx = base + u * TPB + (int)threadIdx.x;
           const float2 th = ptab[min(base + u * TPB, span - 1)];
-          float2 v = rotate(xv[u], cmulf(q, th));
-          if (!FULL && n_lo + idx < 0) v = n_lo + idx >= -h ? xv[u] : make_float2(0.0f, 0.0f);
-          if (idx < span) lds[idx] = v;
+          const float2 v = rotate(raw_to_f2<FMT>(xv[u], a.in_scale), cmulf(q, th));
+          if (idx < span && idx >= first_new) lds[idx] = v;
         }
+      }
+      if (!FULL) {
+        const float2* hist = a.hist0 + (size_t)slot * a.hist0_stride + h + n_lo;  // hist[idx] = stream sample n_lo + idx < 0
+        for (int idx = (int)threadIdx.x; idx < first_new; idx += TPB) lds[idx] = n_lo + idx >= -h ? hist[idx] : make_float2(0.0f, 0.0f);
       }
     }
   }
@@ -500,26 +534,26 @@ __device__ __forceinline__ void chan_dec_tile(const ChanArgs& a, float2* __restr
 
 // One launch: blocks [0, gridDim.x - 4) offer every tile to the full-tile code, the last four blocks offer tiles 0, 1, 2 and
 // the last one to the edge code (block-uniform branch; each side returns at once when the tile is of the other kind).
-template <int LOGG, int PASSES>
+template <int FMT, int LOGG, int PASSES>
 __global__ __launch_bounds__(256) void k_chan_dec(ChanArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char chan_smem[];
   float2* lds = reinterpret_cast<float2*>(chan_smem);
   const int ntiles = (int)gridDim.x - 4;
-  if ((int)blockIdx.x < ntiles) chan_dec_tile<LOGG, PASSES, true>(a, lds, (int)blockIdx.x);
-  else chan_dec_tile<LOGG, PASSES, false>(a, lds, (int)blockIdx.x - ntiles);
+  if ((int)blockIdx.x < ntiles) chan_dec_tile<FMT, LOGG, PASSES, true>(a, lds, (int)blockIdx.x);
+  else chan_dec_tile<FMT, LOGG, PASSES, false>(a, lds, (int)blockIdx.x - ntiles);
 }
 
 // The same as two launches (edge tiles first: grid.x = 4): where the merged kernel's register count — the larger of the
 // two sides' — would cost a wave per SIMD (measured: D <= 32 and the two-pass D > 64 form are faster split, D = 33..64 merged).
-template <int LOGG, int PASSES, bool FULL>
+template <int FMT, int LOGG, int PASSES, bool FULL>
 __global__ __launch_bounds__(256) void k_chan_dec_split(ChanArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char chan_smem[];
-  chan_dec_tile<LOGG, PASSES, FULL>(a, reinterpret_cast<float2*>(chan_smem), (int)blockIdx.x);
+  chan_dec_tile<FMT, LOGG, PASSES, FULL>(a, reinterpret_cast<float2*>(chan_smem), (int)blockIdx.x);
 }
 
 // After a call: the newest h samples of [history | new samples] become the history. One workgroup per slot, staged
 // through LDS because source and destination overlap when fewer than h samples arrived.
-template <bool ROTATE>
+template <bool ROTATE, int FMT>
 __global__ __launch_bounds__(256) void k_chan_keep(ChanArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char chan_smem[];
   float2* lds = reinterpret_cast<float2*>(chan_smem);
@@ -531,7 +565,7 @@ __global__ __launch_bounds__(256) void k_chan_keep(ChanArgs a) {
     float2 v;
     if (ROTATE) {
       if (n < 0) v = a.hist0[(size_t)slot * a.hist0_stride + (h + n)];
-      else v = rotate(a.in_raw[n], phase_of(a.f0[s], a.df[s], n));
+      else v = rotate(load_raw<FMT>(a, n), phase_of(a.f0[s], a.df[s], n));
     } else {
       v = a.in_buf[(size_t)slot * a.in_stride + (h + n)];
     }
@@ -571,7 +605,36 @@ void free_sc(sc_ctx* c) {
   delete c;
 }
 
-int run_stages(sc_ctx* c, const float2* d_iq, int nsamples, int8_t* d_out_i8, float* d_out_cf32, int32_t* counts, int cap) {
+// The first stage (the only one that reads the raw stream) and its history update, for one input format.
+template <int FMT>
+void launch_first_stage(const sc_ctx* c, const Stage& st, const ChanArgs& a, int max_out) {
+  const size_t lds_bytes = sizeof(float2) * (size_t)st.lds_floats2;
+  if (max_out > 0 && st.fast) {
+    // every tile is offered to the full-tile code, tiles 0, 1, 2 and the last one also to the edge code (four more blocks,
+    // or a launch of their own)
+    const unsigned tiles = (unsigned)((max_out + st.tile - 1) / st.tile);
+    const dim3 merged(tiles + 4u, (unsigned)a.nslots), grid(tiles, (unsigned)a.nslots), edge(4, (unsigned)a.nslots), block((unsigned)(64 * st.waves));
+#define SC_LAUNCH_SPLIT(LOGG_, PASSES_)                                                                                          \
+  do {                                                                                                                           \
+    hipLaunchKernelGGL((k_chan_dec_split<FMT, LOGG_, PASSES_, false>), edge, block, lds_bytes, c->stream, a);                    \
+    if (tiles > 1) hipLaunchKernelGGL((k_chan_dec_split<FMT, LOGG_, PASSES_, true>), grid, block, lds_bytes, c->stream, a);      \
+  } while (0)
+    switch (st.logg * 2 + (st.passes - 1)) {
+      case 6: SC_LAUNCH_SPLIT(3, 1); break;
+      case 8: SC_LAUNCH_SPLIT(4, 1); break;
+      case 10: SC_LAUNCH_SPLIT(5, 1); break;
+      case 12: hipLaunchKernelGGL((k_chan_dec<FMT, 6, 1>), merged, block, lds_bytes, c->stream, a); break;
+      default: SC_LAUNCH_SPLIT(6, 2); break;
+    }
+#undef SC_LAUNCH_SPLIT
+  } else if (max_out > 0) {
+    const dim3 grid((unsigned)((max_out + st.tile - 1) / st.tile), (unsigned)a.nslots);
+    hipLaunchKernelGGL((k_chan_stage<true, FMT>), grid, dim3(256), lds_bytes, c->stream, a);
+  }
+  if (st.nt > 1) hipLaunchKernelGGL((k_chan_keep<true, FMT>), dim3((unsigned)a.nslots), dim3(256), sizeof(float2) * (size_t)(st.nt - 1), c->stream, a);
+}
+
+int run_stages(sc_ctx* c, const void* d_iq, int nsamples, int8_t* d_out_i8, float* d_out_cf32, int32_t* counts, int cap) {
   const int nst = (int)c->stages.size();
   ChanArgs a{};
   a.nslots = 0;
@@ -586,6 +649,7 @@ int run_stages(sc_ctx* c, const float2* d_iq, int nsamples, int8_t* d_out_i8, fl
     Stage& st = c->stages[(size_t)k];
     const bool last = k == nst - 1;
     a.in_raw = d_iq;
+    a.in_scale = c->in_scale;
     a.hist0 = c->d_hist0;
     a.hist0_stride = c->hist0_stride;
     a.in_buf = st.d_buf;
@@ -617,34 +681,19 @@ int run_stages(sc_ctx* c, const float2* d_iq, int nsamples, int8_t* d_out_i8, fl
       a.df[s] = sl.df;
       max_out = a.nout[s] > max_out ? a.nout[s] : max_out;
     }
-    const size_t lds_bytes = sizeof(float2) * (size_t)st.lds_floats2;
-    if (max_out > 0 && k == 0 && st.fast) {
-      // every tile is offered to the full-tile code, tiles 0, 1, 2 and the last one also to the edge code (four more blocks,
-      // or a launch of their own)
-      const unsigned tiles = (unsigned)((max_out + st.tile - 1) / st.tile);
-      const dim3 merged(tiles + 4u, (unsigned)a.nslots), grid(tiles, (unsigned)a.nslots), edge(4, (unsigned)a.nslots), block((unsigned)(64 * st.waves));
-#define SC_LAUNCH_SPLIT(LOGG_, PASSES_)                                                                                          \
-  do {                                                                                                                           \
-    hipLaunchKernelGGL((k_chan_dec_split<LOGG_, PASSES_, false>), edge, block, lds_bytes, c->stream, a);                         \
-    if (tiles > 1) hipLaunchKernelGGL((k_chan_dec_split<LOGG_, PASSES_, true>), grid, block, lds_bytes, c->stream, a);           \
-  } while (0)
-      switch (st.logg * 2 + (st.passes - 1)) {
-        case 6: SC_LAUNCH_SPLIT(3, 1); break;
-        case 8: SC_LAUNCH_SPLIT(4, 1); break;
-        case 10: SC_LAUNCH_SPLIT(5, 1); break;
-        case 12: hipLaunchKernelGGL((k_chan_dec<6, 1>), merged, block, lds_bytes, c->stream, a); break;
-        default: SC_LAUNCH_SPLIT(6, 2); break;
+    if (k == 0) {
+      switch (c->in_format) {
+        case SS_FMT_CS8: launch_first_stage<SS_FMT_CS8>(c, st, a, max_out); break;
+        case SS_FMT_CU8: launch_first_stage<SS_FMT_CU8>(c, st, a, max_out); break;
+        case SS_FMT_CS16: launch_first_stage<SS_FMT_CS16>(c, st, a, max_out); break;
+        default: launch_first_stage<SS_FMT_CF32>(c, st, a, max_out); break;  // (sc_set_input_format admits nothing else)
       }
-#undef SC_LAUNCH_SPLIT
-    } else if (max_out > 0) {
-      const dim3 grid((unsigned)((max_out + st.tile - 1) / st.tile), (unsigned)a.nslots);
-      if (k == 0) hipLaunchKernelGGL(k_chan_stage<true>, grid, dim3(256), lds_bytes, c->stream, a);
-      else hipLaunchKernelGGL(k_chan_stage<false>, grid, dim3(256), lds_bytes, c->stream, a);
-    }
-    if (st.nt > 1) {
-      const size_t keep_bytes = sizeof(float2) * (size_t)(st.nt - 1);
-      if (k == 0) hipLaunchKernelGGL(k_chan_keep<true>, dim3((unsigned)a.nslots), dim3(256), keep_bytes, c->stream, a);
-      else hipLaunchKernelGGL(k_chan_keep<false>, dim3((unsigned)a.nslots), dim3(256), keep_bytes, c->stream, a);
+    } else {
+      if (max_out > 0) {
+        const dim3 grid((unsigned)((max_out + st.tile - 1) / st.tile), (unsigned)a.nslots);
+        hipLaunchKernelGGL((k_chan_stage<false, SS_FMT_CF32>), grid, dim3(256), sizeof(float2) * (size_t)st.lds_floats2, c->stream, a);
+      }
+      if (st.nt > 1) hipLaunchKernelGGL((k_chan_keep<false, SS_FMT_CF32>), dim3((unsigned)a.nslots), dim3(256), sizeof(float2) * (size_t)(st.nt - 1), c->stream, a);
     }
     for (int s = 0; s < a.nslots; ++s) {
       Slot& sl = c->slots[a.slot[s]];
@@ -791,10 +840,12 @@ int sc_create(const sc_config* cfg, sc_ctx** out) {
     SC_CREATE_HIP(hipMalloc(&c->d_ptab, sizeof(float2) * (size_t)c->ptab_stride * (size_t)cfg->channels));
     SC_CREATE_HIP(hipMemsetAsync(c->d_ptab, 0, sizeof(float2) * (size_t)c->ptab_stride * (size_t)cfg->channels, c->stream));
   }
-  SC_CREATE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chan_stage<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-  SC_CREATE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chan_stage<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-  SC_CREATE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chan_keep<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-  SC_CREATE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chan_keep<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+  for (const void* f : {reinterpret_cast<const void*>(k_chan_stage<true, SS_FMT_CF32>), reinterpret_cast<const void*>(k_chan_stage<true, SS_FMT_CS8>),
+                        reinterpret_cast<const void*>(k_chan_stage<true, SS_FMT_CU8>), reinterpret_cast<const void*>(k_chan_stage<true, SS_FMT_CS16>),
+                        reinterpret_cast<const void*>(k_chan_stage<false, SS_FMT_CF32>), reinterpret_cast<const void*>(k_chan_keep<true, SS_FMT_CF32>),
+                        reinterpret_cast<const void*>(k_chan_keep<true, SS_FMT_CS8>), reinterpret_cast<const void*>(k_chan_keep<true, SS_FMT_CU8>),
+                        reinterpret_cast<const void*>(k_chan_keep<true, SS_FMT_CS16>), reinterpret_cast<const void*>(k_chan_keep<false, SS_FMT_CF32>)})
+    SC_CREATE_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
   SC_CREATE_HIP(hipStreamSynchronize(c->stream));
 #undef SC_CREATE_HIP
   *out = c;
@@ -871,6 +922,19 @@ int sc_is_recording(const sc_ctx* c, int32_t channel) {
   return c->slots[channel].active ? 1 : 0;
 }
 
+int sc_set_input_format(sc_ctx* c, int32_t in_format, float int_scale) {
+  if (!c) return SS_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (in_format != SS_FMT_CF32 && in_format != SS_FMT_CS8 && in_format != SS_FMT_CU8 && in_format != SS_FMT_CS16)
+    return sc_fail(c, SS_ERR_INVALID, "in_format %d is not an ss_format", in_format);
+  if (!std::isfinite(int_scale) || int_scale < 0.0f) return sc_fail(c, SS_ERR_INVALID, "int_scale %g", (double)int_scale);
+  // ss_create's defaults (specscan.hip): full scale 1.0
+  if (int_scale == 0.0f) int_scale = in_format == SS_FMT_CU8 ? 1.0f / 127.5f : in_format == SS_FMT_CS16 ? 1.0f / 32768.0f : 1.0f / 128.0f;
+  c->in_format = in_format;
+  c->in_scale = int_scale;
+  return SS_OK;
+}
+
 int sc_sync(sc_ctx* c) {
   if (!c) return SS_ERR_INVALID;
   SC_HIP(c, hipSetDevice(c->cfg.device_id));
@@ -883,8 +947,10 @@ int sc_process_device(sc_ctx* c, const void* d_iq, int32_t nsamples, int8_t* d_o
   std::lock_guard<std::mutex> lock(c->mtx);
   if (nsamples < 0 || (nsamples > 0 && !d_iq) || cap < 0) return sc_fail(c, SS_ERR_INVALID, "bad iq/nsamples/cap");
   if (nsamples > c->cfg.max_samples) return sc_fail(c, SS_ERR_BATCH, "nsamples %d > max_samples %d", nsamples, c->cfg.max_samples);
+  if (c->in_format != SS_FMT_CF32 && reinterpret_cast<uintptr_t>(d_iq) % SS_FMT_BYTES(c->in_format) != 0)
+    return sc_fail(c, SS_ERR_INVALID, "d_iq is not aligned to the %d-byte sample", SS_FMT_BYTES(c->in_format));
   SC_HIP(c, hipSetDevice(c->cfg.device_id));
-  return run_stages(c, static_cast<const float2*>(d_iq), nsamples, d_out_i8, d_out_cf32, counts, cap);
+  return run_stages(c, d_iq, nsamples, d_out_i8, d_out_cf32, counts, cap);
 }
 
 int sc_process(sc_ctx* c, const void* iq, int32_t nsamples, int8_t* out_i8, float* out_cf32, int32_t* counts, int32_t cap) {
@@ -893,7 +959,7 @@ int sc_process(sc_ctx* c, const void* iq, int32_t nsamples, int8_t* out_i8, floa
   if (nsamples < 0 || (nsamples > 0 && !iq) || cap < 0 || !counts) return sc_fail(c, SS_ERR_INVALID, "bad iq/nsamples/cap/counts");
   if (nsamples > c->cfg.max_samples) return sc_fail(c, SS_ERR_BATCH, "nsamples %d > max_samples %d", nsamples, c->cfg.max_samples);
   SC_HIP(c, hipSetDevice(c->cfg.device_id));
-  if (!c->d_in) SC_HIP(c, hipMalloc(&c->d_in, sizeof(float2) * (size_t)c->cfg.max_samples));
+  if (!c->d_in) SC_HIP(c, hipMalloc(&c->d_in, sizeof(float2) * (size_t)c->cfg.max_samples));  // CF32-sized: a format switch never reallocates
   if (cap > c->out_cap_alloc) {
     (void)hipFree(c->d_out_i8);
     (void)hipFree(c->d_out_cf32);
@@ -904,7 +970,7 @@ int sc_process(sc_ctx* c, const void* iq, int32_t nsamples, int8_t* out_i8, floa
     SC_HIP(c, hipMalloc(&c->d_out_cf32, sizeof(float2) * (size_t)cap * (size_t)c->cfg.channels));
     c->out_cap_alloc = cap;
   }
-  if (nsamples > 0) SC_HIP(c, hipMemcpyAsync(c->d_in, iq, sizeof(float2) * (size_t)nsamples, hipMemcpyHostToDevice, c->stream));
+  if (nsamples > 0) SC_HIP(c, hipMemcpyAsync(c->d_in, iq, (size_t)SS_FMT_BYTES(c->in_format) * (size_t)nsamples, hipMemcpyHostToDevice, c->stream));
   const int st = run_stages(c, c->d_in, nsamples, out_i8 ? c->d_out_i8 : nullptr, out_cf32 ? c->d_out_cf32 : nullptr, counts, cap);
   if (st != SS_OK) return st;
   for (int ch = 0; ch < c->cfg.channels; ++ch) {

@@ -7,6 +7,7 @@
 // items (`samplesSize` int8 samples, recorder.cpp:35) with their arrival times, and flush -> publish in the argument
 // order of DataController::pushTransmission (sources/network/data_controller.cpp:27). Header-only C++17; links libspecscan.so.
 #pragma once
+#include <specscan.h>
 #include <specscan_channelizer.h>
 
 #include <algorithm>
@@ -28,7 +29,9 @@ class RecorderBank {
   using Publish = std::function<void(int64_t time_ms, int32_t frequency, int32_t sample_rate, const int8_t* iq, int nsamples)>;
   using ShiftFlush = std::pair<int32_t, bool>;  // FrequencyFlush, sources/radio/help_structures.h:15
 
-  RecorderBank(int32_t sample_rate, int32_t bandwidth, int recorders, int max_samples, Publish publish, int device_id = 0)
+  // in_format / int_scale: the ss_format of the device stream work() reads (sc_set_input_format; 0 scale: the format's default)
+  RecorderBank(int32_t sample_rate, int32_t bandwidth, int recorders, int max_samples, Publish publish, int device_id = 0,
+               int32_t in_format = SS_FMT_CF32, float int_scale = 0.0f)
       : m_bandwidth(bandwidth), m_publish(std::move(publish)), m_slots((size_t)recorders) {
     sc_config cfg;
     sc_default_config(&cfg, sample_rate, bandwidth);
@@ -36,6 +39,11 @@ class RecorderBank {
     cfg.max_samples = max_samples;
     cfg.device_id = device_id;
     if (sc_create(&cfg, &m_ctx) != 0) throw std::runtime_error(std::string("RecorderBank: ") + sc_last_error(nullptr));
+    if (sc_set_input_format(m_ctx, in_format, int_scale) != 0) {
+      const std::string err = std::string("RecorderBank: ") + sc_last_error(m_ctx);
+      sc_destroy(m_ctx);
+      throw std::runtime_error(err);
+    }
     // roundUp(recordingBandwidth * RECORDER_FLUSH_INTERVAL / 1000, 4096), recorder.cpp:35, config.h:19
     const int raw = bandwidth * 100 / 1000;
     m_itemSamples = raw % 4096 == 0 ? raw : (raw / 4096 + 1) * 4096;
@@ -52,9 +60,10 @@ class RecorderBank {
   int32_t shift(int slot) const { return m_slots[(size_t)slot].shift; }  // Recorder::getShift: max() while idle
   int64_t durationMs(int slot) const { return m_slots[(size_t)slot].last_ms - m_slots[(size_t)slot].first_ms; }
 
-  // The device stream: what every work() of the source delivers. Slots that record get their samples.
-  void work(const void* iq_cf32, int nsamples, int64_t now_ms) {
-    if (sc_process(m_ctx, iq_cf32, nsamples, m_out.data(), nullptr, m_counts.data(), m_cap) != 0) throw std::runtime_error(sc_last_error(m_ctx));
+  // The device stream: what every work() of the source delivers, nsamples in the bank's input format. Slots that record get
+  // their samples.
+  void work(const void* iq, int nsamples, int64_t now_ms) {
+    if (sc_process(m_ctx, iq, nsamples, m_out.data(), nullptr, m_counts.data(), m_cap) != 0) throw std::runtime_error(sc_last_error(m_ctx));
     for (size_t k = 0; k < m_slots.size(); ++k) {
       Slot& s = m_slots[k];
       if (!s.recording) continue;

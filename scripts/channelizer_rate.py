@@ -1,6 +1,11 @@
-"""Throughput of the recorder channeliser on HBM-resident input (sc_process_device), next to the VALU bound.
-    python scripts/channelizer_rate.py [--fs 2048000] [--bw 32000] [--samples 8388608] [--slots 1 4 8]"""
+"""Throughput of the recorder channeliser on HBM-resident input (sc_process_device), next to the VALU bound, per input format;
+with --host also sc_process from pageable host memory (the PCIe copy of the raw stream included).
+    python scripts/channelizer_rate.py [--fs 2048000] [--bw 32000] [--samples 8388608] [--slots 1 4 8]
+                                       [--format cf32 cs8 cu8 cs16] [--host] [--repeats 5] [--steps 20] [--host-steps 20]
+The formats are timed in alternation, --repeats rounds of --steps (device) / --host-steps (host) calls each; the medians of the
+rounds are reported."""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -10,7 +15,20 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from rtl_sdr_scanner_cpp_amd import abi as A  # noqa: E402
 from rtl_sdr_scanner_cpp_amd.channelizer import Channelizer  # noqa: E402
+
+FORMATS = {"cf32": (A.SS_FMT_CF32, np.float32), "cs8": (A.SS_FMT_CS8, np.int8), "cu8": (A.SS_FMT_CU8, np.uint8), "cs16": (A.SS_FMT_CS16, np.int16)}
+
+
+def _stream(samples, name, rng):
+    """The same noise in every format: [samples, 2] float32 (CF32) or the format's integers at a quarter of full scale."""
+    x = rng.standard_normal((samples, 2), dtype=np.float32) * np.float32(0.25)
+    if name == "cf32":
+        return x
+    full, off = {"cs8": (127.0, 0.0), "cu8": (127.5, 127.5), "cs16": (32767.0, 0.0)}[name]
+    dt = FORMATS[name][1]
+    return np.clip(np.rint(x * full + off), np.iinfo(dt).min, np.iinfo(dt).max).astype(dt)
 
 
 def main():
@@ -19,32 +37,72 @@ def main():
     ap.add_argument("--bw", type=int, default=32_000)
     ap.add_argument("--samples", type=int, default=1 << 23)
     ap.add_argument("--slots", type=int, nargs="+", default=[1, 4, 8])
+    ap.add_argument("--format", nargs="+", default=["cf32"], choices=list(FORMATS))
+    ap.add_argument("--host", action="store_true", help="also time sc_process from pageable host memory")
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--host-steps", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
-    x = (rng.standard_normal((a.samples, 2)) * 0.1).astype(np.float32)
-    d_iq = torch.from_numpy(x).to(dev)
+    host = {f: _stream(a.samples, f, rng) for f in a.format}
+    d_iq = {f: torch.from_numpy(host[f]).to(dev) for f in a.format}
     for nslots in a.slots:
-        ch = Channelizer(a.fs, a.bw, channels=nslots, max_samples=a.samples)
-        for k in range(nslots):
-            ch.start(k, int((k - nslots / 2) * 0.9 * a.fs / max(nslots, 2)))
-        cap = ch.output_capacity(a.samples)
-        d_i8 = torch.zeros((nslots, cap, 2), dtype=torch.int8, device=dev)
-        for _ in range(3):
-            ch.process_device(d_iq, a.samples, d_i8, None, cap)
-        ch.sync()
-        t0 = time.perf_counter()
-        for _ in range(a.steps):
-            ch.process_device(d_iq, a.samples, d_i8, None, cap)
-        ch.sync()
-        dt = (time.perf_counter() - t0) / a.steps
+        ctx, d_i8, h_i8 = {}, {}, {}
+        counts = np.zeros(nslots, np.int32)
+        for f in a.format:
+            ch = Channelizer(a.fs, a.bw, in_format=FORMATS[f][0], channels=nslots, max_samples=a.samples)
+            for k in range(nslots):
+                ch.start(k, int((k - nslots / 2) * 0.9 * a.fs / max(nslots, 2)))
+            ctx[f] = ch
+        cap = ctx[a.format[0]].output_capacity(a.samples)
+        for f in a.format:
+            d_i8[f] = torch.zeros((nslots, cap, 2), dtype=torch.int8, device=dev)
+            h_i8[f] = np.zeros((nslots, cap, 2), np.int8)
+
+        def dev_call(f):
+            ctx[f].process_device(d_iq[f], a.samples, d_i8[f], None, cap)
+
+        def host_call(f):
+            ch = ctx[f]
+            ch._check(ch._lib.sc_process(ch._h, host[f].ctypes.data, a.samples, h_i8[f].ctypes.data, None,
+                                         counts.ctypes.data_as(C.POINTER(C.c_int32)), cap))
+
+        def timed(f, call, steps):
+            ctx[f].sync()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                call(f)
+            ctx[f].sync()
+            return (time.perf_counter() - t0) / steps
+
+        kinds = [("device", dev_call, a.steps)] + ([("host", host_call, a.host_steps)] if a.host else [])
+        for f in a.format:  # warm-up: code objects, staging buffers
+            for _kind, call, _steps in kinds:
+                for _ in range(3):
+                    call(f)
+            ctx[f].sync()
+        runs = {(f, kind): [] for f in a.format for kind, _, _ in kinds}
+        for _ in range(a.repeats):  # alternating rounds
+            for kind, call, steps in kinds:
+                for f in a.format:
+                    runs[(f, kind)].append(timed(f, call, steps))
+        ch = ctx[a.format[0]]
         taps_per_in = sum(nt / d * np.prod([i2 / d2 for i2, d2, _ in ch.stages[:k]]) for k, (i, d, nt) in enumerate(ch.stages))
         flops = 4.0 * taps_per_in * a.samples * nslots  # 2 FMA per tap per input sample (real taps, complex data)
-        print(json.dumps({"fs": a.fs, "bw": a.bw, "stages": ch.stages, "slots": nslots, "samples": a.samples, "ms_per_call": round(dt * 1e3, 4),
-                          "input_GSps": round(a.samples / dt / 1e9, 2), "slot_GSps": round(a.samples * nslots / dt / 1e9, 2),
-                          "fir_TFLOPs": round(flops / dt / 1e12, 2), "taps_per_input_sample": round(float(taps_per_in), 2)}))
-        ch.close()
+        for f in a.format:
+            dt = float(np.median(runs[(f, "device")]))
+            rec = {"fs": a.fs, "bw": a.bw, "stages": ch.stages, "slots": nslots, "samples": a.samples, "format": f,
+                   "input_MB": round(a.samples * A.SS_FMT_BYTES[FORMATS[f][0]] / 1e6, 1), "ms_per_call": round(dt * 1e3, 4),
+                   "ms_per_call_runs": [round(t * 1e3, 4) for t in runs[(f, "device")]], "input_GSps": round(a.samples / dt / 1e9, 2),
+                   "slot_GSps": round(a.samples * nslots / dt / 1e9, 2), "fir_TFLOPs": round(flops / dt / 1e12, 2),
+                   "taps_per_input_sample": round(float(taps_per_in), 2)}
+            if a.host:
+                ht = float(np.median(runs[(f, "host")]))
+                rec.update(host_ms_per_call=round(ht * 1e3, 4), host_ms_per_call_runs=[round(t * 1e3, 4) for t in runs[(f, "host")]])
+            print(json.dumps(rec), flush=True)
+        for c in ctx.values():
+            c.close()
 
 
 if __name__ == "__main__":
