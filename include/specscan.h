@@ -106,7 +106,14 @@ typedef struct ss_config {
   int32_t in_format;   /* ss_format */
   float int_scale;     /* CS8/CU8/CS16 -> float scale; 0 selects 1/128 (CS8), 1/127.5 (CU8) or
                           1/32768 (CS16)                                                       */
-  const float* window; /* N taps, or NULL for gr::fft::window::hamming(N) (sdr_device.cpp:164)  */
+  const float* window; /* N taps, copied at create, or NULL for gr::fft::window::hamming(N)
+                          (sdr_device.cpp:164). Results follow the taps at every size and format;
+                          three fast paths need NULL: the column tiles of 65536- and 2^20-point
+                          frames form Hamming taps instead of loading them (a caller's taps are
+                          loaded from a table: a few bytes per sample more), and int8 IQ at 65536
+                          and 131072 points takes the radix-8/16 fold (and, at 131072 points, tile
+                          culling) only with the default taps — the four-step form otherwise.
+                          Passing hamming(N) explicitly is a caller's window in this sense.       */
   int32_t grouping_x;  /* bins averaged in frequency, odd; GROUPING_X = 21 (config.h:28)        */
   int32_t grouping_y;  /* frames averaged in time;       GROUPING_Y = 21 (config.h:29)          */
   float start_level;   /* Device::m_startLevel, dB over the learned ceiling (config.h:30)       */

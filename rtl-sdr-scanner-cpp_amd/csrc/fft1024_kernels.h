@@ -90,7 +90,8 @@ inline void fft1024_window_order(const float* win, float* out, int logc) {
 // of constants, instead of 64 bytes of taps per thread — 4 B/sample through L2 and the vector-memory pipe, a fifth of the tile's
 // loads (12 of the column launch's 81 us per 16-frame call in the 8-column form, profiles/r04/s4_summary.txt). The taps formed
 // this way differ from (float)(0.54 - 0.46 cos(2 pi n / (N - 1))) by 1.2e-7 at most (3.4e-8 rms: the size of the rounding of the
-// exact tap itself), the dB plane by < 1e-5 dB but for the deepest nulls (tests/test_window_rotation.py).
+// exact tap itself), the dB plane by < 1e-5 dB but for the deepest nulls (the taps: tests/host/index_check.cpp;
+// the planes against the oracle, and the table taps this form replaces under a caller's window: tests/test_gpu_window.py).
 __device__ constexpr float kWin1024C[16] = {-0.460000008f, -0.424984515f, -0.325268865f, -0.176033899f, 6.89093611e-07f, 0.176035181f, 0.325269848f, 0.424985051f,
                                             0.460000008f, 0.424983978f, 0.325267911f, 0.176032633f, -2.06728078e-06f, -0.176036447f, -0.325270832f, -0.424985588f};
 __device__ constexpr float kWin1024S[16] = {0.0f, 0.17603454f, 0.325269371f, 0.424984783f, 0.460000008f, 0.424984246f, 0.325268388f, 0.176033258f,

@@ -148,18 +148,19 @@ def hamming_f32(n):
     return (0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(n) / (n - 1))).astype(np.float32)
 
 
-def fp64_psd_rows(iq_rows, fs):
+def fp64_psd_rows(iq_rows, fs, window=None):
     """dB rows of the SAME windowed frames (the fp32 product sample x tap both chains form) through an fp64 FFT: the truth two
-    fp32 FFTs are measured against."""
+    fp32 FFTs are measured against. window: the caller's taps (ss_config.window); None = the default Hamming taps."""
     n = iq_rows.shape[1]
-    w = hamming_f32(n)
+    w = hamming_f32(n) if window is None else np.ascontiguousarray(window, dtype=np.float32)
+    assert w.shape == (n,)
     x = (iq_rows.real.astype(np.float32) * w).astype(np.float64) + 1j * (iq_rows.imag.astype(np.float32) * w).astype(np.float64)
     spec = np.fft.fftshift(np.fft.fft(x, axis=1), axes=1)
     with np.errstate(divide="ignore"):
         return 10.0 * np.log10((spec.real ** 2 + spec.imag ** 2) / float(fs))
 
 
-def excess_vs_fp64(iq, got_psd, ref_psd, fs, max_rows=256):
+def excess_vs_fp64(iq, got_psd, ref_psd, fs, max_rows=256, window=None):
     """On the PSD bins outside the bare 1e-4 tolerance (deep nulls, where two correct fp32 FFTs part): how far the engine and the
     reference's fp32 FFT each are from an fp64 FFT of the same windowed frame. The engine is held to being no worse than 1.5 x the
     reference there (rms), i.e. the allowance covers fp32 rounding, not a defect. iq: complex64 frames [nframes, N] (decimated).
@@ -172,7 +173,7 @@ def excess_vs_fp64(iq, got_psd, ref_psd, fs, max_rows=256):
         return None
     if rows.size > max_rows:
         rows = rows[np.linspace(0, rows.size - 1, max_rows).astype(int)]
-    truth = fp64_psd_rows(iq[rows], fs)
+    truth = fp64_psd_rows(iq[rows], fs, window)
     m = over[rows]
     de = np.abs(got_psd[rows].astype(np.float64) - truth)[m]
     dr = np.abs(ref_psd[rows].astype(np.float64) - truth)[m]
@@ -193,7 +194,7 @@ def _arbitrate(res):
         assert res["engine_max"] <= 2.0 * res["reference_max"] + res["floor_max"], res
 
 
-def all_bins_vs_fp64(iq, got_psd, ref_psd, fs, max_rows=None):
+def all_bins_vs_fp64(iq, got_psd, ref_psd, fs, max_rows=None, window=None):
     """Engine and reference against an fp64 FFT of the same windowed frames over ALL ordinary bins of a sample of rows (not only
     the bins where the two part): rms, p99.9 and max of |dB - fp64| for each, and the ratio of the rms values — whether the engine's
     transform is systematically farther from the truth than the reference's fp32 FFT is. (A sample of rows: an fp64 FFT of every
@@ -204,7 +205,7 @@ def all_bins_vs_fp64(iq, got_psd, ref_psd, fs, max_rows=None):
     rows = np.arange(got_psd.shape[0])
     if rows.size > max_rows:
         rows = rows[np.linspace(0, rows.size - 1, max_rows).astype(int)]
-    truth = fp64_psd_rows(iq[rows], fs)
+    truth = fp64_psd_rows(iq[rows], fs, window)
     fin = np.isfinite(truth) & np.isfinite(got_psd[rows]) & np.isfinite(ref_psd[rows])
     if not fin.any():
         return None
@@ -231,7 +232,7 @@ def format_all_bins(v):
             f"median {v['engine_over_reference_median']:.2f}, p99 {v['engine_over_reference_p99']:.2f} (the five largest bins hold {e['top5_share_of_squares']:.0%} / {r['top5_share_of_squares']:.0%} of the squares)")
 
 
-def excess_vs_fp64_rel(iq, got_rel, ref_rel, fs, n_learn, max_rows=256):
+def excess_vs_fp64_rel(iq, got_rel, ref_rel, fs, n_learn, max_rows=256, window=None):
     """The same arbitration for the noise-relative plane (rel = dB - learned ceiling, noise_learner.cpp:55): on its bins outside the
     bare 1e-4 tolerance, the distance of the engine and of the reference to an fp64 chain — fp64 FFT of the same windowed frames,
     ceiling = the maximum over the first n_learn frames, subtraction in fp64. None when no bin is outside."""
@@ -243,8 +244,8 @@ def excess_vs_fp64_rel(iq, got_rel, ref_rel, fs, n_learn, max_rows=256):
         return None
     if rows.size > max_rows:
         rows = rows[np.linspace(0, rows.size - 1, max_rows).astype(int)]
-    thr = fp64_psd_rows(iq[:n_learn], fs).max(axis=0)
-    truth = fp64_psd_rows(iq[rows], fs) - thr[None, :]
+    thr = fp64_psd_rows(iq[:n_learn], fs, window).max(axis=0)
+    truth = fp64_psd_rows(iq[rows], fs, window) - thr[None, :]
     m = over[rows]
     de = np.abs(got_rel[rows].astype(np.float64) - truth)[m]
     dr = np.abs(ref_rel[rows].astype(np.float64) - truth)[m]
