@@ -69,7 +69,8 @@ typedef enum ss_plane {
 } ss_plane;
 
 /* ss_config.flags: keep the full avg plane of every batch on the device so that ss_read_window can serve
- * SS_PLANE_AVG (the host-side signal tracker needs it); costs 4 B/sample of extra HBM writes. */
+ * SS_PLANE_AVG (the host-side signal tracker needs it) and the tracking digest (specscan_track.h) can compute on the
+ * device what that tracker reads of the planes; costs 4 B/sample of extra HBM writes. */
 #define SS_FLAG_KEEP_PLANES 1u
 /* Also run the Spectrogram side branch (sources/radio/blocks/spectrogram.cpp): accumulate the bin-decimated raw
  * PSD per centre frequency; read it back with ss_spectrogram_read. */

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/specscan.h"
+#include "../../include/specscan_track.h"
 #include "detect_fused.h"
 #include "detect_kernels.h"
 #include "fft1024_kernels.h"
@@ -31,6 +32,7 @@
 #include "fft_kernels.h"
 #include "ring_place.h"
 #include "scan_step.h"
+#include "track_digest.h"
 
 namespace {
 
@@ -520,6 +522,10 @@ struct ss_ctx {
   int cand_cap_alloc = 0;
   const float* last_psd = nullptr;  // where the last batch's PSD plane lives (device)
   int last_n = 0;
+  // the tracking digest (st_digest, below): the capacity the last batch's candidate lists were given, and whether the centre
+  // frequency has changed since that batch (retunes so far; how many there were when the batch ran)
+  int last_cand_cap = 0;
+  unsigned long long retunes = 0, last_retunes = 0;
   // optional per-launch timing of the dominant (FFT+PSD) kernel: start/stop events attached to the
   // dispatch itself (hipExtLaunchKernelGGL), read back by ss_kernel_timing_read
   bool prof_on = false;
@@ -2275,6 +2281,8 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
   c->last_rows_db = ring_only_rows != nullptr;  // (... and whether they hold dB values, from frame last_db_from on)
   c->last_settled_lo = c->last_settled_hi = nullptr;
   c->last_n = nframes;
+  c->last_cand_cap = cand_cap;
+  c->last_retunes = c->retunes;
   return SS_OK;
 }
 
@@ -3128,6 +3136,7 @@ int ss_set_frequency_range(ss_ctx* c, int32_t lo_hz, int32_t hi_hz) {
   c->range_lo = lo_hz;
   c->range_hi = hi_hz;
   c->pass_dirty = true;
+  ++c->retunes;
   c->clean_abs = c->abs_frames;  // another centre frequency, another noise ceiling: the ring rows so far were formed with the old one
   return SS_OK;
 }
@@ -3519,6 +3528,290 @@ int ss_feed_collect(ss_feed* f, ss_feed_result* out) {
   s->state = 0;
   f->next_collect = (f->next_collect + 1) % f->depth;
   --f->pending;
+  return SS_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The tracking digest (include/specscan_track.h, kernels: track_digest.h): what the host-side signal tracker reads of the last
+// batch's rel and avg planes, computed next to them.
+struct st_ctx {
+  ss_ctx* scan = nullptr;
+  st_config cfg{};
+  int nrows = 1;      // ceil(grouping_y / 2): the rel rows getBestIndex looks at
+  int tail_rows = 0;  // nrows - 1: how many of them can lie before a batch
+  float* d_tail[2] = {};  // [tail_rows][n] each; [tail_cur] holds the rows before the next batch, the other one is written by the digest
+  int tail_cur = 0;
+  unsigned long long seen_batch = 0;  // ss_ctx::batch_no of the last batch digested (or at st_create / st_reset)
+  int32_t *d_off = nullptr, *d_idx = nullptr, *d_best = nullptr, *d_watch = nullptr, *d_pidx = nullptr;
+  float *d_cavg = nullptr, *d_pavg = nullptr;
+  int32_t *h_off = nullptr, *h_idx = nullptr, *h_best = nullptr, *h_watch = nullptr, *h_pidx = nullptr;  // pinned
+  float *h_cavg = nullptr, *h_pavg = nullptr;
+  size_t peak_cap = 0;  // elements of d_pidx / d_pavg / h_pidx / h_pavg (grown to nframes x nwatch as needed)
+  size_t cand_alloc = 0;  // elements of d_idx / d_best / d_cavg and their host twins (grown as needed, cfg.cand_cap at most)
+  std::vector<int32_t> merged;  // the watch list being formed
+  std::vector<uint8_t> mark;    // [n], all zero between digests
+  char err[512] = "";
+};
+
+namespace {
+
+thread_local char g_st_create_err[512] = "";
+
+int st_fail(st_ctx* t, int status, const char* fmt, ...) {
+  char* dst = t ? t->err : g_st_create_err;
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(dst, 512, fmt, ap);
+  va_end(ap);
+  return status;
+}
+
+#define ST_HIP(ctx, call)                                                                                 \
+  do {                                                                                                    \
+    hipError_t e_ = (call);                                                                               \
+    if (e_ != hipSuccess) return st_fail(ctx, SS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+  } while (0)
+
+void st_free(st_ctx* t) {
+  if (!t) return;
+  for (float* p : t->d_tail) (void)hipFree(p);
+  for (void* p : {(void*)t->d_off, (void*)t->d_idx, (void*)t->d_best, (void*)t->d_watch, (void*)t->d_pidx, (void*)t->d_cavg, (void*)t->d_pavg}) (void)hipFree(p);
+  for (void* p : {(void*)t->h_off, (void*)t->h_idx, (void*)t->h_best, (void*)t->h_watch, (void*)t->h_pidx, (void*)t->h_cavg, (void*)t->h_pavg}) (void)hipHostFree(p);
+  delete t;
+}
+
+// (cfg.cand_cap is a limit, not an allocation: an adapter that cannot know its traffic states fft_size x max_batch and pays for what comes)
+int st_grow_cands(st_ctx* t, size_t need) {
+  if (need <= t->cand_alloc) return SS_OK;
+  const size_t cap = std::min((size_t)t->cfg.cand_cap, std::max({need, t->cand_alloc * 2, (size_t)4096}));
+  for (void* p : {(void*)t->d_idx, (void*)t->d_best, (void*)t->d_cavg}) (void)hipFree(p);
+  for (void* p : {(void*)t->h_idx, (void*)t->h_best, (void*)t->h_cavg}) (void)hipHostFree(p);
+  t->d_idx = t->d_best = t->h_idx = t->h_best = nullptr;
+  t->d_cavg = t->h_cavg = nullptr;
+  t->cand_alloc = 0;
+  ST_HIP(t, hipMalloc(&t->d_idx, sizeof(int32_t) * cap));
+  ST_HIP(t, hipMalloc(&t->d_best, sizeof(int32_t) * cap));
+  ST_HIP(t, hipMalloc(&t->d_cavg, sizeof(float) * cap));
+  ST_HIP(t, hipHostMalloc(&t->h_idx, sizeof(int32_t) * cap));
+  ST_HIP(t, hipHostMalloc(&t->h_best, sizeof(int32_t) * cap));
+  ST_HIP(t, hipHostMalloc(&t->h_cavg, sizeof(float) * cap));
+  t->cand_alloc = cap;
+  return SS_OK;
+}
+
+int st_grow_peaks(st_ctx* t, size_t need) {
+  if (need <= t->peak_cap) return SS_OK;
+  const size_t cap = std::max(need, t->peak_cap * 2);
+  (void)hipFree(t->d_pidx);
+  (void)hipFree(t->d_pavg);
+  (void)hipHostFree(t->h_pidx);
+  (void)hipHostFree(t->h_pavg);
+  t->d_pidx = t->h_pidx = nullptr;
+  t->d_pavg = t->h_pavg = nullptr;
+  t->peak_cap = 0;
+  ST_HIP(t, hipMalloc(&t->d_pidx, sizeof(int32_t) * cap));
+  ST_HIP(t, hipMalloc(&t->d_pavg, sizeof(float) * cap));
+  ST_HIP(t, hipHostMalloc(&t->h_pidx, sizeof(int32_t) * cap));
+  ST_HIP(t, hipHostMalloc(&t->h_pavg, sizeof(float) * cap));
+  t->peak_cap = cap;
+  return SS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int st_create(ss_ctx* scan, const st_config* cfg, st_ctx** out) {
+  if (!scan || !cfg || !out) return st_fail(nullptr, SS_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (cfg->abi_version != ST_ABI_VERSION) return st_fail(nullptr, SS_ERR_INVALID, "abi_version %u, library has %u", cfg->abi_version, ST_ABI_VERSION);
+  if (cfg->group_size < 0 || cfg->max_watch <= 0 || cfg->cand_cap <= 0) return st_fail(nullptr, SS_ERR_INVALID, "group_size >= 0, max_watch > 0 and cand_cap > 0 required");
+  std::lock_guard<std::mutex> lock(scan->mtx);
+  if (!(scan->cfg.flags & SS_FLAG_KEEP_PLANES)) return st_fail(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_KEEP_PLANES (the digest reads the kept dB and avg planes)");
+  const int nrows = (scan->cfg.grouping_y + 1) / 2;
+  const size_t lds = sizeof(float) * (size_t)nrows * (size_t)(ss::kTrackTile + 2 * (cfg->group_size / 2)) + sizeof(int) * (size_t)nrows * ss::kTrackTile;
+  if (lds > 65536) return st_fail(nullptr, SS_ERR_INVALID, "group_size %d with %d rows needs %zu bytes of LDS per tile (64 KiB at most)", cfg->group_size, nrows, lds);
+  st_ctx* t = new (std::nothrow) st_ctx();
+  if (!t) return st_fail(nullptr, SS_ERR_NOMEM, "out of memory");
+  t->scan = scan;
+  t->cfg = *cfg;
+  t->nrows = nrows;
+  t->tail_rows = nrows - 1;
+  t->seen_batch = scan->batch_no;
+  const size_t tail_bytes = sizeof(float) * (size_t)std::max(1, t->tail_rows) * (size_t)scan->n;
+  const size_t frames = (size_t)scan->cfg.max_batch;
+  bool ok = hipSetDevice(scan->cfg.device_id) == hipSuccess;
+  for (int k = 0; k < 2 && ok; ++k) ok = hipMalloc(&t->d_tail[k], tail_bytes) == hipSuccess && hipMemsetAsync(t->d_tail[k], 0, tail_bytes, scan->stream) == hipSuccess;
+  ok = ok && hipMalloc(&t->d_off, sizeof(int32_t) * (frames + 1)) == hipSuccess && hipHostMalloc(&t->h_off, sizeof(int32_t) * (frames + 1)) == hipSuccess;
+  ok = ok && hipMalloc(&t->d_watch, sizeof(int32_t) * (size_t)cfg->max_watch) == hipSuccess && hipHostMalloc(&t->h_watch, sizeof(int32_t) * (size_t)cfg->max_watch) == hipSuccess;
+  ok = ok && hipStreamSynchronize(scan->stream) == hipSuccess;
+  if (!ok) {
+    const hipError_t e = hipGetLastError();
+    st_free(t);
+    return st_fail(nullptr, SS_ERR_NOMEM, "allocating the digest's buffers failed: %s", hipGetErrorString(e));
+  }
+  *out = t;
+  return SS_OK;
+}
+
+void st_destroy(st_ctx* t) {
+  if (!t) return;
+  {
+    std::lock_guard<std::mutex> lock(t->scan->mtx);
+    (void)hipSetDevice(t->scan->cfg.device_id);
+    (void)hipStreamSynchronize(t->scan->stream);
+  }
+  st_free(t);
+}
+
+const char* st_last_error(const st_ctx* t) { return t ? t->err : g_st_create_err; }
+
+int st_reset(st_ctx* t) {
+  if (!t) return SS_ERR_INVALID;
+  ss_ctx* c = t->scan;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  ST_HIP(t, hipSetDevice(c->cfg.device_id));
+  const size_t tail_bytes = sizeof(float) * (size_t)std::max(1, t->tail_rows) * (size_t)c->n;
+  ST_HIP(t, hipMemsetAsync(t->d_tail[t->tail_cur], 0, tail_bytes, c->stream));
+  ST_HIP(t, hipStreamSynchronize(c->stream));
+  t->seen_batch = c->batch_no;
+  return SS_OK;
+}
+
+int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const int32_t* keys, int32_t nkeys, st_result* out) {
+  if (!t) return SS_ERR_INVALID;
+  if (!cand_off || !out || nkeys < 0 || (nkeys > 0 && !keys)) return st_fail(t, SS_ERR_INVALID, "null argument");
+  ss_ctx* c = t->scan;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  const int n = c->n, nframes = c->last_n, G = c->cfg.grouping_y;
+  if (nframes <= 0) return st_fail(t, SS_ERR_INVALID, "no batch processed since ss_create / ss_reset / ss_reset_noise");
+  if (c->batch_no == t->seen_batch) return st_fail(t, SS_ERR_INVALID, "the last batch has been digested already (or none has run since st_create / st_reset)");
+  if (c->batch_no != t->seen_batch + 1)
+    return st_fail(t, SS_ERR_INVALID, "%llu batches went by without st_digest: the kept rel rows are stale until st_reset", c->batch_no - t->seen_batch - 1);
+  if (c->last_retunes != c->retunes) return st_fail(t, SS_ERR_INVALID, "ss_set_frequency_range since the last batch: its noise ceiling is not the current one");
+  if (!c->last_avg || (c->fused && (!c->last_psd || !c->last_thr))) return st_fail(t, SS_ERR_INVALID, "the last batch left no dB plane, avg plane or noise ceiling to digest");
+  // the lists: offsets clipped to what the batch's call could write (SS_ERR_CAND_OVERFLOW leaves truncated lists), bins checked
+  const int64_t cap = c->last_cand_cap > 0 ? c->last_cand_cap : 0;
+  int64_t prev = 0;
+  for (int f = 0; f <= nframes; ++f) {
+    int64_t o = cand_off[f];
+    if (o < prev || (f == 0 && o != 0)) return st_fail(t, SS_ERR_INVALID, "cand_off is not a list of offsets (frame %d)", f);
+    prev = o;
+    if (o > cap) o = cap;
+    t->h_off[f] = (int32_t)o;
+  }
+  const int ncand = t->h_off[nframes];
+  if (ncand > t->cfg.cand_cap) return st_fail(t, SS_ERR_INVALID, "%d candidates > cand_cap %d", ncand, t->cfg.cand_cap);
+  if (ncand > 0 && !cand_idx) return st_fail(t, SS_ERR_INVALID, "null argument");
+  ST_HIP(t, hipSetDevice(c->cfg.device_id));
+  if (const int st = st_grow_cands(t, (size_t)ncand); st != SS_OK) return st;
+  for (int j = 0; j < ncand; ++j) {
+    const int32_t b = cand_idx[j];
+    if (b < 0 || b >= n) return st_fail(t, SS_ERR_INVALID, "candidate %d: bin %d outside [0, %d)", j, b, n);
+    t->h_idx[j] = b;
+  }
+  if (nkeys > t->cfg.max_watch) return st_fail(t, SS_ERR_INVALID, "%d keys > max_watch %d", nkeys, t->cfg.max_watch);
+  for (int k = 0; k < nkeys; ++k)
+    if (keys[k] < 0 || keys[k] >= n) return st_fail(t, SS_ERR_INVALID, "key %d: bin %d outside [0, %d)", k, keys[k], n);
+  ST_HIP(t, hipSetDevice(c->cfg.device_id));
+  flush_stages(c);
+  ss::RelRows rows{};
+  rows.n = n;
+  rows.n_learn = c->last_n_learn;
+  rows.tail_rows = t->tail_rows;
+  rows.tail = t->d_tail[t->tail_cur];
+  if (c->fused) {
+    rows.psd = c->last_psd;
+    rows.thr = c->last_thr;
+  } else {
+    rows.rel = c->d_rel + (size_t)(G - 1) * n;
+  }
+  const int half = t->cfg.group_size / 2;
+  uint64_t d2h = 0;
+  if (ncand > 0) {
+    ST_HIP(t, hipMemcpyAsync(t->d_off, t->h_off, sizeof(int32_t) * ((size_t)nframes + 1), hipMemcpyHostToDevice, c->stream));
+    ST_HIP(t, hipMemcpyAsync(t->d_idx, t->h_idx, sizeof(int32_t) * (size_t)ncand, hipMemcpyHostToDevice, c->stream));
+    ss::CandBestArgs a{};
+    a.rows = rows;
+    a.avg = c->last_avg;
+    a.cand_off = t->d_off;
+    a.cand_idx = t->d_idx;
+    a.cand_best = t->d_best;
+    a.cand_avg = t->d_cavg;
+    a.nframes = nframes;
+    a.tiles = (n + ss::kTrackTile - 1) / ss::kTrackTile;
+    a.half = half;
+    a.nrows = t->nrows;
+    a.width = ss::kTrackTile + 2 * half;
+    a.start_level = t->cfg.start_level;
+    const size_t lds = sizeof(float) * (size_t)a.nrows * (size_t)a.width + sizeof(int) * (size_t)a.nrows * ss::kTrackTile;
+    hipLaunchKernelGGL(ss::k_cand_best, dim3((unsigned)((size_t)nframes * a.tiles)), dim3(ss::kTrackTile), lds, c->stream, a);
+    ST_HIP(t, hipGetLastError());
+    ST_HIP(t, hipMemcpyAsync(t->h_best, t->d_best, sizeof(int32_t) * (size_t)ncand, hipMemcpyDeviceToHost, c->stream));
+    ST_HIP(t, hipMemcpyAsync(t->h_cavg, t->d_cavg, sizeof(float) * (size_t)ncand, hipMemcpyDeviceToHost, c->stream));
+    ST_HIP(t, stream_wait(c->stream));
+    d2h += 8ull * (uint64_t)ncand;
+  }
+  // the watch list: every key the tracker can hold while it walks the batch
+  // (one flag per bin and a walk over the bins: a batch brings hundreds of thousands of candidates and a handful of distinct keys)
+  std::vector<int32_t>& w = t->merged;
+  w.clear();
+  t->mark.resize((size_t)n, 0);
+  for (int k = 0; k < nkeys; ++k) t->mark[(size_t)keys[k]] = 1;
+  bool sane = true;
+  for (int j = 0; j < ncand; ++j) {
+    const uint32_t b = (uint32_t)t->h_best[j];
+    if (b < (uint32_t)n) t->mark[b] = 1;
+    else sane = false;
+  }
+  for (int b = 0; b < n; ++b)
+    if (t->mark[(size_t)b]) {
+      w.push_back(b);
+      t->mark[(size_t)b] = 0;
+    }
+  if (!sane) return st_fail(t, SS_ERR_HIP, "k_cand_best returned a bin outside [0, %d)", n);
+  const int nwatch = (int)w.size();
+  if (nwatch > t->cfg.max_watch) return st_fail(t, SS_ERR_INVALID, "%d watch keys > max_watch %d", nwatch, t->cfg.max_watch);
+  if (nwatch > 0) {
+    const int st = st_grow_peaks(t, (size_t)nframes * (size_t)nwatch);
+    if (st != SS_OK) return st;
+    memcpy(t->h_watch, w.data(), sizeof(int32_t) * (size_t)nwatch);
+    ST_HIP(t, hipMemcpyAsync(t->d_watch, t->h_watch, sizeof(int32_t) * (size_t)nwatch, hipMemcpyHostToDevice, c->stream));
+    ss::WindowPeaksArgs p{};
+    p.avg = c->last_avg;
+    p.watch = t->d_watch;
+    p.peak_idx = t->d_pidx;
+    p.peak_avg = t->d_pavg;
+    p.n = n;
+    p.nframes = nframes;
+    p.nwatch = nwatch;
+    p.half = half;
+    const size_t items = (size_t)nframes * (size_t)nwatch;
+    hipLaunchKernelGGL(ss::k_window_peaks, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, c->stream, p);
+    ST_HIP(t, hipGetLastError());
+    ST_HIP(t, hipMemcpyAsync(t->h_pidx, t->d_pidx, sizeof(int32_t) * items, hipMemcpyDeviceToHost, c->stream));
+    ST_HIP(t, hipMemcpyAsync(t->h_pavg, t->d_pavg, sizeof(float) * items, hipMemcpyDeviceToHost, c->stream));
+    d2h += 8ull * (uint64_t)items;
+  }
+  if (t->tail_rows > 0) {
+    const size_t total = (size_t)t->tail_rows * (size_t)n;
+    hipLaunchKernelGGL(ss::k_save_tail, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream, rows, nframes, t->d_tail[t->tail_cur ^ 1]);
+    ST_HIP(t, hipGetLastError());
+  }
+  ST_HIP(t, stream_wait(c->stream));
+  if (t->tail_rows > 0) t->tail_cur ^= 1;
+  t->seen_batch = c->batch_no;
+  out->nframes = nframes;
+  out->ncand = ncand;
+  out->nwatch = nwatch;
+  out->cand_best = t->h_best;
+  out->cand_avg = t->h_cavg;
+  out->watch = t->h_watch;
+  out->peak_idx = t->h_pidx;
+  out->peak_avg = t->h_pavg;
+  out->d2h_bytes = d2h;
   return SS_OK;
 }
 

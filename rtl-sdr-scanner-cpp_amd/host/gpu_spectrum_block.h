@@ -16,6 +16,11 @@
 // what Transmission::process hands to m_notification.notify (transmission.cpp:67) — goes to a callback, so that the
 // Scanner thread (sources/scanner.cpp:36-64) sees exactly the interface it sees today.
 //
+// enableDeviceTracker does the same without the planes: the config carries SS_FLAG_KEEP_PLANES, work() asks ss_process for neither the
+// rel nor the avg plane (8 B/sample of PCIe traffic and a host copy of every row), st_digest (include/specscan_track.h) computes on
+// the device what the tracker would have read of them, and SignalTracker::processFrameDigest runs the same bookkeeping on that. The
+// callback sees the same sequence either way (tests/test_gpu_track_digest.py).
+//
 // With SS_FLAG_SPECTROGRAM in the config the Spectrogram side branch runs on the GPU as well (enableSpectrogram): the
 // block keeps Spectrogram::send's 1000 ms gate per centre frequency (spectrogram.cpp:62-75) and hands the int8 row to a
 // callback with DataController::pushSpectrogram's arguments; ss_spectrogram_payload frames it for the wire. The gate is
@@ -28,10 +33,13 @@
 #pragma once
 #include <gnuradio/sync_block.h>
 #include <specscan.h>
+#include <specscan_track.h>
 
 #include "signal_tracker.h"
 
+#include <algorithm>
 #include <atomic>
+#include <climits>
 #include <chrono>
 #include <cstdint>
 #include <functional>
@@ -63,7 +71,10 @@ class GpuSpectrum : virtual public gr::sync_block {
     m_center = (m_config.range_lo + m_config.range_hi) / 2;
   }
 
-  ~GpuSpectrum() override { ss_destroy(m_ctx); }
+  ~GpuSpectrum() override {
+    st_destroy(m_digest);
+    ss_destroy(m_ctx);
+  }
 
   // Bytes of one input item: N*D samples of the config's in_format (sizeof(gr_complex) each for CF32).
   static int inputItemBytes(const ss_config& config) {
@@ -79,10 +90,31 @@ class GpuSpectrum : virtual public gr::sync_block {
 
   // Run Transmission's signal bookkeeping on every frame and report what Notification::notify would receive.
   void enableTracker(const specscan::TrackerConfig& config, TransmissionCallback on_transmissions) {
+    st_destroy(m_digest);  // (a block that was tracking from the digest goes back to the planes)
+    m_digest = nullptr;
     m_tracker = std::make_unique<specscan::SignalTracker>(config);
     m_onTransmissions = std::move(on_transmissions);
     m_rel.resize(static_cast<size_t>(m_config.max_batch) * static_cast<size_t>(m_config.fft_size));
     m_avgPlane.resize(m_rel.size());
+  }
+  // The same, fed by the device-side digest instead of the rel / avg planes. The block's config must carry SS_FLAG_KEEP_PLANES.
+  void enableDeviceTracker(const specscan::TrackerConfig& config, TransmissionCallback on_transmissions, int32_t max_watch = 4096) {
+    st_config sc{};
+    sc.abi_version = ST_ABI_VERSION;
+    sc.group_size = config.group_size;
+    sc.start_level = config.start_level;
+    sc.max_watch = max_watch;
+    // (a limit, not an allocation: the lists this block hands over grow after an overflow, fft_size x max_batch bounds them for good)
+    sc.cand_cap = static_cast<int32_t>(std::min<int64_t>(static_cast<int64_t>(m_config.max_batch) * m_config.fft_size, INT32_MAX));
+    st_ctx* digest = nullptr;
+    if (st_create(m_ctx, &sc, &digest) != SS_OK) throw std::runtime_error(std::string("GpuSpectrum: ") + st_last_error(nullptr));
+    std::lock_guard<std::mutex> lock(m_mutex);
+    st_destroy(m_digest);
+    m_digest = digest;
+    m_tracker = std::make_unique<specscan::SignalTracker>(config);
+    m_onTransmissions = std::move(on_transmissions);
+    m_rel.clear();
+    m_avgPlane.clear();
   }
   void setClock(Clock clock) { m_clock = std::move(clock); }
 
@@ -102,7 +134,7 @@ class GpuSpectrum : virtual public gr::sync_block {
                                 : std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count();
     for (int f = 0; f < nframes; ++f) m_times[static_cast<size_t>(f)] = now;
     const int status = ss_process(m_ctx, input_items[0], nframes, m_times.data(), static_cast<float*>(output_items[0]),
-                                  m_tracker ? m_rel.data() : nullptr, m_tracker ? m_avgPlane.data() : nullptr, m_offsets.data(), m_bins.data(),
+                                  m_tracker && !m_digest ? m_rel.data() : nullptr, m_tracker && !m_digest ? m_avgPlane.data() : nullptr, m_offsets.data(), m_bins.data(),
                                   m_avg.data(), static_cast<int32_t>(m_bins.size()));
     size_t grow_to = 0;
     if (status == SS_ERR_CAND_OVERFLOW) {
@@ -127,7 +159,29 @@ class GpuSpectrum : virtual public gr::sync_block {
         m_onCandidates(f, m_bins.data() + begin, m_avg.data() + begin, end - begin);
       }
     }
-    if (m_tracker) {
+    if (m_tracker && m_digest) {
+      std::lock_guard<std::mutex> lock(m_mutex);
+      const std::vector<int> keys = m_tracker->signalKeys();
+      st_result d{};
+      // (a resetBuffers() from the Scanner's thread since ss_process returned leaves no batch to digest: reported, nothing tracked)
+      if (st_digest(m_digest, m_offsets.data(), m_bins.data(), keys.data(), static_cast<int32_t>(keys.size()), &d) != SS_OK) {
+        m_lastError = st_last_error(m_digest);
+      } else {
+        const int32_t cap = d.ncand;  // (the lists as the digest clipped them: to this call's capacity)
+        for (int f = 0; f < d.nframes; ++f) {
+          const int32_t begin = m_offsets[static_cast<size_t>(f)] < cap ? m_offsets[static_cast<size_t>(f)] : cap;
+          const int32_t end = m_offsets[static_cast<size_t>(f) + 1] < cap ? m_offsets[static_cast<size_t>(f) + 1] : cap;
+          const size_t row = static_cast<size_t>(f) * static_cast<size_t>(d.nwatch);
+          const auto* tx = m_tracker->processFrameDigest(now, m_bins.data() + begin, d.cand_avg + begin, d.cand_best + begin, end - begin, d.watch,
+                                                         d.nwatch, d.peak_idx + row, d.peak_avg + row);
+          if (!tx) {
+            m_lastError = "a tracked key is missing from the digest's watch list";
+            break;
+          }
+          if (m_onTransmissions) m_onTransmissions(*tx);
+        }
+      }
+    } else if (m_tracker) {
       std::lock_guard<std::mutex> lock(m_mutex);
       const int32_t cap = static_cast<int32_t>(m_bins.size());
       const size_t n = static_cast<size_t>(m_config.fft_size);
@@ -161,11 +215,14 @@ class GpuSpectrum : virtual public gr::sync_block {
   void setFrequencyRange(int32_t lo_hz, int32_t hi_hz) {
     ss_set_frequency_range(m_ctx, lo_hz, hi_hz);
     m_center = (lo_hz + hi_hz) / 2;
+    std::lock_guard<std::mutex> lock(m_mutex);
+    if (m_digest) st_reset(m_digest);  // (the rows it kept belong to the old range; SdrDevice::setFrequencyRange resets the buffers next anyway)
   }
   void resetBuffers() {  // Transmission::resetBuffers, transmission.cpp:42-55: signals cleared, averager reset
     ss_reset(m_ctx);
     std::lock_guard<std::mutex> lock(m_mutex);
     if (m_tracker) m_tracker->reset();
+    if (m_digest) st_reset(m_digest);
   }
   const std::string& lastError() const { return m_lastError; }
   int candidateOverflows() const { return m_overflows; }  // work() calls whose lists were cut (capacity grows each time)
@@ -179,6 +236,7 @@ class GpuSpectrum : virtual public gr::sync_block {
   std::vector<int64_t> m_times;
   std::string m_lastError;
   std::unique_ptr<specscan::SignalTracker> m_tracker;
+  st_ctx* m_digest = nullptr;  // enableDeviceTracker: the tracker runs on st_digest's result instead of the planes
   TransmissionCallback m_onTransmissions;
   Clock m_clock;
   std::vector<float> m_rel, m_avgPlane;

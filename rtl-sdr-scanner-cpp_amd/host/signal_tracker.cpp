@@ -110,6 +110,54 @@ const std::vector<FrequencyFlush>& SignalTracker::processFrame(int64_t now, cons
     if (m_config.stop_level <= avg[bestAvg]) s.last_ms = now;
     if (m_config.start_level <= avg[bestAvg]) s.indexes.push_back(bestAvg);
   }
+  return clearAndReport(now);
+}
+
+// The digest form of processFrame: the same steps in the same order, with its three reads of the planes — the candidates' avg values,
+// getBestIndex of a candidate, the window arg-max of the avg row around a tracked key — replaced by what the device computed from the
+// same planes (include/specscan_track.h). The tracker's own ring is neither written nor read: do not mix the two forms on one
+// tracker without a reset() in between.
+const std::vector<FrequencyFlush>* SignalTracker::processFrameDigest(int64_t now, const int32_t* cand_idx, const float* cand_avg,
+                                                                     const int32_t* cand_best, int ncand, const int32_t* watch, int nwatch,
+                                                                     const int32_t* peak_idx, const float* peak_avg) {
+  // addSignals — transmission.cpp:88-111: the same std::sort on the same initial order, the key carried along instead of looked up
+  struct Candidate {
+    int index;
+    float avg;
+    int best;
+  };
+  std::vector<Candidate> indexes(static_cast<size_t>(ncand));
+  for (int j = 0; j < ncand; ++j) indexes[static_cast<size_t>(j)] = {cand_idx[j], cand_avg[j], cand_best[j]};
+  std::sort(indexes.begin(), indexes.end(), [](const Candidate& i1, const Candidate& i2) { return i1.avg > i2.avg; });
+  for (const Candidate& c : indexes) {
+    if (!containsWithMargin(m_signals, c.index, m_config.group_size)) {
+      m_signals.insert({c.best, Signal{now, now, 0.0f, {}}});
+    }
+  }
+  // updateSignals — transmission.cpp:113-130. Both lists ascend: one walk finds every key's column; a key the watch list lacks is
+  // the caller's error (nothing is guessed, and no signal has been updated yet)
+  std::vector<int> column;
+  column.reserve(m_signals.size());
+  const int32_t* w = watch;
+  for (const auto& kv : m_signals) {
+    w = std::lower_bound(w, watch + nwatch, kv.first);
+    if (w == watch + nwatch || *w != kv.first) return nullptr;
+    column.push_back(static_cast<int>(w - watch));
+  }
+  size_t k = 0;
+  for (auto& kv : m_signals) {
+    Signal& s = kv.second;
+    const int bestAvg = peak_idx[column[k]];
+    const float power = peak_avg[column[k]];
+    ++k;
+    s.power = power;
+    if (m_config.stop_level <= power) s.last_ms = now;
+    if (m_config.start_level <= power) s.indexes.push_back(bestAvg);
+  }
+  return &clearAndReport(now);
+}
+
+const std::vector<FrequencyFlush>& SignalTracker::clearAndReport(int64_t now) {
   // clearSignals — transmission.cpp:70-86, Signal::isTimeout / isMaximalTime — signal.cpp:28-30
   for (auto it = m_signals.begin(); it != m_signals.end();) {
     const Signal& s = it->second;
@@ -133,6 +181,32 @@ const std::vector<FrequencyFlush>& SignalTracker::processFrame(int64_t now, cons
 }
 
 }  // namespace specscan
+
+namespace {
+
+// tx_out: pairs (shift_hz, flush); sig_out: the tracked keys — what both C entry points hand back
+int report(const specscan::SignalTracker& t, const std::vector<specscan::FrequencyFlush>& tx, int32_t* tx_out, int tx_cap, int32_t* sig_out, int sig_cap,
+           int* nsig) {
+  int k = 0;
+  for (const auto& x : tx) {
+    if (k >= tx_cap) break;
+    tx_out[2 * k] = x.shift_hz;
+    tx_out[2 * k + 1] = x.flush ? 1 : 0;
+    ++k;
+  }
+  if (nsig) {
+    const auto keys = t.signalKeys();
+    int m = 0;
+    for (const int key : keys) {
+      if (m >= sig_cap) break;
+      sig_out[m++] = key;
+    }
+    *nsig = static_cast<int>(keys.size());
+  }
+  return static_cast<int>(tx.size());
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -159,24 +233,17 @@ void sst_reset(void* tracker) { static_cast<specscan::SignalTracker*>(tracker)->
 int sst_process_frame(void* tracker, int64_t now_ms, const float* avg, const float* raw, const int32_t* candidates, int ncand, int32_t* tx_out,
                       int tx_cap, int32_t* sig_out, int sig_cap, int* nsig) {
   auto* t = static_cast<specscan::SignalTracker*>(tracker);
-  const auto& tx = t->processFrame(now_ms, avg, raw, candidates, ncand);
-  int k = 0;
-  for (const auto& x : tx) {
-    if (k >= tx_cap) break;
-    tx_out[2 * k] = x.shift_hz;
-    tx_out[2 * k + 1] = x.flush ? 1 : 0;
-    ++k;
-  }
-  if (nsig) {
-    const auto keys = t->signalKeys();
-    int m = 0;
-    for (const int key : keys) {
-      if (m >= sig_cap) break;
-      sig_out[m++] = key;
-    }
-    *nsig = static_cast<int>(keys.size());
-  }
-  return static_cast<int>(tx.size());
+  return report(*t, t->processFrame(now_ms, avg, raw, candidates, ncand), tx_out, tx_cap, sig_out, sig_cap, nsig);
+}
+
+int sst_process_frame_digest(void* tracker, int64_t now_ms, const int32_t* cand_idx, const float* cand_avg, const int32_t* cand_best, int ncand,
+                             const int32_t* watch, int nwatch, const int32_t* peak_idx, const float* peak_avg, int32_t* tx_out, int tx_cap,
+                             int32_t* sig_out, int sig_cap, int* nsig) {
+  auto* t = static_cast<specscan::SignalTracker*>(tracker);
+  if (ncand < 0 || nwatch < 0) return -1;
+  const auto* tx = t->processFrameDigest(now_ms, cand_idx, cand_avg, cand_best, ncand, watch, nwatch, peak_idx, peak_avg);
+  if (!tx) return -1;
+  return report(*t, *tx, tx_out, tx_cap, sig_out, sig_cap, nsig);
 }
 
 }  // extern "C"

@@ -52,6 +52,14 @@ class SignalTracker {
   // Returns the vector the reference hands to Notification::notify (transmission.cpp:67).
   const std::vector<FrequencyFlush>& processFrame(int64_t now_ms, const float* avg, const float* raw, const int32_t* candidates, int ncand);
 
+  // The same frame from a device-side digest (include/specscan_track.h) instead of the planes: cand_avg[j] = avg[cand_idx[j]],
+  // cand_best[j] = getBestIndex(cand_idx[j]) at this frame, and for every key in watch (ascending; it must hold every tracked key and
+  // every cand_best) the arg-max peak_idx[w] and maximum peak_avg[w] of the avg row over the key's window. Same steps, same order, same
+  // std::sort: the result equals processFrame's on the planes the digest was taken from. nullptr — and no signal updated — when a
+  // tracked key is missing from watch. The tracker's own ring is not used: reset() before switching between the two forms.
+  const std::vector<FrequencyFlush>* processFrameDigest(int64_t now_ms, const int32_t* cand_idx, const float* cand_avg, const int32_t* cand_best,
+                                                        int ncand, const int32_t* watch, int nwatch, const int32_t* peak_idx, const float* peak_avg);
+
   void reset();  // Transmission::resetBuffers (transmission.cpp:42-55): signals cleared, ring zeroed
   std::vector<int> signalKeys() const;
 
@@ -62,6 +70,7 @@ class SignalTracker {
     std::vector<int> indexes;
   };
   int getBestIndex(int index) const;
+  const std::vector<FrequencyFlush>& clearAndReport(int64_t now_ms);  // clearSignals, getSortedTransmissions
   int32_t indexToShift(int index) const;
 
   TrackerConfig m_config;
@@ -83,4 +92,9 @@ void sst_reset(void* tracker);
 // Returns the number of transmissions; *nsig receives the number of tracked signals.
 int sst_process_frame(void* tracker, int64_t now_ms, const float* avg, const float* raw, const int32_t* candidates, int ncand,
                       int32_t* tx_out, int tx_cap, int32_t* sig_out, int sig_cap, int* nsig);
+// One frame of an st_digest result (SignalTracker::processFrameDigest): cand_* are the frame's slices of the candidate lists,
+// peak_idx / peak_avg the frame's rows. Returns -1 when a tracked key is missing from watch.
+int sst_process_frame_digest(void* tracker, int64_t now_ms, const int32_t* cand_idx, const float* cand_avg, const int32_t* cand_best, int ncand,
+                             const int32_t* watch, int nwatch, const int32_t* peak_idx, const float* peak_avg, int32_t* tx_out, int tx_cap,
+                             int32_t* sig_out, int sig_cap, int* nsig);
 }

@@ -1,5 +1,7 @@
 """ctypes binding of host/libspecscan_host.so — the host-side signal tracker (host/signal_tracker.h), the part of
-the reference's Transmission block that turns per-frame candidates into the Scanner's (shift Hz, flush) list."""
+the reference's Transmission block that turns per-frame candidates into the Scanner's (shift Hz, flush) list — and of the
+st_* entry points of libspecscan.so (include/specscan_track.h), the device-side digest that tracker can run on instead of
+the rel and avg planes."""
 from __future__ import annotations
 
 import ctypes as C
@@ -28,6 +30,9 @@ def load_host_library() -> C.CDLL:
         lib.sst_process_frame.argtypes = [C.c_void_p, C.c_int64, c_float_p, c_float_p, c_int32_p, C.c_int, c_int32_p, C.c_int, c_int32_p,
                                           C.c_int, C.POINTER(C.c_int)]
         lib.sst_process_frame.restype = C.c_int
+        lib.sst_process_frame_digest.argtypes = [C.c_void_p, C.c_int64, c_int32_p, c_float_p, c_int32_p, C.c_int, c_int32_p, C.c_int, c_int32_p,
+                                                 c_float_p, c_int32_p, C.c_int, c_int32_p, C.c_int, C.POINTER(C.c_int)]
+        lib.sst_process_frame_digest.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -49,6 +54,9 @@ class SignalTracker:
             raise ValueError("bad tracker configuration")
         self._tx = np.empty(2 * fft_size, np.int32)
         self._sig = np.empty(fft_size, np.int32)
+        self.group_size = group_size
+        self.start_level = start_level
+        self.keys = np.zeros(0, np.int32)  # the tracked keys after the last frame: what the next st_digest must watch
 
     def close(self):
         if getattr(self, "_h", None):
@@ -63,6 +71,7 @@ class SignalTracker:
 
     def reset(self):
         self._lib.sst_reset(self._h)
+        self.keys = np.zeros(0, np.int32)
 
     def process_frame(self, now_ms: int, avg_row: np.ndarray, rel_row: np.ndarray, candidates: np.ndarray):
         """Returns (transmissions [k, 2] = (shift Hz, flush), tracked signal keys)."""
@@ -73,10 +82,120 @@ class SignalTracker:
         ntx = self._lib.sst_process_frame(self._h, int(now_ms), a.ctypes.data_as(c_float_p), r.ctypes.data_as(c_float_p),
                                           c.ctypes.data_as(c_int32_p), c.size, self._tx.ctypes.data_as(c_int32_p), self.n,
                                           self._sig.ctypes.data_as(c_int32_p), self.n, C.byref(nsig))
-        return self._tx[:2 * ntx].reshape(-1, 2).copy(), self._sig[:nsig.value].copy()
+        self.keys = self._sig[:nsig.value].copy()
+        return self._tx[:2 * ntx].reshape(-1, 2).copy(), self.keys
+
+    def process_frame_digest(self, now_ms: int, cand_idx, cand_avg, cand_best, watch, peak_idx_row, peak_avg_row):
+        """One frame of a digest (include/specscan_track.h): the frame's slices of the candidate lists, the watch list and the
+        frame's rows of the peaks. Same return as process_frame; ValueError when a tracked key is missing from ``watch``."""
+        ci = np.ascontiguousarray(cand_idx, np.int32)
+        ca = np.ascontiguousarray(cand_avg, np.float32)
+        cb = np.ascontiguousarray(cand_best, np.int32)
+        w = np.ascontiguousarray(watch, np.int32)
+        pi = np.ascontiguousarray(peak_idx_row, np.int32)
+        pa = np.ascontiguousarray(peak_avg_row, np.float32)
+        if not (ci.size == ca.size == cb.size) or not (w.size == pi.size == pa.size):
+            raise ValueError("digest arrays of different lengths")
+        nsig = C.c_int()
+        ntx = self._lib.sst_process_frame_digest(self._h, int(now_ms), ci.ctypes.data_as(c_int32_p), ca.ctypes.data_as(c_float_p),
+                                                 cb.ctypes.data_as(c_int32_p), ci.size, w.ctypes.data_as(c_int32_p), w.size,
+                                                 pi.ctypes.data_as(c_int32_p), pa.ctypes.data_as(c_float_p), self._tx.ctypes.data_as(c_int32_p),
+                                                 self.n, self._sig.ctypes.data_as(c_int32_p), self.n, C.byref(nsig))
+        if ntx < 0:
+            raise ValueError("a tracked key is missing from the digest's watch list")
+        self.keys = self._sig[:nsig.value].copy()
+        return self._tx[:2 * ntx].reshape(-1, 2).copy(), self.keys
+
+    def process_batch_digest(self, t_ms, result):
+        """A whole batch from ``TrackDigest.digest`` (or any dict with the same arrays): what process_batch returns on the planes."""
+        off, watch = result["cand_off"], result["watch"]
+        out = []
+        for f in range(len(off) - 1):
+            a, b = int(off[f]), int(off[f + 1])
+            out.append(self.process_frame_digest(t_ms[f], result["cand_idx"][a:b], result["cand_avg"][a:b], result["cand_best"][a:b], watch,
+                                                 result["peak_idx"][f], result["peak_avg"][f]))
+        return out
 
     def process_batch(self, t_ms, avg, rel, cand_off, cand_idx):
         out = []
         for f in range(avg.shape[0]):
             out.append(self.process_frame(t_ms[f], avg[f], rel[f], cand_idx[cand_off[f]:cand_off[f + 1]]))
         return out
+
+
+class StConfig(C.Structure):  # st_config, include/specscan_track.h
+    _fields_ = [("abi_version", C.c_uint32), ("group_size", C.c_int32), ("start_level", C.c_float), ("max_watch", C.c_int32), ("cand_cap", C.c_int32)]
+
+
+class StResult(C.Structure):  # st_result
+    _fields_ = [("nframes", C.c_int32), ("ncand", C.c_int32), ("nwatch", C.c_int32), ("cand_best", c_int32_p), ("cand_avg", c_float_p),
+                ("watch", c_int32_p), ("peak_idx", c_int32_p), ("peak_avg", c_float_p), ("d2h_bytes", C.c_uint64)]
+
+
+ST_ABI_VERSION = 1
+
+
+def bind_track(lib: C.CDLL) -> None:
+    lib.st_create.argtypes = [C.c_void_p, C.POINTER(StConfig), C.POINTER(C.c_void_p)]
+    lib.st_create.restype = C.c_int
+    lib.st_destroy.argtypes = [C.c_void_p]
+    lib.st_destroy.restype = None
+    lib.st_last_error.argtypes = [C.c_void_p]
+    lib.st_last_error.restype = C.c_char_p
+    lib.st_reset.argtypes = [C.c_void_p]
+    lib.st_reset.restype = C.c_int
+    lib.st_digest.argtypes = [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, C.c_int32, C.POINTER(StResult)]
+    lib.st_digest.restype = C.c_int
+
+
+class TrackDigest:
+    """One st_ctx bound to a SpectrumEngine created with SS_FLAG_KEEP_PLANES (SpectrumEngine.track_digest). Call ``digest`` once
+    after every batch, ``reset`` with the engine's ``reset``."""
+
+    def __init__(self, engine, group_size: int, start_level: float = 8.0, max_watch: int = 1024, cand_cap: int = 1 << 20):
+        from .abi import SpecscanError
+        self._err = SpecscanError
+        self._engine = engine  # (the scan context must outlive the digest object)
+        self._lib = engine._lib
+        bind_track(self._lib)
+        cfg = StConfig(ST_ABI_VERSION, int(group_size), float(start_level), int(max_watch), int(cand_cap))
+        h = C.c_void_p()
+        st = self._lib.st_create(engine._h, C.byref(cfg), C.byref(h))
+        if st != 0:
+            raise SpecscanError(st, (self._lib.st_last_error(None) or b"").decode())
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._engine, "_h", None):  # (an engine closed first took its stream with it; the object is only freed)
+                self._lib.st_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        if st != 0:
+            raise self._err(st, (self._lib.st_last_error(self._h) or b"").decode())
+
+    def reset(self):
+        self._check(self._lib.st_reset(self._h))
+
+    def digest(self, cand_off, cand_idx, keys) -> dict:
+        """The digest of the engine's last batch as numpy copies: cand_off (clipped to the lists), cand_idx, cand_best, cand_avg,
+        watch, peak_idx / peak_avg [nframes, nwatch], d2h_bytes."""
+        off = np.ascontiguousarray(cand_off, np.int32)
+        idx = np.ascontiguousarray(cand_idx, np.int32)
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1)
+        r = StResult()
+        self._check(self._lib.st_digest(self._h, off.ctypes.data_as(c_int32_p), idx.ctypes.data_as(c_int32_p), k.ctypes.data_as(c_int32_p), k.size,
+                                        C.byref(r)))
+        take = lambda p, count, dt: np.ctypeslib.as_array(p, shape=(count,)).astype(dt, copy=True) if count else np.zeros(0, dt)  # noqa: E731
+        nf, nc, nw = r.nframes, r.ncand, r.nwatch
+        return {"nframes": nf, "cand_off": np.minimum(off[:nf + 1], nc).astype(np.int32), "cand_idx": idx[:nc].copy(),
+                "cand_best": take(r.cand_best, nc, np.int32), "cand_avg": take(r.cand_avg, nc, np.float32), "watch": take(r.watch, nw, np.int32),
+                "peak_idx": take(r.peak_idx, nf * nw, np.int32).reshape(nf, nw), "peak_avg": take(r.peak_avg, nf * nw, np.float32).reshape(nf, nw),
+                "d2h_bytes": int(r.d2h_bytes)}

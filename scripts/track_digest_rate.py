@@ -1,0 +1,130 @@
+"""Transmissions per batch, two routes, one process, the same synthetic stream (synth.SyntheticBand):
+
+  (a) planes:  ss_process with rel_db and avg_db, then sst_process_frame per frame          — what enableTracker does
+  (b) digest:  ss_process without them (SS_FLAG_KEEP_PLANES), st_digest, then
+               sst_process_frame_digest per frame                                           — what enableDeviceTracker does
+
+at 8192 points in 1024-frame batches and at 2^20 points in 16-frame batches. Wall clock around the whole batch (the call, the
+digest, the tracker's frames), median of --reps repetitions after a warm-up; both routes go through the C ABI with buffers allocated
+once, and the per-frame loop is the same Python loop in both. Prints one JSON line per shape. With --route b only route (b) runs:
+the form to put behind `rocprofv3 --kernel-trace --stats --` for the device times of k_cand_best and k_window_peaks.
+
+    python scripts/track_digest_rate.py [--reps 7] [--route ab|a|b] [--shapes 8192,1048576]
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import rtl_sdr_scanner_cpp_amd as pkg  # noqa: E402
+from rtl_sdr_scanner_cpp_amd import abi, tracker  # noqa: E402
+
+f32p, i32p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+
+
+def at(a, offset_elems, typ):
+    return C.cast(a.ctypes.data + offset_elems * a.itemsize, typ)
+
+
+class Route:
+    def __init__(self, n, fs, batch, g, digest: bool):
+        self.n, self.batch, self.digest = n, batch, digest
+        self.eng = pkg.SpectrumEngine(fs, 145_000_000, fft_size=n, decim=1, max_batch=batch, learn_ms=280, flags=abi.SS_FLAG_KEEP_PLANES if digest else 0)
+        self.trk = tracker.SignalTracker(n, fs, group_size=g, min_time_ms=200, timeout_ms=400)
+        self.cap = batch * 1024
+        self.psd = np.empty((batch, n), np.float32)
+        self.rel = None if digest else np.empty((batch, n), np.float32)
+        self.avg = None if digest else np.empty((batch, n), np.float32)
+        self.off = np.zeros(batch + 1, np.int32)
+        self.idx = np.empty(self.cap, np.int32)
+        self.cav = np.empty(self.cap, np.float32)
+        self.tx = np.empty(2 * n, np.int32)
+        self.sig = np.empty(n, np.int32)
+        self.nsig = C.c_int()
+        self.dig = self.eng.track_digest(g, max_watch=4096, cand_cap=self.cap) if digest else None
+        self.res = tracker.StResult()
+        self.keys = np.zeros(n, np.int32)
+        self.nkeys = 0
+        self.d2h = 0
+
+    def run(self, iq, t):
+        """One batch; returns (seconds, transmissions)."""
+        lib, hl, n, nf = self.eng._lib, self.trk._lib, self.n, self.batch
+        seen = 0
+        t0 = time.perf_counter()
+        st = lib.ss_process(self.eng._h, iq.ctypes.data_as(C.c_void_p), nf, t.ctypes.data_as(i64p), at(self.psd, 0, f32p),
+                            None if self.digest else at(self.rel, 0, f32p), None if self.digest else at(self.avg, 0, f32p), at(self.off, 0, i32p),
+                            at(self.idx, 0, i32p), at(self.cav, 0, f32p), self.cap)
+        assert st == 0, (st, lib.ss_last_error(self.eng._h))
+        off = self.off.tolist()
+        if self.digest:
+            st = lib.st_digest(self.dig._h, at(self.off, 0, i32p), at(self.idx, 0, i32p), at(self.keys, 0, i32p), self.nkeys, C.byref(self.res))
+            assert st == 0, (st, lib.st_last_error(self.dig._h))
+            r = self.res
+            best, cavg, pidx, pavg = (C.addressof(p.contents) if p else 0 for p in (r.cand_best, r.cand_avg, r.peak_idx, r.peak_avg))
+            nw = r.nwatch
+            self.d2h = int(r.d2h_bytes)
+            for f in range(nf):
+                a, b = off[f], off[f + 1]
+                seen += hl.sst_process_frame_digest(self.trk._h, int(t[f]), at(self.idx, a, i32p), C.cast(cavg + 4 * a, f32p), C.cast(best + 4 * a, i32p), b - a,
+                                                    r.watch, nw, C.cast(pidx + 4 * f * nw, i32p), C.cast(pavg + 4 * f * nw, f32p), at(self.tx, 0, i32p), n,
+                                                    at(self.sig, 0, i32p), n, C.byref(self.nsig))
+            self.nkeys = self.nsig.value
+            self.keys[:self.nkeys] = self.sig[:self.nkeys]
+        else:
+            for f in range(nf):
+                a, b = off[f], off[f + 1]
+                seen += hl.sst_process_frame(self.trk._h, int(t[f]), at(self.avg, f * n, f32p), at(self.rel, f * n, f32p), at(self.idx, a, i32p), b - a,
+                                             at(self.tx, 0, i32p), n, at(self.sig, 0, i32p), n, C.byref(self.nsig))
+        return time.perf_counter() - t0, seen
+
+
+def shape(n, batch, g, reps, routes, warm=3, distinct=4):
+    fs = 2_048_000 if n == 8192 else n * 250
+    band = pkg.synth.SyntheticBand(n, seed=0, on_frame=batch // 8 + 30, off_frame=5 * max(batch, 64) // 8 + 30, period=max(batch, 64) + 60)
+    batches = [band.frames_cf32(batch) for _ in range(distinct)]
+    out = {"fft_size": n, "batch": batch, "group_size": g, "reps": reps}
+    made = {name: Route(n, fs, batch, g, digest=name == "b") for name in routes}
+    times = {name: [] for name in routes}
+    seen = {name: 0 for name in routes}
+    for k in range(warm + reps):  # the routes alternate batch by batch: whatever else the host does meets both
+        t = (1_000 + 40 * (k * batch + np.arange(batch))).astype(np.int64)
+        for name, route in made.items():
+            dt, tx = route.run(batches[k % distinct], t)
+            if k >= warm:
+                times[name].append(dt)
+                seen[name] += tx
+    for name, route in made.items():
+        label = "planes" if name == "a" else "digest"
+        out[f"{label}_ms_median"] = round(1e3 * statistics.median(times[name]), 3)
+        out[f"{label}_ms_all"] = [round(1e3 * x, 3) for x in times[name]]
+        out[f"{label}_transmissions"] = seen[name]
+        if name == "b":
+            out["digest_d2h_bytes_last"] = route.d2h
+            out["planes_d2h_bytes"] = 8 * n * batch
+    if len(routes) == 2:
+        out["same_transmission_count"] = seen["a"] == seen["b"]  # (tests/test_gpu_track_digest.py holds the two routes to each other frame by frame)
+        out["digest_over_planes"] = round(out["digest_ms_median"] / out["planes_ms_median"], 4)
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--route", default="ab", choices=("ab", "a", "b"))
+    ap.add_argument("--shapes", default="8192,1048576")
+    args = ap.parse_args()
+    for n in (int(s) for s in args.shapes.split(",")):
+        shape(n, 1024 if n == 8192 else 16, 128 if n == 8192 else 547, args.reps, list(args.route))
+
+
+if __name__ == "__main__":
+    main()
