@@ -22,8 +22,8 @@
  * Use: after every batch (ss_process, or ss_process_device + ss_sync) call st_digest once with the batch's candidate
  * lists and the tracker's current keys (SignalTracker::signalKeys). The object keeps the batch's last
  * ceil(grouping_y / 2) - 1 rel rows for the next batch's first frames, so a batch that went by without st_digest
- * makes the next st_digest fail until st_reset. Call st_reset with ss_reset. Not for the ss_feed_* pipeline (several
- * batches in flight: the last batch is not the collected one).
+ * makes the next st_digest fail until st_reset. Call st_reset with ss_reset. The ss_feed_* pipeline (several
+ * batches in flight: the last batch is not the collected one) has its own form of the digest: specscan_track_feed.h.
  */
 #ifndef SPECSCAN_TRACK_H
 #define SPECSCAN_TRACK_H

@@ -13,8 +13,8 @@ LIB = os.path.join(CSRC, "libspecscan.so")
 LIB_DIAG = os.path.join(CSRC, "libspecscan_diag.so")
 SOURCES = ["specscan.hip", "channelizer.hip"]
 HEADERS = ["fft_kernels.h", "fft8192_kernel.h", "fft8192_v2.h", "scan_step.h", "fft256_kernels.h", "detect_kernels.h", "detect_fused.h", "reference_nan.h", "fft1024_kernels.h", "ring_place.h",
-           "track_digest.h", os.path.join("..", "..", "include", "specscan.h"), os.path.join("..", "..", "include", "specscan_channelizer.h"),
-           os.path.join("..", "..", "include", "specscan_track.h")]
+           "track_digest.h", "track_feed.h", os.path.join("..", "..", "include", "specscan.h"), os.path.join("..", "..", "include", "specscan_channelizer.h"),
+           os.path.join("..", "..", "include", "specscan_track.h"), os.path.join("..", "..", "include", "specscan_track_feed.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC", "-shared", "-Wall", "-Wno-unused-result"]
 
 
@@ -80,11 +80,13 @@ REPLAY_TOOL = os.path.join(HOST_DIR, "specscan_replay")
 def build_replay_tool(force: bool = False, verbose: bool = False) -> str:
     """g++ -> host/specscan_replay: the C++ replay host (host/replay_main.cpp) linked against libspecscan.so."""
     src = os.path.join(HOST_DIR, "replay_main.cpp")
-    deps = [src, os.path.join(HOST_DIR, "raw_file.h"), os.path.join(HERE, "..", "include", "specscan.h"), LIB]
+    tracker = os.path.join(HOST_DIR, "signal_tracker.cpp")
+    deps = [src, tracker, os.path.join(HOST_DIR, "raw_file.h"), os.path.join(HOST_DIR, "signal_tracker.h"), os.path.join(HERE, "..", "include", "specscan.h"),
+            os.path.join(HERE, "..", "include", "specscan_track_feed.h"), LIB]
     if force or not os.path.exists(REPLAY_TOOL) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(REPLAY_TOOL):
         build_lib()
         cmd = [shutil.which("g++") or "g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Wpedantic", "-Werror",
-               "-I" + os.path.join(HERE, "..", "include"), "-o", REPLAY_TOOL, src, "-L" + CSRC, "-lspecscan", "-Wl,-rpath,$ORIGIN/../csrc",
+               "-I" + os.path.join(HERE, "..", "include"), "-o", REPLAY_TOOL, src, tracker, "-L" + CSRC, "-lspecscan", "-Wl,-rpath,$ORIGIN/../csrc",
                "-Wl,-rpath-link," + os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib"), "-lpthread"]
         if verbose:
             print(" ".join(cmd))

@@ -24,6 +24,7 @@
 
 #include "../../include/specscan.h"
 #include "../../include/specscan_track.h"
+#include "../../include/specscan_track_feed.h"
 #include "detect_fused.h"
 #include "detect_kernels.h"
 #include "fft1024_kernels.h"
@@ -33,6 +34,7 @@
 #include "ring_place.h"
 #include "scan_step.h"
 #include "track_digest.h"
+#include "track_feed.h"
 
 namespace {
 
@@ -3360,9 +3362,15 @@ struct ss_feed {
   std::vector<ss_feed_slot> slots;
   int next_acquire = 0, next_collect = 0, pending = 0, acquired = -1;
   hipStream_t copy_stream = nullptr, d2h_stream = nullptr;
+  stf_ctx* tracker = nullptr;  // stf_create: every batch is digested behind its chain (include/specscan_track_feed.h)
 };
 
 namespace {
+// (the tracked feed, further down)
+int stf_enqueue(ss_feed* f, int slot, int nframes);
+void stf_feed_gone(stf_ctx* t);
+int feed_collect(ss_feed* f, ss_feed_result* out, stf_result* digest);
+
 void feed_free(ss_feed* f) {
   if (!f) return;
   for (auto& s : f->slots) {
@@ -3436,6 +3444,7 @@ void ss_feed_destroy(ss_feed* f) {
     (void)hipStreamSynchronize(f->copy_stream);
     (void)hipStreamSynchronize(f->c->stream);
     (void)hipStreamSynchronize(f->d2h_stream);
+    if (f->tracker) stf_feed_gone(f->tracker);
   }
   feed_free(f);
 }
@@ -3488,6 +3497,10 @@ int ss_feed_submit(ss_feed* f, int32_t nframes, const int64_t* t_ms, int64_t use
   flush_stages(c);  // the slot's results are copied out right behind the batch
   SS_HIP(c, hipMemcpyAsync(s.h_off, s.d_off, sizeof(int32_t) * ((size_t)nframes + 1), hipMemcpyDeviceToHost, c->stream));
   if (f->want_psd) SS_HIP(c, hipMemcpyAsync(s.h_psd, c->last_psd, sizeof(float) * (size_t)n * (size_t)nframes, hipMemcpyDeviceToHost, c->stream));
+  if (f->tracker) {  // the digest: behind the chain and the result copies, in front of ev_done; nothing in it waits on the host
+    st = stf_enqueue(f, f->acquired, nframes);
+    if (st != SS_OK) return st;
+  }
   SS_HIP(c, hipEventRecord(s.ev_done, c->stream));
   s.nframes = nframes;
   s.tag = user_tag;
@@ -3499,36 +3512,7 @@ int ss_feed_submit(ss_feed* f, int32_t nframes, const int64_t* t_ms, int64_t use
 
 int ss_feed_collect(ss_feed* f, ss_feed_result* out) {
   if (!f || !out) return SS_ERR_INVALID;
-  ss_ctx* c = f->c;
-  ss_feed_slot* s = nullptr;
-  {
-    std::lock_guard<std::mutex> lock(c->mtx);
-    if (f->pending == 0) return fail(c, SS_ERR_INVALID, "ss_feed_collect: nothing pending");
-    s = &f->slots[(size_t)f->next_collect];
-  }
-  // wait outside the lock: a producer thread may acquire / submit the next slots meanwhile
-  hipError_t e = hipEventSynchronize(s->ev_done);
-  std::lock_guard<std::mutex> lock(c->mtx);
-  if (e != hipSuccess) return fail(c, SS_ERR_HIP, "hipEventSynchronize failed: %s", hipGetErrorString(e));
-  SS_HIP(c, hipSetDevice(c->cfg.device_id));
-  const int total = s->h_off[s->nframes];
-  const int ncopy = total < f->cand_cap ? total : f->cand_cap;
-  if (ncopy > 0) {
-    SS_HIP(c, hipMemcpyAsync(s->h_idx, s->d_idx, sizeof(int32_t) * (size_t)ncopy, hipMemcpyDeviceToHost, f->d2h_stream));
-    SS_HIP(c, hipMemcpyAsync(s->h_avg, s->d_avg, sizeof(float) * (size_t)ncopy, hipMemcpyDeviceToHost, f->d2h_stream));
-    SS_HIP(c, hipStreamSynchronize(f->d2h_stream));
-  }
-  out->nframes = s->nframes;
-  out->status = (f->cand_cap > 0 && total > f->cand_cap) ? SS_ERR_CAND_OVERFLOW : SS_OK;
-  out->user_tag = s->tag;
-  out->cand_off = s->h_off;
-  out->cand_idx = s->h_idx;
-  out->cand_avg = s->h_avg;
-  out->psd_db = f->want_psd ? s->h_psd : nullptr;
-  s->state = 0;
-  f->next_collect = (f->next_collect + 1) % f->depth;
-  --f->pending;
-  return SS_OK;
+  return feed_collect(f, out, nullptr);
 }
 
 }  // extern "C"
@@ -3812,6 +3796,358 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
   out->peak_idx = t->h_pidx;
   out->peak_avg = t->h_pavg;
   out->d2h_bytes = d2h;
+  return SS_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The tracking digest behind the pipelined feed (include/specscan_track_feed.h, kernels: track_feed.h + track_digest.h): every batch
+// submitted through a tracked feed is digested on the context's stream right behind its chain; the watch list is formed on the
+// device from sequence-number marks, so no step waits for the host.
+//
+// Ordering against the next batch's chain, which may run on the library's own queues and rotates the PSD / avg / mask / offset
+// buffers (and raises the noise ceiling in place while it learns): the digest is on the context's stream, and whatever that stream
+// holds comes before a batch — an in-order call is on that stream itself, and an overlapped call's first launch waits for an event
+// recorded behind it (run_call_deep: "whatever the public stream holds ... comes first"; the want_psd copy of ss_feed_submit
+// rests on the same lines). ss_feed_submit has drained the deferred stages (flush_stages joins the queues into the stream) before
+// the digest is enqueued, so the digest in turn sees the whole batch.
+struct stf_slot {
+  int32_t *d_coff = nullptr, *d_best = nullptr, *d_watch = nullptr, *d_pidx = nullptr, *d_keys = nullptr;
+  float *d_cavg = nullptr, *d_pavg = nullptr;
+  ss::FeedDigestHeader* d_hdr = nullptr;
+  int32_t *h_best = nullptr, *h_watch = nullptr, *h_pidx = nullptr, *h_keys = nullptr;  // pinned
+  float *h_cavg = nullptr, *h_pavg = nullptr;
+  ss::FeedDigestHeader* h_hdr = nullptr;
+  uint64_t seq = 0, keys_seq = 0;
+};
+
+struct stf_ctx {
+  ss_ctx* scan = nullptr;
+  ss_feed* feed = nullptr;  // null once the feed has been destroyed: only stf_destroy / stf_last_error from then on
+  stf_config cfg{};
+  int nrows = 1, tail_rows = 0;  // as st_ctx
+  float* d_tail[2] = {};
+  int tail_cur = 0;
+  uint32_t *d_mark = nullptr, *d_keymark = nullptr;  // [n] each: sequence number of the newest batch that had the bin as cand_best / as a posted key
+  int32_t* d_counts = nullptr;                       // [ceil(n / 256)] block counts, then their prefix sums
+  int nblocks = 0;
+  std::vector<stf_slot> slots;
+  uint64_t next_seq = 1, collected = 0;  // the next batch's sequence number; the newest collected one
+  uint64_t post_seq = 0;                 // p and K_p as last posted
+  std::vector<int32_t> post_keys;
+  char err[512] = "";
+};
+
+namespace {
+
+thread_local char g_stf_create_err[512] = "";
+
+int stf_fail(stf_ctx* t, int status, const char* fmt, ...) {
+  char* dst = t ? t->err : g_stf_create_err;
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(dst, 512, fmt, ap);
+  va_end(ap);
+  return status;
+}
+
+void stf_free(stf_ctx* t) {
+  if (!t) return;
+  for (float* p : t->d_tail) (void)hipFree(p);
+  for (void* p : {(void*)t->d_mark, (void*)t->d_keymark, (void*)t->d_counts}) (void)hipFree(p);
+  for (auto& s : t->slots) {
+    for (void* p : {(void*)s.d_coff, (void*)s.d_best, (void*)s.d_watch, (void*)s.d_pidx, (void*)s.d_keys, (void*)s.d_cavg, (void*)s.d_pavg, (void*)s.d_hdr}) (void)hipFree(p);
+    for (void* p : {(void*)s.h_best, (void*)s.h_watch, (void*)s.h_pidx, (void*)s.h_keys, (void*)s.h_cavg, (void*)s.h_pavg, (void*)s.h_hdr}) (void)hipHostFree(p);
+  }
+  delete t;
+}
+
+size_t stf_tail_bytes(const stf_ctx* t) { return sizeof(float) * (size_t)std::max(1, t->tail_rows) * (size_t)t->scan->n; }
+
+// (under the context's lock) rows, marks and post back to zero, on the context's stream
+hipError_t stf_clear(stf_ctx* t) {
+  ss_ctx* c = t->scan;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMemsetAsync(t->d_tail[k], 0, stf_tail_bytes(t), c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_mark, 0, sizeof(uint32_t) * (size_t)c->n, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_keymark, 0, sizeof(uint32_t) * (size_t)c->n, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  t->next_seq = 1;
+  t->collected = 0;
+  t->post_seq = 0;
+  t->post_keys.clear();
+  return e;
+}
+
+void stf_feed_gone(stf_ctx* t) { t->feed = nullptr; }
+
+// ss_feed_submit, under the context's lock, behind flush_stages and the result copies: the digest of the batch just enqueued.
+int stf_enqueue(ss_feed* f, int slot_no, int nframes) {
+  stf_ctx* t = f->tracker;
+  ss_ctx* c = f->c;
+  ss_feed_slot& fs = f->slots[(size_t)slot_no];
+  stf_slot& s = t->slots[(size_t)slot_no];
+  const int n = c->n, G = c->cfg.grouping_y;
+  if (t->next_seq > 0xffffffffull) return fail(c, SS_ERR_INVALID, "tracked feed: 2^32 - 1 batches since stf_create / stf_reset (the device counts in 32 bits): stf_reset");
+  if (!c->last_avg || (c->fused && (!c->last_psd || !c->last_thr)) || (!c->fused && !c->d_rel))
+    return fail(c, SS_ERR_INVALID, "tracked feed: the batch left no dB plane, avg plane or noise ceiling to digest");
+  const uint32_t seq = (uint32_t)t->next_seq, p = (uint32_t)t->post_seq;
+  const int nkeys = (int)t->post_keys.size();
+  if (nkeys > 0) {
+    memcpy(s.h_keys, t->post_keys.data(), sizeof(int32_t) * (size_t)nkeys);
+    SS_HIP(c, hipMemcpyAsync(s.d_keys, s.h_keys, sizeof(int32_t) * (size_t)nkeys, hipMemcpyHostToDevice, c->stream));
+  }
+  ss::FeedPrepareArgs pa{};
+  pa.off = fs.d_off;
+  pa.coff = s.d_coff;
+  pa.keys = s.d_keys;
+  pa.keymark = t->d_keymark;
+  pa.hdr = s.d_hdr;
+  pa.nframes = nframes;
+  pa.cand_cap = f->cand_cap;
+  pa.nkeys = nkeys;
+  pa.seq = seq;
+  hipLaunchKernelGGL(ss::k_feed_prepare, dim3((unsigned)grid_for((size_t)std::max(nframes + 1, nkeys), 256)), dim3(256), 0, c->stream, pa);
+  ss::RelRows rows{};
+  rows.n = n;
+  rows.n_learn = c->last_n_learn;
+  rows.tail_rows = t->tail_rows;
+  rows.tail = t->d_tail[t->tail_cur];
+  if (c->fused) {
+    rows.psd = c->last_psd;
+    rows.thr = c->last_thr;
+  } else {
+    rows.rel = c->d_rel + (size_t)(G - 1) * n;
+  }
+  const int half = t->cfg.group_size / 2;
+  ss::CandBestArgs a{};
+  a.rows = rows;
+  a.avg = c->last_avg;
+  a.cand_off = s.d_coff;
+  a.cand_idx = fs.d_idx;
+  a.cand_best = s.d_best;
+  a.cand_avg = s.d_cavg;
+  a.nframes = nframes;
+  a.tiles = (n + ss::kTrackTile - 1) / ss::kTrackTile;
+  a.half = half;
+  a.nrows = t->nrows;
+  a.width = ss::kTrackTile + 2 * half;
+  a.start_level = t->cfg.start_level;
+  const size_t lds = sizeof(float) * (size_t)a.nrows * (size_t)a.width + sizeof(int) * (size_t)a.nrows * ss::kTrackTile;
+  hipLaunchKernelGGL(ss::k_cand_best, dim3((unsigned)((size_t)nframes * a.tiles)), dim3(ss::kTrackTile), lds, c->stream, a);
+  hipLaunchKernelGGL(ss::k_feed_stamp, dim3((unsigned)std::min(grid_for((size_t)f->cand_cap, 256), 1024)), dim3(256), 0, c->stream, (const int32_t*)s.d_coff, nframes,
+                     (const int32_t*)s.d_best, t->d_mark, n, seq, s.d_hdr);
+  hipLaunchKernelGGL(ss::k_feed_count, dim3((unsigned)t->nblocks), dim3(ss::kFeedBlock), 0, c->stream, (const uint32_t*)t->d_mark, (const uint32_t*)t->d_keymark, n, p, seq,
+                     t->d_counts);
+  hipLaunchKernelGGL(ss::k_feed_scan, dim3(1), dim3(64), 0, c->stream, t->d_counts, t->nblocks, (const int32_t*)fs.d_off, (const int32_t*)s.d_coff, nframes, t->cfg.max_watch,
+                     s.d_hdr);
+  hipLaunchKernelGGL(ss::k_feed_scatter, dim3((unsigned)t->nblocks), dim3(ss::kFeedBlock), 0, c->stream, (const uint32_t*)t->d_mark, (const uint32_t*)t->d_keymark, n, p, seq,
+                     (const int32_t*)t->d_counts, t->cfg.max_watch, s.d_watch);
+  ss::FeedPeaksArgs pk{};
+  pk.avg = c->last_avg;
+  pk.watch = s.d_watch;
+  pk.hdr = s.d_hdr;
+  pk.peak_idx = s.d_pidx;
+  pk.peak_avg = s.d_pavg;
+  pk.n = n;
+  pk.nframes = nframes;
+  pk.half = half;
+  // (the list's length is known to the device only: enough workgroups to fill the machine, each walks its share)
+  const size_t most = ((size_t)nframes * (size_t)t->cfg.max_watch + 3) / 4;
+  hipLaunchKernelGGL(ss::k_feed_peaks, dim3((unsigned)std::min<size_t>(most, 2048)), dim3(256), 0, c->stream, pk);
+  if (t->tail_rows > 0) {
+    const size_t total = (size_t)t->tail_rows * (size_t)n;
+    hipLaunchKernelGGL(ss::k_save_tail, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream, rows, nframes, t->d_tail[t->tail_cur ^ 1]);
+    t->tail_cur ^= 1;  // (stream order: the next batch's digest reads what this one wrote)
+  }
+  SS_HIP(c, hipGetLastError());
+  SS_HIP(c, hipMemcpyAsync(s.h_hdr, s.d_hdr, sizeof(ss::FeedDigestHeader), hipMemcpyDeviceToHost, c->stream));
+  s.seq = t->next_seq++;
+  s.keys_seq = t->post_seq;
+  return SS_OK;
+}
+
+// ss_feed_collect and stf_collect: the oldest pending batch, and — digest != nullptr — its digest, read back in exact sizes on the
+// feed's read-back stream next to the candidate lists.
+int feed_collect(ss_feed* f, ss_feed_result* out, stf_result* digest) {
+  ss_ctx* c = f->c;
+  ss_feed_slot* s = nullptr;
+  int slot_no = 0;
+  {
+    std::lock_guard<std::mutex> lock(c->mtx);
+    if (f->tracker && !digest) return fail(c, SS_ERR_INVALID, "ss_feed_collect on a tracked feed: collect through stf_collect");
+    if (f->pending == 0) return fail(c, SS_ERR_INVALID, "ss_feed_collect: nothing pending");
+    slot_no = f->next_collect;
+    s = &f->slots[(size_t)slot_no];
+  }
+  // wait outside the lock: a producer thread may acquire / submit the next slots meanwhile
+  hipError_t e = hipEventSynchronize(s->ev_done);
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (e != hipSuccess) return fail(c, SS_ERR_HIP, "hipEventSynchronize failed: %s", hipGetErrorString(e));
+  SS_HIP(c, hipSetDevice(c->cfg.device_id));
+  const int total = s->h_off[s->nframes];
+  const int ncopy = total < f->cand_cap ? total : f->cand_cap;
+  bool copies = false;
+  if (ncopy > 0) {
+    SS_HIP(c, hipMemcpyAsync(s->h_idx, s->d_idx, sizeof(int32_t) * (size_t)ncopy, hipMemcpyDeviceToHost, f->d2h_stream));
+    SS_HIP(c, hipMemcpyAsync(s->h_avg, s->d_avg, sizeof(float) * (size_t)ncopy, hipMemcpyDeviceToHost, f->d2h_stream));
+    copies = true;
+  }
+  if (digest) {
+    stf_ctx* t = f->tracker;
+    stf_slot& d = t->slots[(size_t)slot_no];
+    const ss::FeedDigestHeader h = *d.h_hdr;
+    if (h.ncand != ncopy || h.nwatch < 0 || (h.flags & ss::kFeedBadBest))
+      return fail(c, SS_ERR_HIP, "tracked feed: the digest's header does not fit the batch (ncand %d / %d, nwatch %d, flags %d)", h.ncand, ncopy, h.nwatch, h.flags);
+    const bool over = (h.flags & ss::kFeedOverflow) != 0 || h.nwatch > t->cfg.max_watch;
+    const size_t nw = over ? 0 : (size_t)h.nwatch, items = nw * (size_t)s->nframes;
+    if (ncopy > 0) {
+      SS_HIP(c, hipMemcpyAsync(d.h_best, d.d_best, sizeof(int32_t) * (size_t)ncopy, hipMemcpyDeviceToHost, f->d2h_stream));
+      SS_HIP(c, hipMemcpyAsync(d.h_cavg, d.d_cavg, sizeof(float) * (size_t)ncopy, hipMemcpyDeviceToHost, f->d2h_stream));
+    }
+    if (nw > 0) {
+      SS_HIP(c, hipMemcpyAsync(d.h_watch, d.d_watch, sizeof(int32_t) * nw, hipMemcpyDeviceToHost, f->d2h_stream));
+      SS_HIP(c, hipMemcpyAsync(d.h_pidx, d.d_pidx, sizeof(int32_t) * items, hipMemcpyDeviceToHost, f->d2h_stream));
+      SS_HIP(c, hipMemcpyAsync(d.h_pavg, d.d_pavg, sizeof(float) * items, hipMemcpyDeviceToHost, f->d2h_stream));
+      copies = true;
+    }
+    digest->seq = d.seq;
+    digest->keys_seq = d.keys_seq;
+    digest->status = over ? SS_ERR_INVALID : SS_OK;
+    digest->ncand = ncopy;
+    digest->nwatch = h.nwatch;
+    digest->cand_best = d.h_best;
+    digest->cand_avg = d.h_cavg;
+    digest->watch = d.h_watch;
+    digest->peak_idx = d.h_pidx;
+    digest->peak_avg = d.h_pavg;
+    digest->d2h_bytes = sizeof(ss::FeedDigestHeader) + 8ull * (uint64_t)ncopy + 4ull * nw + 8ull * items;
+    t->collected = d.seq;
+  }
+  if (copies) SS_HIP(c, hipStreamSynchronize(f->d2h_stream));
+  out->nframes = s->nframes;
+  out->status = (f->cand_cap > 0 && total > f->cand_cap) ? SS_ERR_CAND_OVERFLOW : SS_OK;
+  out->user_tag = s->tag;
+  out->cand_off = s->h_off;
+  out->cand_idx = s->h_idx;
+  out->cand_avg = s->h_avg;
+  out->psd_db = f->want_psd ? s->h_psd : nullptr;
+  s->state = 0;
+  f->next_collect = (f->next_collect + 1) % f->depth;
+  --f->pending;
+  return SS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int stf_create(ss_feed* f, const stf_config* cfg, stf_ctx** out) {
+  if (!f || !cfg || !out) return stf_fail(nullptr, SS_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (cfg->abi_version != STF_ABI_VERSION) return stf_fail(nullptr, SS_ERR_INVALID, "abi_version %u, library has %u", cfg->abi_version, STF_ABI_VERSION);
+  if (cfg->group_size < 0 || cfg->max_watch <= 0) return stf_fail(nullptr, SS_ERR_INVALID, "group_size >= 0 and max_watch > 0 required");
+  ss_ctx* c = f->c;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (!(c->cfg.flags & SS_FLAG_KEEP_PLANES)) return stf_fail(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_KEEP_PLANES (the digest reads the kept dB and avg planes)");
+  if (f->cand_cap <= 0) return stf_fail(nullptr, SS_ERR_INVALID, "the feed was created with cand_cap 0: there are no candidate lists to digest");
+  if (f->tracker) return stf_fail(nullptr, SS_ERR_INVALID, "the feed already has a tracker");
+  if (f->pending > 0 || f->acquired >= 0) return stf_fail(nullptr, SS_ERR_INVALID, "the feed has batches pending: collect them first");
+  const int nrows = (c->cfg.grouping_y + 1) / 2;
+  const size_t lds = sizeof(float) * (size_t)nrows * (size_t)(ss::kTrackTile + 2 * (cfg->group_size / 2)) + sizeof(int) * (size_t)nrows * ss::kTrackTile;
+  if (lds > 65536) return stf_fail(nullptr, SS_ERR_INVALID, "group_size %d with %d rows needs %zu bytes of LDS per tile (64 KiB at most)", cfg->group_size, nrows, lds);
+  stf_ctx* t = new (std::nothrow) stf_ctx();
+  if (!t) return stf_fail(nullptr, SS_ERR_NOMEM, "out of memory");
+  t->scan = c;
+  t->feed = f;
+  t->cfg = *cfg;
+  t->nrows = nrows;
+  t->tail_rows = nrows - 1;
+  t->nblocks = (c->n + ss::kFeedBlock - 1) / ss::kFeedBlock;
+  t->slots.resize((size_t)f->depth);
+  const size_t n = (size_t)c->n, frames = (size_t)c->cfg.max_batch, cap = (size_t)f->cand_cap, mw = (size_t)cfg->max_watch;
+  bool ok = hipSetDevice(c->cfg.device_id) == hipSuccess;
+  for (int k = 0; k < 2 && ok; ++k) ok = hipMalloc(&t->d_tail[k], stf_tail_bytes(t)) == hipSuccess;
+  ok = ok && hipMalloc(&t->d_mark, sizeof(uint32_t) * n) == hipSuccess && hipMalloc(&t->d_keymark, sizeof(uint32_t) * n) == hipSuccess;
+  ok = ok && hipMalloc(&t->d_counts, sizeof(int32_t) * (size_t)t->nblocks) == hipSuccess;
+  for (auto& s : t->slots) {
+    ok = ok && hipMalloc(&s.d_coff, sizeof(int32_t) * (frames + 1)) == hipSuccess && hipMalloc(&s.d_hdr, sizeof(ss::FeedDigestHeader)) == hipSuccess;
+    ok = ok && hipMalloc(&s.d_best, sizeof(int32_t) * cap) == hipSuccess && hipMalloc(&s.d_cavg, sizeof(float) * cap) == hipSuccess;
+    ok = ok && hipMalloc(&s.d_watch, sizeof(int32_t) * mw) == hipSuccess && hipMalloc(&s.d_keys, sizeof(int32_t) * mw) == hipSuccess;
+    ok = ok && hipMalloc(&s.d_pidx, sizeof(int32_t) * frames * mw) == hipSuccess && hipMalloc(&s.d_pavg, sizeof(float) * frames * mw) == hipSuccess;
+    ok = ok && hipHostMalloc(&s.h_hdr, sizeof(ss::FeedDigestHeader)) == hipSuccess;
+    ok = ok && hipHostMalloc(&s.h_best, sizeof(int32_t) * cap) == hipSuccess && hipHostMalloc(&s.h_cavg, sizeof(float) * cap) == hipSuccess;
+    ok = ok && hipHostMalloc(&s.h_watch, sizeof(int32_t) * mw) == hipSuccess && hipHostMalloc(&s.h_keys, sizeof(int32_t) * mw) == hipSuccess;
+    ok = ok && hipHostMalloc(&s.h_pidx, sizeof(int32_t) * frames * mw) == hipSuccess && hipHostMalloc(&s.h_pavg, sizeof(float) * frames * mw) == hipSuccess;
+  }
+  ok = ok && stf_clear(t) == hipSuccess;
+  if (!ok) {
+    const hipError_t e = hipGetLastError();
+    stf_free(t);
+    return stf_fail(nullptr, SS_ERR_NOMEM, "allocating the tracked feed's buffers failed: %s", hipGetErrorString(e));
+  }
+  f->tracker = t;
+  *out = t;
+  return SS_OK;
+}
+
+void stf_destroy(stf_ctx* t) {
+  if (!t) return;
+  {
+    std::lock_guard<std::mutex> lock(t->scan->mtx);
+    (void)hipSetDevice(t->scan->cfg.device_id);
+    if (t->feed) {  // (a destroyed feed has waited for its streams already)
+      (void)hipStreamSynchronize(t->scan->stream);
+      (void)hipStreamSynchronize(t->feed->d2h_stream);
+      t->feed->tracker = nullptr;
+    }
+  }
+  stf_free(t);
+}
+
+const char* stf_last_error(const stf_ctx* t) { return t ? t->err : g_stf_create_err; }
+
+int stf_post_keys(stf_ctx* t, uint64_t seq, const int32_t* keys, int32_t nkeys) {
+  if (!t) return SS_ERR_INVALID;
+  if (nkeys < 0 || (nkeys > 0 && !keys)) return stf_fail(t, SS_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(t->scan->mtx);
+  if (!t->feed) return stf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
+  if (seq > t->collected) return stf_fail(t, SS_ERR_INVALID, "keys after batch %llu, but the newest collected batch is %llu: not collected yet", (unsigned long long)seq, (unsigned long long)t->collected);
+  if (seq < t->post_seq) return stf_fail(t, SS_ERR_INVALID, "keys after batch %llu are older than the last post (%llu)", (unsigned long long)seq, (unsigned long long)t->post_seq);
+  if (nkeys > t->cfg.max_watch) return stf_fail(t, SS_ERR_INVALID, "%d keys > max_watch %d", nkeys, t->cfg.max_watch);
+  for (int k = 0; k < nkeys; ++k)
+    if (keys[k] < 0 || keys[k] >= t->scan->n) return stf_fail(t, SS_ERR_INVALID, "key %d: bin %d outside [0, %d)", k, keys[k], t->scan->n);
+  t->post_seq = seq;
+  t->post_keys.assign(keys, keys + nkeys);
+  return SS_OK;
+}
+
+int stf_collect(stf_ctx* t, stf_result* out) {
+  if (!t) return SS_ERR_INVALID;
+  if (!out) return stf_fail(t, SS_ERR_INVALID, "null argument");
+  ss_feed* f = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(t->scan->mtx);
+    f = t->feed;
+    if (!f) return stf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
+  }
+  const int st = feed_collect(f, &out->batch, out);
+  if (st != SS_OK) {
+    std::lock_guard<std::mutex> lock(t->scan->mtx);
+    return stf_fail(t, st, "%s", t->scan->err);
+  }
+  return SS_OK;
+}
+
+int stf_reset(stf_ctx* t) {
+  if (!t) return SS_ERR_INVALID;
+  ss_ctx* c = t->scan;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (!t->feed) return stf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
+  if (t->feed->pending > 0 || t->feed->acquired >= 0) return stf_fail(t, SS_ERR_INVALID, "stf_reset with batches pending: collect them first");
+  if (hipSetDevice(c->cfg.device_id) != hipSuccess || stf_clear(t) != hipSuccess) return stf_fail(t, SS_ERR_HIP, "clearing the kept rows and marks failed: %s", hipGetErrorString(hipGetLastError()));
+  t->tail_cur = 0;
   return SS_OK;
 }
 

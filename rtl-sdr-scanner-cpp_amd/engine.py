@@ -222,6 +222,13 @@ class Feed:
             self._lib.ss_feed_destroy(self._h)
             self._h = None
 
+    def track(self, group_size: int, start_level: float | None = None, max_watch: int = 1024):
+        """The tracking digest behind this feed (include/specscan_track_feed.h; the engine needs ``flags=SS_FLAG_KEEP_PLANES``): from now
+        on every submitted batch is digested in the stream, and the returned object's ``collect()`` — instead of this one's — delivers
+        the batch with its digest for ``tracker.SignalTracker.process_batch_digest``; ``post_keys(seq, keys)``, ``reset()``, ``close()``."""
+        from .tracker import TrackedFeed
+        return TrackedFeed(self, group_size, self._e.cfg.start_level if start_level is None else start_level, max_watch)
+
     def __del__(self):
         try:
             self.close()

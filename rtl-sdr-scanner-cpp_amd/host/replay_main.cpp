@@ -5,9 +5,15 @@
 // earlier batches cross PCIe and run. Optionally writes the raw PSD rows as the reference's DEBUG_SAVE_FULL_POWER
 // dump would (`..._power.raw`, sdr_device.cpp:173-176).
 //
-//   specscan_replay <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR]
+//   specscan_replay <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track [--bandwidth HZ]]
 // Prints one JSON line: frames, batches, candidates, seconds, MS/s (file + PCIe inclusive).
+//
+// --track: the feed is a tracked one (include/specscan_track_feed.h) — every batch is digested on the device behind its chain, and
+// the consumer thread owns a specscan::SignalTracker (host/signal_tracker.h): after each stf_collect it runs the batch's frames
+// through processFrameDigest (frame time 1000 * frame_index * N * D / fs ms, the stream's own clock) and posts its keys. The reader
+// thread is unchanged. The JSON line gains `transmissions` (entries of the per-frame lists, summed) and `tracked_frames`.
 #include <specscan.h>
+#include <specscan_track_feed.h>
 
 #include <chrono>
 #include <condition_variable>
@@ -17,14 +23,18 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <vector>
 
 #include "raw_file.h"
+#include "signal_tracker.h"
 
 namespace {
 
 struct Options {
   std::string path, power_dir;
   int fft = 0, decim = 0, batch = 1024, depth = 3, learn_frames = -1;
+  bool track = false;
+  int bandwidth = 32000;  // Config::recordingBandwidth: the tracker's windows are ceil(bandwidth / (fs / N)) bins wide
 };
 
 bool parse_args(int argc, char** argv, Options* o) {
@@ -45,6 +55,10 @@ bool parse_args(int argc, char** argv, Options* o) {
       if (!next(&o->depth)) return false;
     } else if (a == "--learn-frames") {
       if (!next(&o->learn_frames)) return false;
+    } else if (a == "--track") {
+      o->track = true;
+    } else if (a == "--bandwidth") {
+      if (!next(&o->bandwidth) || o->bandwidth <= 0) return false;
     } else if (a == "--power-dir") {
       if (i + 1 >= argc) return false;
       o->power_dir = argv[++i];
@@ -62,7 +76,7 @@ bool parse_args(int argc, char** argv, Options* o) {
 int main(int argc, char** argv) {
   Options opt;
   if (!parse_args(argc, argv, &opt)) {
-    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR]\n", argv[0]);
+    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track [--bandwidth HZ]]\n", argv[0]);
     return 2;
   }
   specscan::RawFileInfo info;
@@ -75,6 +89,7 @@ int main(int argc, char** argv) {
   if (opt.fft > 0) cfg.fft_size = opt.fft;
   if (opt.decim > 0) cfg.decim = opt.decim;
   if (opt.learn_frames >= 0) cfg.learn_frames = opt.learn_frames;
+  if (opt.track) cfg.flags |= SS_FLAG_KEEP_PLANES;  // the digest reads the kept dB and avg planes
   cfg.max_batch = opt.batch;
   if (info.kind == specscan::RawKind::CS8 || info.kind == specscan::RawKind::CU8) {
     cfg.in_format = info.kind == specscan::RawKind::CS8 ? SS_FMT_CS8 : SS_FMT_CU8;
@@ -94,6 +109,22 @@ int main(int argc, char** argv) {
     fprintf(stderr, "ss_feed_create: %s\n", ss_last_error(ctx));
     ss_destroy(ctx);
     return 1;
+  }
+  stf_ctx* tracked = nullptr;
+  specscan::TrackerConfig tc;
+  tc.fft_size = cfg.fft_size;
+  tc.sample_rate = info.sample_rate;
+  tc.start_level = cfg.start_level;
+  tc.grouping_y = cfg.grouping_y;
+  tc.group_size = (int)((((long long)opt.bandwidth * cfg.fft_size) + info.sample_rate - 1) / info.sample_rate);  // sdr_device.cpp:151
+  if (opt.track) {
+    stf_config tcfg{STF_ABI_VERSION, tc.group_size, cfg.start_level, 4096};
+    if (stf_create(feed, &tcfg, &tracked) != SS_OK) {
+      fprintf(stderr, "stf_create: %s\n", stf_last_error(nullptr));
+      ss_feed_destroy(feed);
+      ss_destroy(ctx);
+      return 1;
+    }
   }
   int rc = 0;
   try {
@@ -143,7 +174,9 @@ int main(int argc, char** argv) {
       }
     });
 
-    long long frames = 0, batches = 0, candidates = 0;
+    long long frames = 0, batches = 0, candidates = 0, transmissions = 0, tracked_frames = 0;
+    specscan::SignalTracker tracker(tc);
+    const auto frame_time_ms = [&](long long index) { return (int64_t)(1000ll * index * cfg.fft_size * cfg.decim / info.sample_rate); };
     for (;;) {
       {
         std::unique_lock<std::mutex> lock(mtx);
@@ -152,10 +185,31 @@ int main(int argc, char** argv) {
         --submitted;
       }
       ss_feed_result r;
-      if (ss_feed_collect(feed, &r) != SS_OK) {
+      stf_result d;
+      std::string why;
+      if (tracked) {
+        if (stf_collect(tracked, &d) != SS_OK) why = stf_last_error(tracked);
+        else if (d.status != SS_OK) why = "more watch keys than the tracked feed holds";
+        r = d.batch;
+        for (int f = 0; why.empty() && f < r.nframes; ++f) {
+          const int a = r.cand_off[f] < d.ncand ? r.cand_off[f] : d.ncand, b = r.cand_off[f + 1] < d.ncand ? r.cand_off[f + 1] : d.ncand;
+          const auto* tx = tracker.processFrameDigest(frame_time_ms(frames + f), r.cand_idx + a, d.cand_avg + a, d.cand_best + a, b - a, d.watch,
+                                                      d.nwatch, d.peak_idx + (size_t)f * d.nwatch, d.peak_avg + (size_t)f * d.nwatch);
+          if (!tx) why = "a tracked key is missing from the digest's watch list";
+          else transmissions += (long long)tx->size();
+        }
+        if (why.empty()) {
+          const std::vector<int> keys = tracker.signalKeys();
+          tracked_frames += r.nframes;
+          if (stf_post_keys(tracked, d.seq, keys.data(), (int32_t)keys.size()) != SS_OK) why = stf_last_error(tracked);
+        }
+      } else if (ss_feed_collect(feed, &r) != SS_OK) {
+        why = ss_last_error(ctx);
+      }
+      if (!why.empty()) {
         std::lock_guard<std::mutex> lock(mtx);
         failed = true;
-        error = ss_last_error(ctx);
+        error = why;
         cv.notify_all();
         break;
       }
@@ -184,14 +238,17 @@ int main(int argc, char** argv) {
       rc = 1;
     } else {
       printf("{\"file\": \"%s\", \"fft_size\": %d, \"decim\": %d, \"items_in_file\": %lld, \"frames\": %lld, \"batches\": %lld, "
-             "\"candidates\": %lld, \"seconds\": %.6f, \"msamples_per_sec\": %.1f}\n",
+             "\"candidates\": %lld, \"seconds\": %.6f, \"msamples_per_sec\": %.1f",
              opt.path.c_str(), cfg.fft_size, cfg.decim, (long long)reader.items(), frames, batches, candidates, seconds,
              seconds > 0 ? (double)frames * cfg.fft_size / seconds / 1e6 : 0.0);
+      if (tracked) printf(", \"transmissions\": %lld, \"tracked_frames\": %lld", transmissions, tracked_frames);
+      printf("}\n");
     }
   } catch (const std::exception& e) {
     fprintf(stderr, "%s\n", e.what());
     rc = 1;
   }
+  stf_destroy(tracked);
   ss_feed_destroy(feed);
   ss_destroy(ctx);
   return rc;

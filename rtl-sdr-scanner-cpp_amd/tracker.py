@@ -1,7 +1,7 @@
 """ctypes binding of host/libspecscan_host.so — the host-side signal tracker (host/signal_tracker.h), the part of
 the reference's Transmission block that turns per-frame candidates into the Scanner's (shift Hz, flush) list — and of the
 st_* entry points of libspecscan.so (include/specscan_track.h), the device-side digest that tracker can run on instead of
-the rel and avg planes."""
+the rel and avg planes — and of the stf_* entry points (include/specscan_track_feed.h), the same digest behind the pipelined feed."""
 from __future__ import annotations
 
 import ctypes as C
@@ -199,3 +199,109 @@ class TrackDigest:
                 "cand_best": take(r.cand_best, nc, np.int32), "cand_avg": take(r.cand_avg, nc, np.float32), "watch": take(r.watch, nw, np.int32),
                 "peak_idx": take(r.peak_idx, nf * nw, np.int32).reshape(nf, nw), "peak_avg": take(r.peak_avg, nf * nw, np.float32).reshape(nf, nw),
                 "d2h_bytes": int(r.d2h_bytes)}
+
+
+class StfConfig(C.Structure):  # stf_config, include/specscan_track_feed.h
+    _fields_ = [("abi_version", C.c_uint32), ("group_size", C.c_int32), ("start_level", C.c_float), ("max_watch", C.c_int32)]
+
+
+_stf_result = None
+
+
+def _stf_result_type():
+    """stf_result, defined once: every binding of the library and every TrackedFeed share the one ctypes class."""
+    global _stf_result
+    if _stf_result is not None:
+        return _stf_result
+    from .abi import SsFeedResult
+
+    class StfResult(C.Structure):  # stf_result
+        _fields_ = [("batch", SsFeedResult), ("seq", C.c_uint64), ("keys_seq", C.c_uint64), ("status", C.c_int32), ("ncand", C.c_int32), ("nwatch", C.c_int32),
+                    ("cand_best", c_int32_p), ("cand_avg", c_float_p), ("watch", c_int32_p), ("peak_idx", c_int32_p), ("peak_avg", c_float_p),
+                    ("d2h_bytes", C.c_uint64)]
+    _stf_result = StfResult
+    return StfResult
+
+
+STF_ABI_VERSION = 1
+STF_EXPORTS = ("stf_create", "stf_destroy", "stf_last_error", "stf_post_keys", "stf_collect", "stf_reset")
+
+
+def bind_track_feed(lib: C.CDLL):
+    result = _stf_result_type()
+    lib.stf_create.argtypes = [C.c_void_p, C.POINTER(StfConfig), C.POINTER(C.c_void_p)]
+    lib.stf_create.restype = C.c_int
+    lib.stf_destroy.argtypes = [C.c_void_p]
+    lib.stf_destroy.restype = None
+    lib.stf_last_error.argtypes = [C.c_void_p]
+    lib.stf_last_error.restype = C.c_char_p
+    lib.stf_post_keys.argtypes = [C.c_void_p, C.c_uint64, c_int32_p, C.c_int32]
+    lib.stf_post_keys.restype = C.c_int
+    lib.stf_collect.argtypes = [C.c_void_p, C.POINTER(result)]
+    lib.stf_collect.restype = C.c_int
+    lib.stf_reset.argtypes = [C.c_void_p]
+    lib.stf_reset.restype = C.c_int
+    return result
+
+
+class TrackedFeed:
+    """One stf_ctx bound to a Feed of an engine created with SS_FLAG_KEEP_PLANES (Feed.track): every batch submitted through the
+    feed is digested in the stream behind its chain. ``collect`` replaces the feed's own; ``post_keys(seq, tracker.keys)`` after
+    every collect keeps the watch lists short; ``reset`` goes with the engine's ``reset`` (feed drained first)."""
+
+    def __init__(self, feed, group_size: int, start_level: float = 8.0, max_watch: int = 1024):
+        from .abi import SpecscanError
+        self._err = SpecscanError
+        self._feed = feed  # (the feed and its engine must outlive the object; a feed closed first leaves it only close())
+        self._lib = feed._lib
+        self._result = bind_track_feed(self._lib)
+        cfg = StfConfig(STF_ABI_VERSION, int(group_size), float(start_level), int(max_watch))
+        h = C.c_void_p()
+        st = self._lib.stf_create(feed._h, C.byref(cfg), C.byref(h))
+        if st != 0:
+            raise SpecscanError(st, (self._lib.stf_last_error(None) or b"").decode())
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._feed._e, "_h", None):  # (an engine closed first took its stream and its lock with it)
+                self._lib.stf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        if st != 0:
+            raise self._err(st, (self._lib.stf_last_error(self._h) or b"").decode())
+
+    def reset(self):
+        self._check(self._lib.stf_reset(self._h))
+
+    def post_keys(self, seq: int, keys):
+        """The tracker's keys after it has processed batch ``seq`` (SignalTracker.keys): batches submitted from now on watch them."""
+        k = np.ascontiguousarray(keys, np.int32).reshape(-1)
+        self._check(self._lib.stf_post_keys(self._h, int(seq), k.ctypes.data_as(c_int32_p), k.size))
+
+    def collect(self) -> dict:
+        """The oldest pending batch with its digest, as numpy copies: the feed's nframes / status / tag (/ psd), seq, keys_seq,
+        digest_status (0, or SS_ERR_INVALID: more than max_watch watch keys — watch and peaks are empty then, nwatch is the true count)
+        and the arrays of ``TrackDigest.digest``: cand_off (clipped to the lists; cand_total is what the batch found), cand_idx, cand_best,
+        cand_avg (gathered from the avg plane; feed_cand_avg is the feed's own list), watch, peak_idx / peak_avg [nframes, nwatch]."""
+        r = self._result()
+        self._check(self._lib.stf_collect(self._h, C.byref(r)))
+        take = lambda p, count, dt: np.ctypeslib.as_array(p, shape=(count,)).astype(dt, copy=True) if count else np.zeros(0, dt)  # noqa: E731
+        nf, nc = r.batch.nframes, r.ncand
+        nw = r.nwatch if r.status == 0 else 0
+        off = take(r.batch.cand_off, nf + 1, np.int32)
+        out = {"nframes": nf, "status": r.batch.status, "tag": r.batch.user_tag, "seq": int(r.seq), "keys_seq": int(r.keys_seq), "digest_status": r.status,
+               "nwatch": r.nwatch, "cand_total": int(off[nf]), "cand_off": np.minimum(off, nc).astype(np.int32), "cand_idx": take(r.batch.cand_idx, nc, np.int32),
+               "feed_cand_avg": take(r.batch.cand_avg, nc, np.float32), "cand_best": take(r.cand_best, nc, np.int32), "cand_avg": take(r.cand_avg, nc, np.float32),
+               "watch": take(r.watch, nw, np.int32), "peak_idx": take(r.peak_idx, nf * nw, np.int32).reshape(nf, nw),
+               "peak_avg": take(r.peak_avg, nf * nw, np.float32).reshape(nf, nw), "d2h_bytes": int(r.d2h_bytes)}
+        if r.batch.psd_db:
+            out["psd"] = np.ctypeslib.as_array(r.batch.psd_db, shape=(nf, self._feed._e.n)).copy()
+        return out

@@ -1,15 +1,20 @@
-"""Transmissions per batch, two routes, one process, the same synthetic stream (synth.SyntheticBand):
+"""Transmissions per batch, three routes, one process, the same synthetic stream (synth.SyntheticBand):
 
   (a) planes:  ss_process with rel_db and avg_db, then sst_process_frame per frame          — what enableTracker does
   (b) digest:  ss_process without them (SS_FLAG_KEEP_PLANES), st_digest, then
                sst_process_frame_digest per frame                                           — what enableDeviceTracker does
+  (c) tracked feed: ss_feed_acquire / ss_feed_submit with an stf_ctx on the feed (depth 3), stf_collect of the
+               batch submitted two turns earlier, sst_process_frame_digest per frame, stf_post_keys — what specscan_replay --track does
 
 at 8192 points in 1024-frame batches and at 2^20 points in 16-frame batches. Wall clock around the whole batch (the call, the
 digest, the tracker's frames), median of --reps repetitions after a warm-up; both routes go through the C ABI with buffers allocated
-once, and the per-frame loop is the same Python loop in both. Prints one JSON line per shape. With --route b only route (b) runs:
-the form to put behind `rocprofv3 --kernel-trace --stats --` for the device times of k_cand_best and k_window_peaks.
+once, and the per-frame loop is the same Python loop in all. Route (c)'s turn is: fill a pinned slot, submit it, and — from the third
+turn on — collect, track and post the oldest batch, so its time per turn is its time per batch with two batches in flight (what it
+leaves in flight when its turn ends is a millisecond or two of device work that finishes while its own tracker loop still runs).
+Prints one JSON line per shape. With --route b (or c) only that route runs: the form to put behind
+`rocprofv3 --kernel-trace --stats --` for the device times of the digest's kernels.
 
-    python scripts/track_digest_rate.py [--reps 7] [--route ab|a|b] [--shapes 8192,1048576]
+    python scripts/track_digest_rate.py [--reps 7] [--route abc|ab|a|b|c] [--shapes 8192,1048576]
 """
 from __future__ import annotations
 
@@ -87,12 +92,68 @@ class Route:
         return time.perf_counter() - t0, seen
 
 
+class FeedRoute:
+    """Route (c): the tracked feed, two batches in flight."""
+
+    def __init__(self, n, fs, batch, g):
+        self.n, self.batch = n, batch
+        self.eng = pkg.SpectrumEngine(fs, 145_000_000, fft_size=n, decim=1, max_batch=batch, learn_ms=280, flags=abi.SS_FLAG_KEEP_PLANES)
+        self.trk = tracker.SignalTracker(n, fs, group_size=g, min_time_ms=200, timeout_ms=400)
+        self.feed = self.eng.feed(depth=3, cand_cap=batch * 1024)
+        self.stf = self.feed.track(g, max_watch=4096)
+        self.res = self.stf._result()
+        self.tx = np.empty(2 * n, np.int32)
+        self.sig = np.empty(n, np.int32)
+        self.nsig = C.c_int()
+        self.times = []  # t_ms of the batches in flight
+        self.d2h = 0
+        self.total = 0  # transmissions over every batch collected, warm-up included
+
+    def collect(self):
+        lib, hl, n = self.eng._lib, self.trk._lib, self.n
+        st = lib.stf_collect(self.stf._h, C.byref(self.res))
+        assert st == 0, (st, lib.stf_last_error(self.stf._h))
+        r, t = self.res, self.times.pop(0)
+        assert r.status == 0, r.nwatch
+        off = np.ctypeslib.as_array(r.batch.cand_off, shape=(r.batch.nframes + 1,)).tolist()
+        idx, best, cavg, pidx, pavg = (C.addressof(p.contents) if p else 0 for p in (r.batch.cand_idx, r.cand_best, r.cand_avg, r.peak_idx, r.peak_avg))
+        nw, nc, seen = r.nwatch, r.ncand, 0
+        self.d2h = int(r.d2h_bytes)
+        for f in range(r.batch.nframes):
+            a, b = min(off[f], nc), min(off[f + 1], nc)
+            seen += hl.sst_process_frame_digest(self.trk._h, int(t[f]), C.cast(idx + 4 * a, i32p), C.cast(cavg + 4 * a, f32p), C.cast(best + 4 * a, i32p), b - a,
+                                                r.watch, nw, C.cast(pidx + 4 * f * nw, i32p), C.cast(pavg + 4 * f * nw, f32p), at(self.tx, 0, i32p), n,
+                                                at(self.sig, 0, i32p), n, C.byref(self.nsig))
+        st = lib.stf_post_keys(self.stf._h, r.seq, at(self.sig, 0, i32p), self.nsig.value)
+        assert st == 0, (st, lib.stf_last_error(self.stf._h))
+        self.total += seen
+        return seen
+
+    def run(self, iq, t):
+        t0 = time.perf_counter()
+        buf = self.feed.acquire()
+        np.copyto(buf[:self.batch], iq)
+        self.feed.submit(self.batch, t_ms=t)
+        self.times.append(t)
+        seen = self.collect() if len(self.times) > 2 else 0
+        return time.perf_counter() - t0, seen
+
+    def drain(self):
+        seen = 0
+        while self.times:
+            seen += self.collect()
+        return seen
+
+
+LABELS = {"a": "planes", "b": "digest", "c": "feed"}
+
+
 def shape(n, batch, g, reps, routes, warm=3, distinct=4):
     fs = 2_048_000 if n == 8192 else n * 250
     band = pkg.synth.SyntheticBand(n, seed=0, on_frame=batch // 8 + 30, off_frame=5 * max(batch, 64) // 8 + 30, period=max(batch, 64) + 60)
     batches = [band.frames_cf32(batch) for _ in range(distinct)]
     out = {"fft_size": n, "batch": batch, "group_size": g, "reps": reps}
-    made = {name: Route(n, fs, batch, g, digest=name == "b") for name in routes}
+    made = {name: FeedRoute(n, fs, batch, g) if name == "c" else Route(n, fs, batch, g, digest=name == "b") for name in routes}
     times = {name: [] for name in routes}
     seen = {name: 0 for name in routes}
     for k in range(warm + reps):  # the routes alternate batch by batch: whatever else the host does meets both
@@ -103,14 +164,20 @@ def shape(n, batch, g, reps, routes, warm=3, distinct=4):
                 times[name].append(dt)
                 seen[name] += tx
     for name, route in made.items():
-        label = "planes" if name == "a" else "digest"
+        label = LABELS[name]
         out[f"{label}_ms_median"] = round(1e3 * statistics.median(times[name]), 3)
         out[f"{label}_ms_all"] = [round(1e3 * x, 3) for x in times[name]]
         out[f"{label}_transmissions"] = seen[name]
         if name == "b":
             out["digest_d2h_bytes_last"] = route.d2h
             out["planes_d2h_bytes"] = 8 * n * batch
-    if len(routes) == 2:
+    if "c" in made:  # (its transmissions lag two batches behind the other routes')
+        out["feed_d2h_bytes_last"] = made["c"].d2h
+        made["c"].drain()
+        out["feed_transmissions_warm_up_included"] = made["c"].total
+    if "b" in made and "c" in made:
+        out["feed_over_digest"] = round(out["feed_ms_median"] / out["digest_ms_median"], 4)
+    if "a" in made and "b" in made:
         out["same_transmission_count"] = seen["a"] == seen["b"]  # (tests/test_gpu_track_digest.py holds the two routes to each other frame by frame)
         out["digest_over_planes"] = round(out["digest_ms_median"] / out["planes_ms_median"], 4)
     print(json.dumps(out), flush=True)
@@ -119,7 +186,7 @@ def shape(n, batch, g, reps, routes, warm=3, distinct=4):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--route", default="ab", choices=("ab", "a", "b"))
+    ap.add_argument("--route", default="ab", choices=("abc", "ab", "a", "b", "c"))
     ap.add_argument("--shapes", default="8192,1048576")
     args = ap.parse_args()
     for n in (int(s) for s in args.shapes.split(",")):
