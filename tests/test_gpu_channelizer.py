@@ -5,7 +5,9 @@ What "parity" means here: the resampler cascade is compared sampl
 scale; summation order differs). The rotator of the reference is an fp32 recurrence whose phase creeps by a few 1e-8
 rad per sample relative to the rotation it stands for (tests/test_channelizer_oracle.py); the engine evaluates that
 rotation in closed form, so outputs are compared modulo a slow linear phase creep per slot, bounded at 1e-7 rad per
-input sample, and exactly (tight tolerance, int8 included) where the creep vanishes: shift 0, short runs."""
+input sample, and exactly (tight tolerance, int8 included) where the creep vanishes: shift 0, short runs.
+
+tests/test_gpu_channelizer_fp64.py holds every first-stage form to an fp64 model and to its own taps, with nothing fitted."""
 import numpy as np
 import pytest
 

@@ -14,6 +14,7 @@ import pytest
 import rtl_sdr_scanner_cpp_amd as pkg
 from rtl_sdr_scanner_cpp_amd import abi as A
 from rtl_sdr_scanner_cpp_amd.channelizer import Channelizer
+from chan_ref import first_stage
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -70,18 +71,6 @@ def _same(a, b, what):
             assert a[k][1].tobytes() == b[k][1].tobytes(), (what, k, "cf32", np.abs(a[k][1] - b[k][1]).max())
 
 
-def _form(stages):
-    """Which first-stage kernel a cascade takes (sc_create's rule): the polyphase-by-branch k_chan_dec<LOGG, PASSES> for
-    interpolation 1, decimation <= 128 and <= 33 taps per branch, else the generic k_chan_stage<true>."""
-    i, d, nt = stages[0]
-    if i != 1 or d > 128 or nt > 33 * d:
-        return "generic"
-    logg = 3
-    while (1 << logg) < d and logg < 6:
-        logg += 1
-    return f"<{logg},{2 if d > 64 else 1}>"
-
-
 CASES = [  # (fs, bw, stages (interp, decim), first-stage form)
     (2_048_000, 32_000, [(1, 64)], "<6,1>"),
     (2_048_000, 16_000, [(1, 8), (1, 16)], "<3,1>"),
@@ -101,7 +90,7 @@ def test_integer_input_is_bit_identical_to_cf32(fs, bw, stages, form, name):
     q = _ints(n, fs, name, seed=fs // 1000 + bw // 1000)
     x = _to_cf32(q, name)
     ci, cf = _pair(fs, bw, name, channels=4, max_samples=1 << 16)
-    assert [(i, d) for i, d, _ in ci.stages] == stages and _form(ci.stages) == form
+    assert [(i, d) for i, d, _ in ci.stages] == stages and first_stage(ci.stages).form == form
     for ch in (ci, cf):  # three active slots, slot 2 idle
         ch.start(0, int(fs / 7))
         ch.start(1, int(-fs / 5))
