@@ -60,8 +60,9 @@ typedef struct st_result {
 } st_result;
 
 /* Binds a digest object to a scan context (which must outlive it). SS_ERR_INVALID unless scan was created with
- * SS_FLAG_KEEP_PLANES, for a bad config, or when the rows of one 256-bin tile (ceil(grouping_y / 2) rows of
- * 256 + group_size bins) do not fit the 64 KiB of LDS a workgroup may use. Errors of st_create: st_last_error(NULL). */
+ * SS_FLAG_KEEP_PLANES, for a bad config, or when one rel row of a 256-bin tile with its tables (8 B for each of
+ * 256 + group_size bins) and the lanes' lists (1 KiB for each of ceil(grouping_y / 2) rows) do not fit the 64 KiB of LDS a
+ * workgroup may use: group_size up to about 6500 bins with grouping_y = 21. Errors of st_create: st_last_error(NULL). */
 int st_create(ss_ctx* scan, const st_config* cfg, st_ctx** out);
 void st_destroy(st_ctx* ctx);
 const char* st_last_error(const st_ctx* ctx);

@@ -77,7 +77,8 @@ typedef struct stf_result {
 
 /* From here on every batch submitted through feed is digested. SS_ERR_INVALID, with a message that names the reason
  * (stf_last_error(NULL)): the scan context was created without SS_FLAG_KEEP_PLANES; the feed has cand_cap 0, has batches
- * pending or has a tracker already; max_watch <= 0; the rows of one 256-bin tile do not fit 64 KiB of LDS (as st_create). */
+ * pending or has a tracker already; max_watch <= 0; one rel row of a 256-bin tile with its tables does not fit 64 KiB of
+ * LDS (as st_create: group_size up to about 6500 bins with grouping_y = 21). */
 int stf_create(ss_feed* feed, const stf_config* cfg, stf_ctx** out);
 void stf_destroy(stf_ctx* ctx);
 const char* stf_last_error(const stf_ctx* ctx); /* NULL: the last stf_create failure of this thread */

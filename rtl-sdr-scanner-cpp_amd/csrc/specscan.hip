@@ -34,6 +34,7 @@
 #include "ring_place.h"
 #include "scan_step.h"
 #include "track_digest.h"
+#include "track_digest_blocked.h"
 #include "track_feed.h"
 
 namespace {
@@ -3518,11 +3519,46 @@ int ss_feed_collect(ss_feed* f, ss_feed_result* out) {
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// The tracking digest (include/specscan_track.h, kernels: track_digest.h): what the host-side signal tracker reads of the last
+// The tracking digest (include/specscan_track.h, kernels: track_digest.h, track_digest_blocked.h): what the host-side signal tracker reads of the last
 // batch's rel and avg planes, computed next to them.
+namespace {
+
+// The candidates' kernel of st_digest and of the tracked feed: the blocked sliding arg-max (track_digest_blocked.h). The walk of
+// track_digest.h, which stages every row at once and so stops near 977 bins, is kept for A/B runs: a build with -DSS_DIAG takes it
+// when SS_CAND_BEST=walk is set at st_create / stf_create.
+bool cand_best_walk() {
+#ifdef SS_DIAG
+  const char* v = getenv("SS_CAND_BEST");
+  return v && strcmp(v, "walk") == 0;
+#else
+  return false;
+#endif
+}
+
+size_t cand_best_lds(int nrows, int group_size, bool walk) {
+  const int half = group_size / 2;
+  if (walk) return sizeof(float) * (size_t)nrows * (size_t)(ss::kTrackTile + 2 * half) + sizeof(int) * (size_t)nrows * ss::kTrackTile;
+  return ss::blocked_lds_bytes(nrows, half);
+}
+
+// a.tiles, a.half, a.nrows and a.width follow from n, group_size and nrows here
+void launch_cand_best(ss::CandBestArgs a, int n, int group_size, int nrows, bool walk, hipStream_t stream) {
+  a.tiles = (n + ss::kTrackTile - 1) / ss::kTrackTile;
+  a.half = group_size / 2;
+  a.nrows = nrows;
+  a.width = ss::kTrackTile + 2 * a.half;
+  const dim3 grid((unsigned)((size_t)a.nframes * a.tiles));
+  const size_t lds = cand_best_lds(nrows, group_size, walk);
+  if (walk) hipLaunchKernelGGL(ss::k_cand_best, grid, dim3(ss::kTrackTile), lds, stream, a);
+  else hipLaunchKernelGGL(ss::k_best_blocked, grid, dim3(ss::kTrackTile), lds, stream, a);
+}
+
+}  // namespace
+
 struct st_ctx {
   ss_ctx* scan = nullptr;
   st_config cfg{};
+  bool walk = false;  // cand_best_walk() at st_create
   int nrows = 1;      // ceil(grouping_y / 2): the rel rows getBestIndex looks at
   int tail_rows = 0;  // nrows - 1: how many of them can lie before a batch
   float* d_tail[2] = {};  // [tail_rows][n] each; [tail_cur] holds the rows before the next batch, the other one is written by the digest
@@ -3615,12 +3651,14 @@ int st_create(ss_ctx* scan, const st_config* cfg, st_ctx** out) {
   std::lock_guard<std::mutex> lock(scan->mtx);
   if (!(scan->cfg.flags & SS_FLAG_KEEP_PLANES)) return st_fail(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_KEEP_PLANES (the digest reads the kept dB and avg planes)");
   const int nrows = (scan->cfg.grouping_y + 1) / 2;
-  const size_t lds = sizeof(float) * (size_t)nrows * (size_t)(ss::kTrackTile + 2 * (cfg->group_size / 2)) + sizeof(int) * (size_t)nrows * ss::kTrackTile;
+  const bool walk = cand_best_walk();
+  const size_t lds = cand_best_lds(nrows, cfg->group_size, walk);
   if (lds > 65536) return st_fail(nullptr, SS_ERR_INVALID, "group_size %d with %d rows needs %zu bytes of LDS per tile (64 KiB at most)", cfg->group_size, nrows, lds);
   st_ctx* t = new (std::nothrow) st_ctx();
   if (!t) return st_fail(nullptr, SS_ERR_NOMEM, "out of memory");
   t->scan = scan;
   t->cfg = *cfg;
+  t->walk = walk;
   t->nrows = nrows;
   t->tail_rows = nrows - 1;
   t->seen_batch = scan->batch_no;
@@ -3725,13 +3763,8 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
     a.cand_best = t->d_best;
     a.cand_avg = t->d_cavg;
     a.nframes = nframes;
-    a.tiles = (n + ss::kTrackTile - 1) / ss::kTrackTile;
-    a.half = half;
-    a.nrows = t->nrows;
-    a.width = ss::kTrackTile + 2 * half;
     a.start_level = t->cfg.start_level;
-    const size_t lds = sizeof(float) * (size_t)a.nrows * (size_t)a.width + sizeof(int) * (size_t)a.nrows * ss::kTrackTile;
-    hipLaunchKernelGGL(ss::k_cand_best, dim3((unsigned)((size_t)nframes * a.tiles)), dim3(ss::kTrackTile), lds, c->stream, a);
+    launch_cand_best(a, n, t->cfg.group_size, t->nrows, t->walk, c->stream);
     ST_HIP(t, hipGetLastError());
     ST_HIP(t, hipMemcpyAsync(t->h_best, t->d_best, sizeof(int32_t) * (size_t)ncand, hipMemcpyDeviceToHost, c->stream));
     ST_HIP(t, hipMemcpyAsync(t->h_cavg, t->d_cavg, sizeof(float) * (size_t)ncand, hipMemcpyDeviceToHost, c->stream));
@@ -3755,7 +3788,7 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
       w.push_back(b);
       t->mark[(size_t)b] = 0;
     }
-  if (!sane) return st_fail(t, SS_ERR_HIP, "k_cand_best returned a bin outside [0, %d)", n);
+  if (!sane) return st_fail(t, SS_ERR_HIP, "the candidates' kernel returned a bin outside [0, %d)", n);
   const int nwatch = (int)w.size();
   if (nwatch > t->cfg.max_watch) return st_fail(t, SS_ERR_INVALID, "%d watch keys > max_watch %d", nwatch, t->cfg.max_watch);
   if (nwatch > 0) {
@@ -3826,6 +3859,7 @@ struct stf_ctx {
   ss_ctx* scan = nullptr;
   ss_feed* feed = nullptr;  // null once the feed has been destroyed: only stf_destroy / stf_last_error from then on
   stf_config cfg{};
+  bool walk = false;             // as st_ctx
   int nrows = 1, tail_rows = 0;  // as st_ctx
   float* d_tail[2] = {};
   int tail_cur = 0;
@@ -3929,13 +3963,8 @@ int stf_enqueue(ss_feed* f, int slot_no, int nframes) {
   a.cand_best = s.d_best;
   a.cand_avg = s.d_cavg;
   a.nframes = nframes;
-  a.tiles = (n + ss::kTrackTile - 1) / ss::kTrackTile;
-  a.half = half;
-  a.nrows = t->nrows;
-  a.width = ss::kTrackTile + 2 * half;
   a.start_level = t->cfg.start_level;
-  const size_t lds = sizeof(float) * (size_t)a.nrows * (size_t)a.width + sizeof(int) * (size_t)a.nrows * ss::kTrackTile;
-  hipLaunchKernelGGL(ss::k_cand_best, dim3((unsigned)((size_t)nframes * a.tiles)), dim3(ss::kTrackTile), lds, c->stream, a);
+  launch_cand_best(a, n, t->cfg.group_size, t->nrows, t->walk, c->stream);
   hipLaunchKernelGGL(ss::k_feed_stamp, dim3((unsigned)std::min(grid_for((size_t)f->cand_cap, 256), 1024)), dim3(256), 0, c->stream, (const int32_t*)s.d_coff, nframes,
                      (const int32_t*)s.d_best, t->d_mark, n, seq, s.d_hdr);
   hipLaunchKernelGGL(ss::k_feed_count, dim3((unsigned)t->nblocks), dim3(ss::kFeedBlock), 0, c->stream, (const uint32_t*)t->d_mark, (const uint32_t*)t->d_keymark, n, p, seq,
@@ -4055,13 +4084,15 @@ int stf_create(ss_feed* f, const stf_config* cfg, stf_ctx** out) {
   if (f->tracker) return stf_fail(nullptr, SS_ERR_INVALID, "the feed already has a tracker");
   if (f->pending > 0 || f->acquired >= 0) return stf_fail(nullptr, SS_ERR_INVALID, "the feed has batches pending: collect them first");
   const int nrows = (c->cfg.grouping_y + 1) / 2;
-  const size_t lds = sizeof(float) * (size_t)nrows * (size_t)(ss::kTrackTile + 2 * (cfg->group_size / 2)) + sizeof(int) * (size_t)nrows * ss::kTrackTile;
+  const bool walk = cand_best_walk();
+  const size_t lds = cand_best_lds(nrows, cfg->group_size, walk);
   if (lds > 65536) return stf_fail(nullptr, SS_ERR_INVALID, "group_size %d with %d rows needs %zu bytes of LDS per tile (64 KiB at most)", cfg->group_size, nrows, lds);
   stf_ctx* t = new (std::nothrow) stf_ctx();
   if (!t) return stf_fail(nullptr, SS_ERR_NOMEM, "out of memory");
   t->scan = c;
   t->feed = f;
   t->cfg = *cfg;
+  t->walk = walk;
   t->nrows = nrows;
   t->tail_rows = nrows - 1;
   t->nblocks = (c->n + ss::kFeedBlock - 1) / ss::kFeedBlock;

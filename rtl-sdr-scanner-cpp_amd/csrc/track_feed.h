@@ -1,6 +1,7 @@
 // track_feed.h — the tracking digest behind the pipelined feed (include/specscan_track_feed.h): the steps of st_digest that ran on the
 // host — clipping the offsets, forming the watch list — as kernels, so that a batch is digested in the stream right behind its chain,
-// with no host wait in between. k_cand_best and k_save_tail of track_digest.h run unchanged between them.
+// with no host wait in between. The candidates' kernel (k_best_blocked of
+// track_digest_blocked.h; launch_cand_best in specscan.hip) and k_save_tail of track_digest.h run unchanged between them.
 //
 //   k_feed_prepare   coff[f] = min(off[f], cand_cap); keymark[key] = seq for the posted keys; the header's flags to zero
 //   k_feed_stamp     mark[cand_best[j]] = seq for every candidate of the clipped lists

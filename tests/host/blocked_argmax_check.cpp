@@ -1,0 +1,181 @@
+// The blocked sliding arg-max of csrc/track_digest_blocked.h on the host: the header's own table build and query (plain functions over a
+// row pointer), with the 256 lanes of k_best_blocked played by loops — chunked local scans, the segmented scan over the chunks in the
+// kernel's order (six shuffle steps inside each wave of 64, the four waves' totals, the neighbour's inclusive result as the exclusive
+// one), the fix-ups — against std::max_element written out. The staged span is copied into vectors of exactly its length, so that
+// the address sanitizer sees any access outside it. Also: the tables against their definitions, and the join operators' associativity.
+// Plain C++ (g++ -fsanitize=address,undefined), no HIP. Prints "... bad 0" when everything holds.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <random>
+#include <vector>
+
+#include "../../rtl-sdr-scanner-cpp_amd/csrc/track_digest_blocked.h"
+
+using ss::Best;
+using ss::SegBest;
+
+static long long g_bad = 0, g_windows = 0, g_tables = 0;
+
+static int argmax_literal(const float* row, int lo, int hi) {
+  int best = lo;
+  for (int i = lo + 1; i < hi; ++i)
+    if (row[best] < row[i]) best = i;
+  return best;
+}
+
+// the first maximum of the bins [a, b] with NaNs left out, as an offset from base, or none
+static uint32_t first_max(const float* full, int a, int b, int base) {
+  uint32_t best = ss::kBestNone;
+  for (int i = a; i <= b; ++i)
+    if (full[i] == full[i] && (best == ss::kBestNone || full[i] > full[base + (int)best])) best = (uint32_t)(i - base);
+  return best;
+}
+
+static void fail(const char* what, int n, int half, int t0, int at, long long got, long long want) {
+  if (g_bad++ < 20) printf("MISMATCH %s: n %d half %d tile %d at %d: got %lld want %lld\n", what, n, half, t0, at, got, want);
+}
+
+// one workgroup of k_best_blocked on one row: tile [t0, t0 + 256) of a row of n bins
+static void run_tile(const std::vector<float>& full, int half, int t0, bool check_tables) {
+  const int n = (int)full.size(), L = ss::kBlockedLanes;
+  const int s_lo = t0 - half < 0 ? 0 : t0 - half;
+  const int s_hi = t0 + L - 1 + half < n ? t0 + L - 1 + half : n - 1;
+  const int len = s_hi - s_lo + 1, W = 2 * half + 1;
+  std::vector<float> row(full.begin() + s_lo, full.begin() + s_hi + 1);
+  std::vector<uint16_t> P((size_t)len, 0xdead), S((size_t)len, 0xdead);
+  std::vector<int> c0((size_t)L), c1((size_t)L), rem0((size_t)L), rem1((size_t)L);
+  std::vector<SegBest> p((size_t)L), s((size_t)L);
+  for (int t = 0; t < L; ++t) {
+    ss::blocked_chunk(t, len, c0[t], c1[t]);
+    rem0[t] = c0[t] < c1[t] ? (s_lo + c0[t]) % W : 0;
+    rem1[t] = c0[t] < c1[t] ? (s_lo + c1[t] - 1) % W : 0;
+    p[t] = ss::blocked_prefix_local(row.data(), P.data(), W, rem0[t], c0[t], c1[t]);
+    s[t] = ss::blocked_suffix_local(row.data(), S.data(), W, rem1[t], c0[t], c1[t]);
+  }
+  for (int d = 1; d < 64; d <<= 1) {  // every lane reads its partner's value of the step before
+    const std::vector<SegBest> po = p, so = s;
+    for (int t = 0; t < L; ++t) {
+      const int lane = t & 63;
+      if (lane >= d) p[t] = ss::seg_join_fwd(po[t - d], po[t]);
+      if (lane + d < 64) s[t] = ss::seg_join_bwd(so[t], so[t + d]);
+    }
+  }
+  SegBest tot_p[4], tot_s[4];
+  for (int w = 0; w < 4; ++w) {
+    tot_p[w] = p[w * 64 + 63];
+    tot_s[w] = s[w * 64];
+  }
+  for (int t = 0; t < L; ++t) {
+    const int lane = t & 63, wave = t >> 6;
+    SegBest before = lane == 0 ? ss::seg_none() : p[t - 1], behind = lane == 63 ? ss::seg_none() : s[t + 1];
+    SegBest carry = ss::seg_none();
+    for (int w = 0; w < wave; ++w) carry = ss::seg_join_fwd(carry, tot_p[w]);
+    before = ss::seg_join_fwd(carry, before);
+    carry = ss::seg_none();
+    for (int w = 3; w > wave; --w) carry = ss::seg_join_bwd(tot_s[w], carry);
+    behind = ss::seg_join_bwd(behind, carry);
+    ss::blocked_prefix_fix(row.data(), P.data(), W, rem0[t], c0[t], c1[t], before.b);
+    ss::blocked_suffix_fix(row.data(), S.data(), W, rem1[t], c0[t], c1[t], behind.b);
+  }
+  if (check_tables) {
+    for (int i = s_lo; i <= s_hi; ++i) {
+      const int bs = i - i % W, be = bs + W - 1;
+      const uint32_t wp = first_max(full.data(), bs > s_lo ? bs : s_lo, i, s_lo), ws = first_max(full.data(), i, be < s_hi ? be : s_hi, s_lo);
+      if (P[(size_t)(i - s_lo)] != wp) fail("P", n, half, t0, i, P[(size_t)(i - s_lo)], wp);
+      if (S[(size_t)(i - s_lo)] != ws) fail("S", n, half, t0, i, S[(size_t)(i - s_lo)], ws);
+      g_tables += 2;
+    }
+  }
+  for (int c = t0; c < t0 + L && c < n; ++c) {
+    const int lo = c - half < 0 ? 0 : c - half, hi = c + half + 1 < n ? c + half + 1 : n;
+    const int got = ss::blocked_query(row.data(), P.data(), S.data(), s_lo, W, lo % W, lo, hi);
+    const int want = argmax_literal(full.data(), lo, hi);
+    if (got != want) fail("window", n, half, t0, c, got, want);
+    ++g_windows;
+  }
+}
+
+static std::vector<float> make_row(int kind, int n, int W, std::mt19937& rng) {
+  const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+  std::vector<float> r((size_t)n);
+  std::uniform_int_distribution<int> ties(-3, 3);
+  std::uniform_real_distribution<float> u(0.0f, 1.0f);
+  std::normal_distribution<float> gauss(0.0f, 5.0f);
+  for (int i = 0; i < n; ++i) r[(size_t)i] = (float)ties(rng);  // many ties, across block edges too
+  switch (kind) {
+    case 0: break;
+    case 1: for (auto& v : r) v = -100.0f; break;                                          // a learning frame: all ties
+    case 2: for (auto& v : r) { if (u(rng) < 0.5f) v = -inf; if (u(rng) < 0.1f) v = nan; } break;  // -inf runs with NaNs
+    case 3: for (auto& v : r) if (u(rng) < 0.25f) v = nan; break;
+    case 4: for (int i = 0; i < n; i += W) r[(size_t)i] = nan; break;                       // NaN at every block start
+    case 5: for (int i = W - 1; i < n; i += W) r[(size_t)i] = nan; r[(size_t)n - 1] = nan; break;  // ... at every block end, the clipped one too
+    case 6: for (auto& v : r) v = nan; break;
+    case 7: for (auto& v : r) v = gauss(rng); break;
+    case 8: for (auto& v : r) v = -inf; break;
+    case 9: for (int i = 0; i < n; ++i) r[(size_t)i] = (float)(i / (W > 1 ? W - 1 : 1) % 3); break;  // plateaus that straddle the block edges
+    default: for (int i = 0; i < n; ++i) if (i % 7 == 3 || i % W == W / 2) r[(size_t)i] = nan; break;  // NaN at lo of many windows
+  }
+  return r;
+}
+
+static bool same(SegBest a, SegBest b) {
+  if (a.head != b.head || a.b.i != b.b.i) return false;
+  return a.b.i == ss::kBestNone || std::memcmp(&a.b.v, &b.b.v, sizeof(float)) == 0;
+}
+
+static void check_associativity(std::mt19937& rng) {
+  const float inf = std::numeric_limits<float>::infinity();
+  const float values[] = {-inf, -100.0f, -1.0f, 0.0f, 0.0f, 1.0f, 1.0f, inf};
+  std::uniform_int_distribution<int> pick(0, 7), coin(0, 3);
+  for (int trial = 0; trial < 200000; ++trial) {
+    SegBest x[3];
+    for (int k = 0; k < 3; ++k) {  // three adjacent ranges: offsets ascending
+      x[k].b.v = values[pick(rng)];
+      x[k].b.i = coin(rng) == 0 ? ss::kBestNone : (uint32_t)(10 * k + coin(rng));
+      x[k].head = coin(rng) == 0;
+    }
+    const Best l = ss::best_join(ss::best_join(x[0].b, x[1].b), x[2].b), r = ss::best_join(x[0].b, ss::best_join(x[1].b, x[2].b));
+    if (!same(SegBest{l, false}, SegBest{r, false})) fail("best_join associativity", 0, 0, 0, trial, l.i, r.i);
+    if (!same(ss::seg_join_fwd(ss::seg_join_fwd(x[0], x[1]), x[2]), ss::seg_join_fwd(x[0], ss::seg_join_fwd(x[1], x[2])))) fail("seg_join_fwd associativity", 0, 0, 0, trial, 0, 0);
+    if (!same(ss::seg_join_bwd(ss::seg_join_bwd(x[0], x[1]), x[2]), ss::seg_join_bwd(x[0], ss::seg_join_bwd(x[1], x[2])))) fail("seg_join_bwd associativity", 0, 0, 0, trial, 0, 0);
+    for (int k = 0; k < 3; ++k)  // none is the identity on both sides
+      if (!same(ss::seg_join_fwd(ss::seg_none(), x[k]), x[k]) || !same(ss::seg_join_fwd(x[k], ss::seg_none()), x[k]) ||
+          !same(ss::seg_join_bwd(ss::seg_none(), x[k]), x[k]) || !same(ss::seg_join_bwd(x[k], ss::seg_none()), x[k]))
+        fail("identity", 0, 0, 0, trial, 0, 0);
+  }
+}
+
+int main() {
+  std::mt19937 rng(20240611);
+  check_associativity(rng);
+  const int halves[] = {0, 1, 2, 20, 64, 65, 127, 128, 300, 550, 2048};
+  for (int half : halves) {
+    const int W = 2 * half + 1;
+    // n < W, n = W, n = W + 1 (both clips, the one-bin last block), rows of several tiles with a clipped last block and with a whole one
+    std::vector<int> sizes = {W, W + 1, 3 * W, 256, 300, 2 * 256 + W + 17, 5 * 256, 4 * 256 + 255};
+    if (W > 1) sizes.push_back(W - 1);
+    if (W > 2) sizes.push_back(W / 2 + 1);
+    const bool wide = half >= 550;
+    for (int n : sizes) {
+      const int tiles = (n + 255) / 256;
+      std::vector<int> which = {0, tiles / 2, tiles - 1};  // the row's start, middle and end
+      if (!wide)
+        for (int t = 1; t < tiles - 1; ++t) which.push_back(t);
+      for (int kind = 0; kind <= 10; ++kind) {
+        if (wide && (kind == 8 || kind == 6) && n > 3 * 256) continue;  // (the literal walk of 4097-bin windows is the cost here)
+        const std::vector<float> row = make_row(kind, n, W, rng);
+        int prev = -1;
+        for (int t : which) {
+          if (t == prev) continue;
+          prev = t;
+          run_tile(row, half, t * 256, !wide);
+        }
+      }
+    }
+  }
+  printf("windows %lld table entries %lld bad %lld\n", g_windows, g_tables, g_bad);
+  return g_bad == 0 ? 0 : 1;
+}
