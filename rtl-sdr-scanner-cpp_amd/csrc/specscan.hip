@@ -568,13 +568,18 @@ struct ss_ctx {
 
 namespace {
 
-int fail(ss_ctx* c, int status, const char* fmt, ...) {
-  char* dst = c ? c->err : g_create_err;
+// every context keeps its last error in 512 bytes, and a create call that has no context yet in a thread-local twin
+int fail_to(char* dst, int status, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(dst, 512, fmt, ap);
   va_end(ap);
   return status;
+}
+
+template <class... A>
+int fail(ss_ctx* c, int status, const char* fmt, A... a) {
+  return fail_to(c ? c->err : g_create_err, status, fmt, a...);
 }
 
 #define SS_HIP(ctx, call)                                                                              \
@@ -3523,34 +3528,90 @@ int ss_feed_collect(ss_feed* f, ss_feed_result* out) {
 // batch's rel and avg planes, computed next to them.
 namespace {
 
-// The candidates' kernel of st_digest and of the tracked feed: the blocked sliding arg-max (track_digest_blocked.h). The walk of
-// track_digest.h, which stages every row at once and so stops near 977 bins, is kept for A/B runs: a build with -DSS_DIAG takes it
-// when SS_CAND_BEST=walk is set at st_create / stf_create.
-bool cand_best_walk() {
-#ifdef SS_DIAG
-  const char* v = getenv("SS_CAND_BEST");
-  return v && strcmp(v, "walk") == 0;
-#else
-  return false;
-#endif
+// What st_ctx and stf_ctx share: the rel rows getBestIndex looks at, and the ones among them that lie before a batch.
+struct digest_rows {
+  int group_size = 0;
+  float start_level = 0.0f;
+  int nrows = 1;      // ceil(grouping_y / 2): the rel rows getBestIndex looks at
+  int tail_rows = 0;  // nrows - 1: how many of them can lie before a batch
+  float* d_tail[2] = {};  // [tail_rows][n] each; [tail_cur] holds the rows before the next batch, the other one is written by the digest
+  int tail_cur = 0;
+};
+
+// create time: the row count, and whether a tile of the candidates' kernel (track_digest_blocked.h) fits LDS; the message goes to err
+int digest_rows_plan(digest_rows& r, const ss_ctx* scan, int group_size, float start_level, char* err) {
+  r.group_size = group_size;
+  r.start_level = start_level;
+  r.nrows = (scan->cfg.grouping_y + 1) / 2;
+  r.tail_rows = r.nrows - 1;
+  const size_t lds = ss::blocked_lds_bytes(r.nrows, group_size / 2);
+  if (lds > 65536) return fail_to(err, SS_ERR_INVALID, "group_size %d with %d rows needs %zu bytes of LDS per tile (64 KiB at most)", group_size, r.nrows, lds);
+  return SS_OK;
 }
 
-size_t cand_best_lds(int nrows, int group_size, bool walk) {
-  const int half = group_size / 2;
-  if (walk) return sizeof(float) * (size_t)nrows * (size_t)(ss::kTrackTile + 2 * half) + sizeof(int) * (size_t)nrows * ss::kTrackTile;
-  return ss::blocked_lds_bytes(nrows, half);
+size_t tail_bytes(const digest_rows& r, const ss_ctx* scan) { return sizeof(float) * (size_t)std::max(1, r.tail_rows) * (size_t)scan->n; }
+
+hipError_t tails_alloc(digest_rows& r, const ss_ctx* scan) {
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc(&r.d_tail[k], tail_bytes(r, scan));
+  return e;
 }
 
-// a.tiles, a.half, a.nrows and a.width follow from n, group_size and nrows here
-void launch_cand_best(ss::CandBestArgs a, int n, int group_size, int nrows, bool walk, hipStream_t stream) {
-  a.tiles = (n + ss::kTrackTile - 1) / ss::kTrackTile;
-  a.half = group_size / 2;
-  a.nrows = nrows;
+// both tails to zero on the context's stream (the caller waits for it)
+hipError_t tails_zero(const digest_rows& r, const ss_ctx* scan) {
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMemsetAsync(r.d_tail[k], 0, tail_bytes(r, scan), scan->stream);
+  return e;
+}
+
+void tails_free(digest_rows& r) {
+  for (float* p : r.d_tail) (void)hipFree(p);
+}
+
+// the rel rows of the last batch and in front of it
+ss::RelRows rel_rows(const ss_ctx* c, const digest_rows& r) {
+  ss::RelRows rows{};
+  rows.n = c->n;
+  rows.n_learn = c->last_n_learn;
+  rows.tail_rows = r.tail_rows;
+  rows.tail = r.d_tail[r.tail_cur];
+  if (c->fused) {
+    rows.psd = c->last_psd;
+    rows.thr = c->last_thr;
+  } else {
+    rows.rel = c->d_rel + (size_t)(c->cfg.grouping_y - 1) * c->n;
+  }
+  return rows;
+}
+
+// the candidates' kernel over the last batch: lists on the device in, cand_best and cand_avg out
+void launch_cand_best(const ss_ctx* c, const digest_rows& r, const ss::RelRows& rows, int nframes, const int32_t* cand_off, const int32_t* cand_idx, int32_t* cand_best,
+                      float* cand_avg) {
+  ss::CandBestArgs a{};
+  a.rows = rows;
+  a.avg = c->last_avg;
+  a.cand_off = cand_off;
+  a.cand_idx = cand_idx;
+  a.cand_best = cand_best;
+  a.cand_avg = cand_avg;
+  a.nframes = nframes;
+  a.tiles = (c->n + ss::kTrackTile - 1) / ss::kTrackTile;
+  a.half = r.group_size / 2;
+  a.nrows = r.nrows;
   a.width = ss::kTrackTile + 2 * a.half;
-  const dim3 grid((unsigned)((size_t)a.nframes * a.tiles));
-  const size_t lds = cand_best_lds(nrows, group_size, walk);
-  if (walk) hipLaunchKernelGGL(ss::k_cand_best, grid, dim3(ss::kTrackTile), lds, stream, a);
-  else hipLaunchKernelGGL(ss::k_best_blocked, grid, dim3(ss::kTrackTile), lds, stream, a);
+  a.start_level = r.start_level;
+  hipLaunchKernelGGL(ss::k_best_blocked, dim3((unsigned)((size_t)nframes * a.tiles)), dim3(ss::kTrackTile), ss::blocked_lds_bytes(r.nrows, a.half), c->stream, a);
+}
+
+// the batch's last rows into the other tail; flip_tail makes it the current one
+void launch_save_tail(const ss_ctx* c, const digest_rows& r, const ss::RelRows& rows, int nframes) {
+  if (r.tail_rows == 0) return;
+  const size_t total = (size_t)r.tail_rows * (size_t)c->n;
+  hipLaunchKernelGGL(ss::k_save_tail, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream, rows, nframes, r.d_tail[r.tail_cur ^ 1]);
+}
+
+void flip_tail(digest_rows& r) {
+  if (r.tail_rows > 0) r.tail_cur ^= 1;
 }
 
 }  // namespace
@@ -3558,11 +3619,7 @@ void launch_cand_best(ss::CandBestArgs a, int n, int group_size, int nrows, bool
 struct st_ctx {
   ss_ctx* scan = nullptr;
   st_config cfg{};
-  bool walk = false;  // cand_best_walk() at st_create
-  int nrows = 1;      // ceil(grouping_y / 2): the rel rows getBestIndex looks at
-  int tail_rows = 0;  // nrows - 1: how many of them can lie before a batch
-  float* d_tail[2] = {};  // [tail_rows][n] each; [tail_cur] holds the rows before the next batch, the other one is written by the digest
-  int tail_cur = 0;
+  digest_rows rows;
   unsigned long long seen_batch = 0;  // ss_ctx::batch_no of the last batch digested (or at st_create / st_reset)
   int32_t *d_off = nullptr, *d_idx = nullptr, *d_best = nullptr, *d_watch = nullptr, *d_pidx = nullptr;
   float *d_cavg = nullptr, *d_pavg = nullptr;
@@ -3579,13 +3636,9 @@ namespace {
 
 thread_local char g_st_create_err[512] = "";
 
-int st_fail(st_ctx* t, int status, const char* fmt, ...) {
-  char* dst = t ? t->err : g_st_create_err;
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(dst, 512, fmt, ap);
-  va_end(ap);
-  return status;
+template <class... A>
+int st_fail(st_ctx* t, int status, const char* fmt, A... a) {
+  return fail_to(t ? t->err : g_st_create_err, status, fmt, a...);
 }
 
 #define ST_HIP(ctx, call)                                                                                 \
@@ -3596,7 +3649,7 @@ int st_fail(st_ctx* t, int status, const char* fmt, ...) {
 
 void st_free(st_ctx* t) {
   if (!t) return;
-  for (float* p : t->d_tail) (void)hipFree(p);
+  tails_free(t->rows);
   for (void* p : {(void*)t->d_off, (void*)t->d_idx, (void*)t->d_best, (void*)t->d_watch, (void*)t->d_pidx, (void*)t->d_cavg, (void*)t->d_pavg}) (void)hipFree(p);
   for (void* p : {(void*)t->h_off, (void*)t->h_idx, (void*)t->h_best, (void*)t->h_watch, (void*)t->h_pidx, (void*)t->h_cavg, (void*)t->h_pavg}) (void)hipHostFree(p);
   delete t;
@@ -3650,22 +3703,16 @@ int st_create(ss_ctx* scan, const st_config* cfg, st_ctx** out) {
   if (cfg->group_size < 0 || cfg->max_watch <= 0 || cfg->cand_cap <= 0) return st_fail(nullptr, SS_ERR_INVALID, "group_size >= 0, max_watch > 0 and cand_cap > 0 required");
   std::lock_guard<std::mutex> lock(scan->mtx);
   if (!(scan->cfg.flags & SS_FLAG_KEEP_PLANES)) return st_fail(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_KEEP_PLANES (the digest reads the kept dB and avg planes)");
-  const int nrows = (scan->cfg.grouping_y + 1) / 2;
-  const bool walk = cand_best_walk();
-  const size_t lds = cand_best_lds(nrows, cfg->group_size, walk);
-  if (lds > 65536) return st_fail(nullptr, SS_ERR_INVALID, "group_size %d with %d rows needs %zu bytes of LDS per tile (64 KiB at most)", cfg->group_size, nrows, lds);
+  digest_rows rows;
+  if (const int st = digest_rows_plan(rows, scan, cfg->group_size, cfg->start_level, g_st_create_err); st != SS_OK) return st;
   st_ctx* t = new (std::nothrow) st_ctx();
   if (!t) return st_fail(nullptr, SS_ERR_NOMEM, "out of memory");
   t->scan = scan;
   t->cfg = *cfg;
-  t->walk = walk;
-  t->nrows = nrows;
-  t->tail_rows = nrows - 1;
+  t->rows = rows;
   t->seen_batch = scan->batch_no;
-  const size_t tail_bytes = sizeof(float) * (size_t)std::max(1, t->tail_rows) * (size_t)scan->n;
   const size_t frames = (size_t)scan->cfg.max_batch;
-  bool ok = hipSetDevice(scan->cfg.device_id) == hipSuccess;
-  for (int k = 0; k < 2 && ok; ++k) ok = hipMalloc(&t->d_tail[k], tail_bytes) == hipSuccess && hipMemsetAsync(t->d_tail[k], 0, tail_bytes, scan->stream) == hipSuccess;
+  bool ok = hipSetDevice(scan->cfg.device_id) == hipSuccess && tails_alloc(t->rows, scan) == hipSuccess && tails_zero(t->rows, scan) == hipSuccess;
   ok = ok && hipMalloc(&t->d_off, sizeof(int32_t) * (frames + 1)) == hipSuccess && hipHostMalloc(&t->h_off, sizeof(int32_t) * (frames + 1)) == hipSuccess;
   ok = ok && hipMalloc(&t->d_watch, sizeof(int32_t) * (size_t)cfg->max_watch) == hipSuccess && hipHostMalloc(&t->h_watch, sizeof(int32_t) * (size_t)cfg->max_watch) == hipSuccess;
   ok = ok && hipStreamSynchronize(scan->stream) == hipSuccess;
@@ -3695,8 +3742,7 @@ int st_reset(st_ctx* t) {
   ss_ctx* c = t->scan;
   std::lock_guard<std::mutex> lock(c->mtx);
   ST_HIP(t, hipSetDevice(c->cfg.device_id));
-  const size_t tail_bytes = sizeof(float) * (size_t)std::max(1, t->tail_rows) * (size_t)c->n;
-  ST_HIP(t, hipMemsetAsync(t->d_tail[t->tail_cur], 0, tail_bytes, c->stream));
+  ST_HIP(t, hipMemsetAsync(t->rows.d_tail[t->rows.tail_cur], 0, tail_bytes(t->rows, c), c->stream));
   ST_HIP(t, hipStreamSynchronize(c->stream));
   t->seen_batch = c->batch_no;
   return SS_OK;
@@ -3707,7 +3753,7 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
   if (!cand_off || !out || nkeys < 0 || (nkeys > 0 && !keys)) return st_fail(t, SS_ERR_INVALID, "null argument");
   ss_ctx* c = t->scan;
   std::lock_guard<std::mutex> lock(c->mtx);
-  const int n = c->n, nframes = c->last_n, G = c->cfg.grouping_y;
+  const int n = c->n, nframes = c->last_n;
   if (nframes <= 0) return st_fail(t, SS_ERR_INVALID, "no batch processed since ss_create / ss_reset / ss_reset_noise");
   if (c->batch_no == t->seen_batch) return st_fail(t, SS_ERR_INVALID, "the last batch has been digested already (or none has run since st_create / st_reset)");
   if (c->batch_no != t->seen_batch + 1)
@@ -3737,34 +3783,13 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
   if (nkeys > t->cfg.max_watch) return st_fail(t, SS_ERR_INVALID, "%d keys > max_watch %d", nkeys, t->cfg.max_watch);
   for (int k = 0; k < nkeys; ++k)
     if (keys[k] < 0 || keys[k] >= n) return st_fail(t, SS_ERR_INVALID, "key %d: bin %d outside [0, %d)", k, keys[k], n);
-  ST_HIP(t, hipSetDevice(c->cfg.device_id));
   flush_stages(c);
-  ss::RelRows rows{};
-  rows.n = n;
-  rows.n_learn = c->last_n_learn;
-  rows.tail_rows = t->tail_rows;
-  rows.tail = t->d_tail[t->tail_cur];
-  if (c->fused) {
-    rows.psd = c->last_psd;
-    rows.thr = c->last_thr;
-  } else {
-    rows.rel = c->d_rel + (size_t)(G - 1) * n;
-  }
-  const int half = t->cfg.group_size / 2;
+  const ss::RelRows rows = rel_rows(c, t->rows);
   uint64_t d2h = 0;
   if (ncand > 0) {
     ST_HIP(t, hipMemcpyAsync(t->d_off, t->h_off, sizeof(int32_t) * ((size_t)nframes + 1), hipMemcpyHostToDevice, c->stream));
     ST_HIP(t, hipMemcpyAsync(t->d_idx, t->h_idx, sizeof(int32_t) * (size_t)ncand, hipMemcpyHostToDevice, c->stream));
-    ss::CandBestArgs a{};
-    a.rows = rows;
-    a.avg = c->last_avg;
-    a.cand_off = t->d_off;
-    a.cand_idx = t->d_idx;
-    a.cand_best = t->d_best;
-    a.cand_avg = t->d_cavg;
-    a.nframes = nframes;
-    a.start_level = t->cfg.start_level;
-    launch_cand_best(a, n, t->cfg.group_size, t->nrows, t->walk, c->stream);
+    launch_cand_best(c, t->rows, rows, nframes, t->d_off, t->d_idx, t->d_best, t->d_cavg);
     ST_HIP(t, hipGetLastError());
     ST_HIP(t, hipMemcpyAsync(t->h_best, t->d_best, sizeof(int32_t) * (size_t)ncand, hipMemcpyDeviceToHost, c->stream));
     ST_HIP(t, hipMemcpyAsync(t->h_cavg, t->d_cavg, sizeof(float) * (size_t)ncand, hipMemcpyDeviceToHost, c->stream));
@@ -3804,7 +3829,7 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
     p.n = n;
     p.nframes = nframes;
     p.nwatch = nwatch;
-    p.half = half;
+    p.half = t->rows.group_size / 2;
     const size_t items = (size_t)nframes * (size_t)nwatch;
     hipLaunchKernelGGL(ss::k_window_peaks, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, c->stream, p);
     ST_HIP(t, hipGetLastError());
@@ -3812,13 +3837,10 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
     ST_HIP(t, hipMemcpyAsync(t->h_pavg, t->d_pavg, sizeof(float) * items, hipMemcpyDeviceToHost, c->stream));
     d2h += 8ull * (uint64_t)items;
   }
-  if (t->tail_rows > 0) {
-    const size_t total = (size_t)t->tail_rows * (size_t)n;
-    hipLaunchKernelGGL(ss::k_save_tail, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream, rows, nframes, t->d_tail[t->tail_cur ^ 1]);
-    ST_HIP(t, hipGetLastError());
-  }
+  launch_save_tail(c, t->rows, rows, nframes);
+  ST_HIP(t, hipGetLastError());
   ST_HIP(t, stream_wait(c->stream));
-  if (t->tail_rows > 0) t->tail_cur ^= 1;
+  flip_tail(t->rows);
   t->seen_batch = c->batch_no;
   out->nframes = nframes;
   out->ncand = ncand;
@@ -3859,10 +3881,7 @@ struct stf_ctx {
   ss_ctx* scan = nullptr;
   ss_feed* feed = nullptr;  // null once the feed has been destroyed: only stf_destroy / stf_last_error from then on
   stf_config cfg{};
-  bool walk = false;             // as st_ctx
-  int nrows = 1, tail_rows = 0;  // as st_ctx
-  float* d_tail[2] = {};
-  int tail_cur = 0;
+  digest_rows rows;
   uint32_t *d_mark = nullptr, *d_keymark = nullptr;  // [n] each: sequence number of the newest batch that had the bin as cand_best / as a posted key
   int32_t* d_counts = nullptr;                       // [ceil(n / 256)] block counts, then their prefix sums
   int nblocks = 0;
@@ -3877,18 +3896,14 @@ namespace {
 
 thread_local char g_stf_create_err[512] = "";
 
-int stf_fail(stf_ctx* t, int status, const char* fmt, ...) {
-  char* dst = t ? t->err : g_stf_create_err;
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(dst, 512, fmt, ap);
-  va_end(ap);
-  return status;
+template <class... A>
+int stf_fail(stf_ctx* t, int status, const char* fmt, A... a) {
+  return fail_to(t ? t->err : g_stf_create_err, status, fmt, a...);
 }
 
 void stf_free(stf_ctx* t) {
   if (!t) return;
-  for (float* p : t->d_tail) (void)hipFree(p);
+  tails_free(t->rows);
   for (void* p : {(void*)t->d_mark, (void*)t->d_keymark, (void*)t->d_counts}) (void)hipFree(p);
   for (auto& s : t->slots) {
     for (void* p : {(void*)s.d_coff, (void*)s.d_best, (void*)s.d_watch, (void*)s.d_pidx, (void*)s.d_keys, (void*)s.d_cavg, (void*)s.d_pavg, (void*)s.d_hdr}) (void)hipFree(p);
@@ -3897,13 +3912,10 @@ void stf_free(stf_ctx* t) {
   delete t;
 }
 
-size_t stf_tail_bytes(const stf_ctx* t) { return sizeof(float) * (size_t)std::max(1, t->tail_rows) * (size_t)t->scan->n; }
-
 // (under the context's lock) rows, marks and post back to zero, on the context's stream
 hipError_t stf_clear(stf_ctx* t) {
   ss_ctx* c = t->scan;
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMemsetAsync(t->d_tail[k], 0, stf_tail_bytes(t), c->stream);
+  hipError_t e = tails_zero(t->rows, c);
   if (e == hipSuccess) e = hipMemsetAsync(t->d_mark, 0, sizeof(uint32_t) * (size_t)c->n, c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(t->d_keymark, 0, sizeof(uint32_t) * (size_t)c->n, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -3922,7 +3934,7 @@ int stf_enqueue(ss_feed* f, int slot_no, int nframes) {
   ss_ctx* c = f->c;
   ss_feed_slot& fs = f->slots[(size_t)slot_no];
   stf_slot& s = t->slots[(size_t)slot_no];
-  const int n = c->n, G = c->cfg.grouping_y;
+  const int n = c->n;
   if (t->next_seq > 0xffffffffull) return fail(c, SS_ERR_INVALID, "tracked feed: 2^32 - 1 batches since stf_create / stf_reset (the device counts in 32 bits): stf_reset");
   if (!c->last_avg || (c->fused && (!c->last_psd || !c->last_thr)) || (!c->fused && !c->d_rel))
     return fail(c, SS_ERR_INVALID, "tracked feed: the batch left no dB plane, avg plane or noise ceiling to digest");
@@ -3943,28 +3955,8 @@ int stf_enqueue(ss_feed* f, int slot_no, int nframes) {
   pa.nkeys = nkeys;
   pa.seq = seq;
   hipLaunchKernelGGL(ss::k_feed_prepare, dim3((unsigned)grid_for((size_t)std::max(nframes + 1, nkeys), 256)), dim3(256), 0, c->stream, pa);
-  ss::RelRows rows{};
-  rows.n = n;
-  rows.n_learn = c->last_n_learn;
-  rows.tail_rows = t->tail_rows;
-  rows.tail = t->d_tail[t->tail_cur];
-  if (c->fused) {
-    rows.psd = c->last_psd;
-    rows.thr = c->last_thr;
-  } else {
-    rows.rel = c->d_rel + (size_t)(G - 1) * n;
-  }
-  const int half = t->cfg.group_size / 2;
-  ss::CandBestArgs a{};
-  a.rows = rows;
-  a.avg = c->last_avg;
-  a.cand_off = s.d_coff;
-  a.cand_idx = fs.d_idx;
-  a.cand_best = s.d_best;
-  a.cand_avg = s.d_cavg;
-  a.nframes = nframes;
-  a.start_level = t->cfg.start_level;
-  launch_cand_best(a, n, t->cfg.group_size, t->nrows, t->walk, c->stream);
+  const ss::RelRows rows = rel_rows(c, t->rows);
+  launch_cand_best(c, t->rows, rows, nframes, s.d_coff, fs.d_idx, s.d_best, s.d_cavg);
   hipLaunchKernelGGL(ss::k_feed_stamp, dim3((unsigned)std::min(grid_for((size_t)f->cand_cap, 256), 1024)), dim3(256), 0, c->stream, (const int32_t*)s.d_coff, nframes,
                      (const int32_t*)s.d_best, t->d_mark, n, seq, s.d_hdr);
   hipLaunchKernelGGL(ss::k_feed_count, dim3((unsigned)t->nblocks), dim3(ss::kFeedBlock), 0, c->stream, (const uint32_t*)t->d_mark, (const uint32_t*)t->d_keymark, n, p, seq,
@@ -3981,15 +3973,12 @@ int stf_enqueue(ss_feed* f, int slot_no, int nframes) {
   pk.peak_avg = s.d_pavg;
   pk.n = n;
   pk.nframes = nframes;
-  pk.half = half;
+  pk.half = t->rows.group_size / 2;
   // (the list's length is known to the device only: enough workgroups to fill the machine, each walks its share)
   const size_t most = ((size_t)nframes * (size_t)t->cfg.max_watch + 3) / 4;
   hipLaunchKernelGGL(ss::k_feed_peaks, dim3((unsigned)std::min<size_t>(most, 2048)), dim3(256), 0, c->stream, pk);
-  if (t->tail_rows > 0) {
-    const size_t total = (size_t)t->tail_rows * (size_t)n;
-    hipLaunchKernelGGL(ss::k_save_tail, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream, rows, nframes, t->d_tail[t->tail_cur ^ 1]);
-    t->tail_cur ^= 1;  // (stream order: the next batch's digest reads what this one wrote)
-  }
+  launch_save_tail(c, t->rows, rows, nframes);
+  flip_tail(t->rows);  // (stream order: the next batch's digest reads what this one wrote)
   SS_HIP(c, hipGetLastError());
   SS_HIP(c, hipMemcpyAsync(s.h_hdr, s.d_hdr, sizeof(ss::FeedDigestHeader), hipMemcpyDeviceToHost, c->stream));
   s.seq = t->next_seq++;
@@ -4083,23 +4072,18 @@ int stf_create(ss_feed* f, const stf_config* cfg, stf_ctx** out) {
   if (f->cand_cap <= 0) return stf_fail(nullptr, SS_ERR_INVALID, "the feed was created with cand_cap 0: there are no candidate lists to digest");
   if (f->tracker) return stf_fail(nullptr, SS_ERR_INVALID, "the feed already has a tracker");
   if (f->pending > 0 || f->acquired >= 0) return stf_fail(nullptr, SS_ERR_INVALID, "the feed has batches pending: collect them first");
-  const int nrows = (c->cfg.grouping_y + 1) / 2;
-  const bool walk = cand_best_walk();
-  const size_t lds = cand_best_lds(nrows, cfg->group_size, walk);
-  if (lds > 65536) return stf_fail(nullptr, SS_ERR_INVALID, "group_size %d with %d rows needs %zu bytes of LDS per tile (64 KiB at most)", cfg->group_size, nrows, lds);
+  digest_rows rows;
+  if (const int st = digest_rows_plan(rows, c, cfg->group_size, cfg->start_level, g_stf_create_err); st != SS_OK) return st;
   stf_ctx* t = new (std::nothrow) stf_ctx();
   if (!t) return stf_fail(nullptr, SS_ERR_NOMEM, "out of memory");
   t->scan = c;
   t->feed = f;
   t->cfg = *cfg;
-  t->walk = walk;
-  t->nrows = nrows;
-  t->tail_rows = nrows - 1;
+  t->rows = rows;
   t->nblocks = (c->n + ss::kFeedBlock - 1) / ss::kFeedBlock;
   t->slots.resize((size_t)f->depth);
   const size_t n = (size_t)c->n, frames = (size_t)c->cfg.max_batch, cap = (size_t)f->cand_cap, mw = (size_t)cfg->max_watch;
-  bool ok = hipSetDevice(c->cfg.device_id) == hipSuccess;
-  for (int k = 0; k < 2 && ok; ++k) ok = hipMalloc(&t->d_tail[k], stf_tail_bytes(t)) == hipSuccess;
+  bool ok = hipSetDevice(c->cfg.device_id) == hipSuccess && tails_alloc(t->rows, c) == hipSuccess;
   ok = ok && hipMalloc(&t->d_mark, sizeof(uint32_t) * n) == hipSuccess && hipMalloc(&t->d_keymark, sizeof(uint32_t) * n) == hipSuccess;
   ok = ok && hipMalloc(&t->d_counts, sizeof(int32_t) * (size_t)t->nblocks) == hipSuccess;
   for (auto& s : t->slots) {
@@ -4178,7 +4162,7 @@ int stf_reset(stf_ctx* t) {
   if (!t->feed) return stf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
   if (t->feed->pending > 0 || t->feed->acquired >= 0) return stf_fail(t, SS_ERR_INVALID, "stf_reset with batches pending: collect them first");
   if (hipSetDevice(c->cfg.device_id) != hipSuccess || stf_clear(t) != hipSuccess) return stf_fail(t, SS_ERR_HIP, "clearing the kept rows and marks failed: %s", hipGetErrorString(hipGetLastError()));
-  t->tail_cur = 0;
+  t->rows.tail_cur = 0;
   return SS_OK;
 }
 

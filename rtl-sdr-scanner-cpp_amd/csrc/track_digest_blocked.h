@@ -1,6 +1,6 @@
-// track_digest_blocked.h — k_cand_best's job (track_digest.h: per candidate the mode of the window arg-maxes of the newest rel rows)
-// with the blocked sliding arg-max in place of the walk: a lane's work per row no longer grows with the window, and one row at a time
-// sits in LDS, so a window may be thousands of bins wide.
+// track_digest_blocked.h — the candidates' kernel of the tracking digest (track_digest.h: per candidate the mode of the window arg-maxes
+// of the newest rel rows), by a blocked sliding arg-max: a lane's work per row does not grow with the window, and one row at a time
+// sits in LDS, so a window may be thousands of bins wide. (It replaced a bin-by-bin walk of every window, now retired.)
 //
 // A row is cut into blocks of W = 2 * half + 1 bins, aligned at bin 0 of the row, the last one clipped at n. Two tables per staged bin:
 //   P[i]  arg-max of [block start, i]: scanned forward, a bin replaces the running best if it is no NaN and nothing is held yet or its
@@ -18,13 +18,16 @@
 // The staged span [s_lo, s_hi] of the tile is enough: P[hi - 1] is never asked for a block that starts below s_lo unless lo is that
 // start (and lo >= s_lo), S[lo] never for a block that ends above s_hi unless hi - 1 = n - 1 = s_hi.
 //
-// The table build and the query are plain functions over a row pointer; tests/host/blocked_argmax_check.cpp compiles them for the host.
+// A lane keeps the arg-maxes of the rows that qualify in an ascending list in LDS (list_insert) and answers with their mode (list_mode).
+//
+// The table build, the query and the list functions are plain functions over pointers; tests/host/blocked_argmax_check.cpp compiles them
+// for the host.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
 #ifdef __HIPCC__
-#include <hip/hip_runtime.h>
+#include "track_digest.h"
 #define SS_BLOCKED_HD __host__ __device__ __forceinline__
 #else
 #define SS_BLOCKED_HD inline
@@ -135,19 +138,85 @@ SS_BLOCKED_HD int blocked_query(const float* row, const uint16_t* P, const uint1
   return s_lo + (int)a;
 }
 
+// A lane's list: entry k at list[k * stride], ascending. Inserts v into a list of m entries; the caller counts.
+SS_BLOCKED_HD void list_insert(int* list, int stride, int m, int v) {
+  int k = m;
+  while (k > 0 && list[(k - 1) * stride] > v) {
+    list[k * stride] = list[(k - 1) * stride];
+    --k;
+  }
+  list[k * stride] = v;
+}
+
+// mostFrequentValue over the list's m entries: of the runs of equal values, the longest; of several that long, the one at position
+// ties / 2 in ascending order. An empty list gives otherwise.
+SS_BLOCKED_HD int list_mode(const int* list, int stride, int m, int otherwise) {
+  int result = otherwise;
+  if (m > 0) {
+    int top = 0, ties = 0;
+    for (int i = 0; i < m;) {
+      const int v = list[i * stride];
+      int e = i + 1;
+      while (e < m && list[e * stride] == v) ++e;
+      if (e - i > top) {
+        top = e - i;
+        ties = 1;
+      } else if (e - i == top) {
+        ++ties;
+      }
+      i = e;
+    }
+    int want = ties / 2;
+    for (int i = 0; i < m;) {
+      const int v = list[i * stride];
+      int e = i + 1;
+      while (e < m && list[e * stride] == v) ++e;
+      if (e - i == top) {
+        if (want == 0) {
+          result = v;
+          break;
+        }
+        --want;
+      }
+      i = e;
+    }
+  }
+  return result;
+}
+
 // dynamic LDS of k_best_blocked: one row's values, P and S, the lanes' lists, the waves' totals
 SS_BLOCKED_HD size_t blocked_lds_bytes(int nrows, int half) {
   return (size_t)8 * (size_t)(kBlockedLanes + 2 * half) + sizeof(int) * (size_t)nrows * kBlockedLanes + 64;
 }
 
-}  // namespace ss
-
-#ifdef __HIPCC__
-#include "track_digest.h"
-
-namespace ss {
+#ifdef __HIPCC__  // the kernel itself
 
 static_assert(kBlockedLanes == kTrackTile, "one lane per bin of a tile");
+
+struct CandBestArgs {
+  RelRows rows;
+  const float* avg;         // the batch's avg plane
+  const int32_t* cand_off;  // [nframes + 1], clipped to ncand
+  const int32_t* cand_idx;  // [ncand], ascending inside a frame
+  int32_t* cand_best;       // [ncand]
+  float* cand_avg;          // [ncand]
+  int nframes;
+  int tiles;       // ceil(n / kTrackTile)
+  int half;        // group_size / 2
+  int nrows;       // ceil(grouping_y / 2) = tail_rows + 1
+  int width;       // staged bins of a row: kTrackTile + 2 * half
+  float start_level;
+};
+
+// first candidate of the frame's list [a, b) at or above bin: the lists are ascending
+__device__ __forceinline__ int cand_lower_bound(const int32_t* idx, int a, int b, int bin) {
+  while (a < b) {
+    const int m = (a + b) >> 1;
+    if (idx[m] < bin) a = m + 1;
+    else b = m;
+  }
+  return a;
+}
 
 __device__ __forceinline__ SegBest seg_shfl_up(SegBest x, int d) {
   const uint32_t k = __shfl_up(x.b.i | (x.head ? 0x10000u : 0u), d, 64);
@@ -159,8 +228,10 @@ __device__ __forceinline__ SegBest seg_shfl_down(SegBest x, int d) {
   return SegBest{Best{__shfl_down(x.b.v, d, 64), k & 0xffffu}, (k & 0x10000u) != 0};
 }
 
-// Arguments, grid, outputs and the early return of k_cand_best. Dynamic LDS (blocked_lds_bytes): width floats (the row), nrows * 256
-// ints (the lanes' ascending lists), width + width 16-bit offsets (P, S), 16 words (wave totals).
+// grid nframes * tiles, 256 threads. A workgroup whose tile of its frame holds no candidate returns at once; otherwise it stages, row
+// by row, the bins its candidates' windows can touch, and lane t takes the tile's t-th candidate (a tile holds at most 256).
+// Dynamic LDS (blocked_lds_bytes): width floats (the row), nrows * 256 ints (the lanes' ascending lists), width + width 16-bit
+// offsets (P, S), 16 words (wave totals).
 __global__ __launch_bounds__(kTrackTile) void k_best_blocked(const CandBestArgs a) {
   extern __shared__ float lds_blocked[];
   const int n = a.rows.n;
@@ -229,53 +300,15 @@ __global__ __launch_bounds__(kTrackTile) void k_best_blocked(const CandBestArgs 
     __syncthreads();
     if (active) {
       const int best = blocked_query(row, P, S, s_lo, W, rem_lo, lo, hi);
-      if (a.start_level <= row[best - s_lo]) {  // insert into the ascending list
-        int k = m;
-        while (k > 0 && mine[(k - 1) * kTrackTile] > best) {
-          mine[k * kTrackTile] = mine[(k - 1) * kTrackTile];
-          --k;
-        }
-        mine[k * kTrackTile] = best;
-        ++m;
-      }
+      if (a.start_level <= row[best - s_lo]) list_insert(mine, kTrackTile, m++, best);
     }
     __syncthreads();  // (the next row overwrites row, P and S)
   }
   if (!active) return;
-  int result = c;  // no row qualifies: the candidate itself (signal_tracker.cpp, getBestIndex)
-  if (m > 0) {
-    // runs of equal values: the longest count, how many runs reach it, and of those the one at position size / 2
-    int top = 0, ties = 0;
-    for (int i = 0; i < m;) {
-      const int v = mine[i * kTrackTile];
-      int e = i + 1;
-      while (e < m && mine[e * kTrackTile] == v) ++e;
-      if (e - i > top) {
-        top = e - i;
-        ties = 1;
-      } else if (e - i == top) {
-        ++ties;
-      }
-      i = e;
-    }
-    int want = ties / 2;
-    for (int i = 0; i < m;) {
-      const int v = mine[i * kTrackTile];
-      int e = i + 1;
-      while (e < m && mine[e * kTrackTile] == v) ++e;
-      if (e - i == top) {
-        if (want == 0) {
-          result = v;
-          break;
-        }
-        --want;
-      }
-      i = e;
-    }
-  }
-  a.cand_best[j] = result;
+  a.cand_best[j] = list_mode(mine, kTrackTile, m, c);  // no row qualifies: the candidate itself (signal_tracker.cpp, getBestIndex)
   a.cand_avg[j] = a.avg[(size_t)f * n + c];
 }
 
-}  // namespace ss
 #endif  // __HIPCC__
+
+}  // namespace ss

@@ -1,14 +1,14 @@
 // track_feed.h — the tracking digest behind the pipelined feed (include/specscan_track_feed.h): the steps of st_digest that ran on the
 // host — clipping the offsets, forming the watch list — as kernels, so that a batch is digested in the stream right behind its chain,
-// with no host wait in between. The candidates' kernel (k_best_blocked of
-// track_digest_blocked.h; launch_cand_best in specscan.hip) and k_save_tail of track_digest.h run unchanged between them.
+// with no host wait in between. The candidates' kernel (k_best_blocked of track_digest_blocked.h; launch_cand_best in specscan.hip)
+// and k_save_tail of track_digest.h run unchanged between them.
 //
 //   k_feed_prepare   coff[f] = min(off[f], cand_cap); keymark[key] = seq for the posted keys; the header's flags to zero
 //   k_feed_stamp     mark[cand_best[j]] = seq for every candidate of the clipped lists
 //   k_feed_count     per 256-bin block: how many bins are watched (mark > p, or keymark == seq)
 //   k_feed_scan      exclusive scan of the block counts (one wave, a run of consecutive counts per lane); writes the header
 //   k_feed_scatter   the watched bins, ascending, to watch[0 .. min(nwatch, max_watch))
-//   k_feed_peaks     k_window_peaks over a list whose length only the device knows: grid-stride, one wave per (frame, watch key)
+//   k_feed_peaks     k_window_peaks (its window_peak) over a list whose length only the device knows: grid-stride, one wave per (frame, watch key)
 //
 // The watch list: mark[b] is the sequence number of the newest batch that had b as cand_best of a candidate, keymark[b] the one of the
 // newest batch whose submit found b among the posted keys K_p. Batch seq watches {b: mark[b] > p} U {b: keymark[b] == seq}
@@ -134,31 +134,16 @@ struct FeedPeaksArgs {
   int n, nframes, half;
 };
 
-// Grid-stride, one wave per (frame, watch key), the arg-max rule of k_window_peaks (track_digest.h) word for word. The list's length is
-// read from the header; a list that overflowed max_watch has no peaks (stf_result::status says so).
+// Grid-stride, one wave per (frame, watch key): window_peak of track_digest.h. The list's length is read from the header; a list that
+// overflowed max_watch has no peaks (stf_result::status says so).
 __global__ __launch_bounds__(256) void k_feed_peaks(const FeedPeaksArgs a) {
   const int lane = threadIdx.x & 63;
   const int nwatch = (a.hdr->flags & kFeedOverflow) ? 0 : a.hdr->nwatch;
   const long long items = (long long)a.nframes * nwatch;
   for (long long item = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); item < items; item += (long long)gridDim.x * 4) {
     const int f = (int)(item / nwatch), w = (int)(item % nwatch);
-    const int key = a.watch[w];
-    const int lo = key - a.half < 0 ? 0 : key - a.half;
-    const int hi = key + a.half + 1 < a.n ? key + a.half + 1 : a.n;
     const float* row = a.avg + (size_t)f * a.n;
-    const float head = row[lo];
-    float v = 0.0f;
-    int best = -1;
-    for (int i = lo + lane; i < hi; i += 64) {
-      const float x = row[i];
-      if (x != x) continue;  // a NaN behind lo never wins (and one at lo is settled below)
-      if (best < 0 || v < x) {
-        v = x;
-        best = i;
-      }
-    }
-    wave_argmax(v, best);
-    if (head != head || best < 0) best = lo;  // a NaN at lo is never displaced (v[best] < x is false for every x)
+    const int best = window_peak(row, a.n, a.half, a.watch[w], lane);
     if (lane == 0) {
       a.peak_idx[item] = best;
       a.peak_avg[item] = row[best];

@@ -14,10 +14,9 @@ leaves in flight when its turn ends is a millisecond or two of device work that 
 Prints one JSON line per shape. With --route b (or c) only that route runs: the form to put behind
 `rocprofv3 --kernel-trace --stats --` for the device times of the digest's kernels.
 
-    python scripts/track_digest_rate.py [--reps 7] [--route abc|ab|a|b|c] [--shapes 8192,1048576] [--group G] [--diag]
+    python scripts/track_digest_rate.py [--reps 7] [--route abc|ab|a|b|c] [--shapes 8192,1048576] [--group G]
 
---group G replaces the shapes' group_size (128 and 547). --diag loads the diagnostics build, which reads SS_CAND_BEST=walk at
-st_create / stf_create: the walk of csrc/track_digest.h instead of the blocked kernel, on the same library.
+--group G replaces the shapes' group_size (128 and 547).
 """
 from __future__ import annotations
 
@@ -192,10 +191,7 @@ def main():
     ap.add_argument("--route", default="ab", choices=("abc", "ab", "a", "b", "c"))
     ap.add_argument("--shapes", default="8192,1048576")
     ap.add_argument("--group", type=int, default=None)
-    ap.add_argument("--diag", action="store_true")
     args = ap.parse_args()
-    if args.diag:
-        pkg.engine.use_diag_library(True)
     for n in (int(s) for s in args.shapes.split(",")):
         g = args.group if args.group is not None else 128 if n == 8192 else 547
         shape(n, 1024 if n == 8192 else 16, g, args.reps, list(args.route))

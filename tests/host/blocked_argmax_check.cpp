@@ -2,8 +2,10 @@
 // row pointer), with the 256 lanes of k_best_blocked played by loops — chunked local scans, the segmented scan over the chunks in the
 // kernel's order (six shuffle steps inside each wave of 64, the four waves' totals, the neighbour's inclusive result as the exclusive
 // one), the fix-ups — against std::max_element written out. The staged span is copied into vectors of exactly its length, so that
-// the address sanitizer sees any access outside it. Also: the tables against their definitions, and the join operators' associativity.
+// the address sanitizer sees any access outside it. Also: the tables against their definitions, the join operators' associativity, and
+// the lanes' list functions (list_insert, list_mode) against mostFrequentValue written out.
 // Plain C++ (g++ -fsanitize=address,undefined), no HIP. Prints "... bad 0" when everything holds.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -17,7 +19,7 @@
 using ss::Best;
 using ss::SegBest;
 
-static long long g_bad = 0, g_windows = 0, g_tables = 0;
+static long long g_bad = 0, g_windows = 0, g_tables = 0, g_lists = 0;
 
 static int argmax_literal(const float* row, int lo, int hi) {
   int best = lo;
@@ -148,9 +150,57 @@ static void check_associativity(std::mt19937& rng) {
   }
 }
 
+// mostFrequentValue (collection_utils.h:29-50) written out: sort, count, the values that reach the top count in ascending order, and of
+// those the one at size / 2
+static int mode_literal(std::vector<int> values) {
+  std::sort(values.begin(), values.end());
+  std::vector<std::pair<int, int>> counts;  // (value, count), ascending
+  for (int v : values) {
+    if (counts.empty() || counts.back().first != v) counts.push_back({v, 0});
+    ++counts.back().second;
+  }
+  int top = 0;
+  for (const auto& c : counts) top = std::max(top, c.second);
+  std::vector<int> most;
+  for (const auto& c : counts)
+    if (c.second == top) most.push_back(c.first);
+  return most[most.size() / 2];
+}
+
+// A lane's list as k_best_blocked keeps it: entry k at list[k * 256], up to eleven of them (grouping_y 21), inserted in random order.
+// Lane t's buffer ends with its list's last possible entry; whatever a trial does not own holds a canary (bins are never negative)
+// that must survive.
+static void check_lists(std::mt19937& rng) {
+  const int stride = ss::kBlockedLanes, rows = 11, canary = -12345;
+  const int spans[] = {1, 2, 3, 50};  // distinct bins to draw from: ties of every multiplicity
+  std::vector<std::vector<int>> lds((size_t)stride);
+  for (int t = 0; t < stride; ++t) lds[(size_t)t].assign((size_t)((rows - 1) * stride + t + 1), canary);
+  std::uniform_int_distribution<int> len(0, rows), lane(0, stride - 1), base(0, 1 << 20);
+  for (int trial = 0; trial < 300000; ++trial) {
+    const int m = len(rng), t = lane(rng), b0 = base(rng), cand = b0 + 7;
+    std::uniform_int_distribution<int> bin(b0, b0 + spans[trial % 4] - 1);
+    int* mine = lds[(size_t)t].data() + t;
+    std::vector<int> values;
+    for (int k = 0; k < m; ++k) {
+      values.push_back(bin(rng));
+      ss::list_insert(mine, stride, k, values.back());
+    }
+    for (int k = 1; k < m; ++k)
+      if (mine[(k - 1) * stride] > mine[k * stride]) fail("list order", m, 0, t, k, mine[k * stride], mine[(k - 1) * stride]);
+    const int got = ss::list_mode(mine, stride, m, cand), want = m == 0 ? cand : mode_literal(values);
+    if (got != want) fail("list mode", m, spans[trial % 4], t, trial, got, want);
+    for (int k = 0; k < m; ++k) mine[k * stride] = canary;
+    ++g_lists;
+  }
+  for (int t = 0; t < stride; ++t)
+    for (size_t i = 0; i < lds[(size_t)t].size(); ++i)
+      if (lds[(size_t)t][i] != canary) fail("list canary", 0, 0, t, (int)i, lds[(size_t)t][i], canary);
+}
+
 int main() {
   std::mt19937 rng(20240611);
   check_associativity(rng);
+  check_lists(rng);
   const int halves[] = {0, 1, 2, 20, 64, 65, 127, 128, 300, 550, 2048};
   for (int half : halves) {
     const int W = 2 * half + 1;
@@ -176,6 +226,6 @@ int main() {
       }
     }
   }
-  printf("windows %lld table entries %lld bad %lld\n", g_windows, g_tables, g_bad);
+  printf("windows %lld table entries %lld lists %lld bad %lld\n", g_windows, g_tables, g_lists, g_bad);
   return g_bad == 0 ? 0 : 1;
 }

@@ -221,7 +221,7 @@ def test_digest_kernels_use_no_scratch(tmp_path):
         seen[name] = dict(vgprs=get("VGPRs"), spill=get("VGPRs Spill"), scratch=get(r"ScratchSize \[bytes/lane\]"), lds=get(r"LDS Size \[bytes/block\]"),
                           occupancy=get(r"Occupancy \[waves/SIMD\]"))
     print(seen)
-    for kernel in ("k_cand_best", "k_window_peaks", "k_save_tail"):
+    for kernel in ("k_window_peaks", "k_save_tail"):
         hit = [r for name, r in seen.items() if kernel in name]
         assert len(hit) == 1, (kernel, list(seen))
         assert hit[0]["scratch"] == 0 and hit[0]["spill"] == 0, (kernel, hit[0])
