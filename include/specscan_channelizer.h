@@ -84,6 +84,36 @@ int sc_process(sc_ctx* ctx, const void* iq, int32_t nsamples, int8_t* out_i8, fl
 int sc_process_device(sc_ctx* ctx, const void* d_iq, int32_t nsamples, int8_t* d_out_i8, float* d_out_cf32, int32_t* counts, int32_t cap);
 int sc_sync(sc_ctx* ctx);
 
+/* Per-slot sample ranges in one call: recordings that begin, end and retune inside the stream of one call, at sample
+ * resolution, without sc_start / sc_stop between calls. */
+#define SC_MAX_RANGES 64
+typedef struct sc_range {
+  int32_t channel;    /* 0 .. channels-1 */
+  int32_t shift_hz;   /* as sc_start */
+  int32_t begin, end; /* samples of THIS call's stream: [begin, end), 0 <= begin <= end <= nsamples */
+} sc_range;
+
+/* Defined by the entry points above: for every channel, its ranges in the order given, and for each of them
+ * sc_start(channel, shift_hz), a sc_process* of samples [begin, end) with only that channel unblocked, sc_stop(channel).
+ * A channel's outputs are concatenated from element 0 of its plane ([channels][cap] as above); nothing is written at or
+ * beyond cap, though the state advances past it. counts[channel] is the channel's true total, range_counts[i] the outputs
+ * of ranges[i] (nullable); both are host arrays, do not depend on the data, and the device form returns them at once.
+ * Phase, filter histories and polyphase counters carry across a channel's ranges and across calls as they carry across a
+ * stop / restart; what lies between two ranges is dropped, as the Blocker drops it. Every range is bit-identical to its
+ * step of that sequence run through sc_process_device on d_iq + begin.
+ *   - ranges of one channel ascend and do not overlap (end_i <= begin_{i+1}); channels may interleave in any order
+ *   - begin == end is a no-op with range_counts[i] = 0
+ *   - nranges > SC_MAX_RANGES, a bad channel, begin > end or end > nsamples: SS_ERR_INVALID
+ *   - the two ways of driving a context are not mixed: refused (SS_ERR_INVALID) while any channel sc_is_recording; on
+ *     return no channel is recording
+ *   - the device form keeps sc_process_device's alignment rule for d_iq
+ *   - sc_output_capacity(ctx, nsamples) is a valid cap: a channel's total depends only on how many samples it saw
+ * Everything is validated before the first launch: a refused call changes nothing. */
+int sc_process_ranges(sc_ctx* ctx, const void* iq, int32_t nsamples, const sc_range* ranges, int32_t nranges, int8_t* out_i8, float* out_cf32,
+                      int32_t* counts, int32_t* range_counts, int32_t cap);
+int sc_process_ranges_device(sc_ctx* ctx, const void* d_iq, int32_t nsamples, const sc_range* ranges, int32_t nranges, int8_t* d_out_i8,
+                             float* d_out_cf32, int32_t* counts, int32_t* range_counts, int32_t cap);
+
 /* DataController::pushTransmission payload (data_controller.cpp:27-42): uint64 time ms, int32 start, int32 stop,
  * uint32 sample rate, then the samples as offset-binary bytes (int8 ^ 0x80). Host-side helper; returns the byte count
  * (out may be NULL to query it), or < 0 if cap is too small. */

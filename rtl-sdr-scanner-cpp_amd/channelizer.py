@@ -16,7 +16,8 @@ SC_MAX_CHANNELS = 16
 
 EXPORTS = ("sc_default_config", "sc_create", "sc_destroy", "sc_last_error", "sc_stage_count", "sc_stage_info", "sc_stage_taps",
            "sc_output_capacity", "sc_start", "sc_stop", "sc_is_recording", "sc_process", "sc_process_device", "sc_sync",
-           "sc_transmission_payload", "sc_set_input_format")
+           "sc_transmission_payload", "sc_set_input_format", "sc_process_ranges", "sc_process_ranges_device")
+SC_MAX_RANGES = 64
 
 # what process() / process_device() take for each input format (ss_format): integers interleaved re,im
 _NP_DTYPE = {abi.SS_FMT_CS8: np.int8, abi.SS_FMT_CU8: np.uint8, abi.SS_FMT_CS16: np.int16}
@@ -25,6 +26,16 @@ _NP_DTYPE = {abi.SS_FMT_CS8: np.int8, abi.SS_FMT_CU8: np.uint8, abi.SS_FMT_CS16:
 class ScConfig(C.Structure):  # sc_config
     _fields_ = [("abi_version", C.c_uint32), ("sample_rate", C.c_int32), ("bandwidth", C.c_int32), ("threshold", C.c_int32),
                 ("channels", C.c_int32), ("max_samples", C.c_int32), ("pack_scale", C.c_float), ("device_id", C.c_int32)]
+
+
+class ScRange(C.Structure):  # sc_range
+    _fields_ = [("channel", C.c_int32), ("shift_hz", C.c_int32), ("begin", C.c_int32), ("end", C.c_int32)]
+
+
+def _ranges(ranges):
+    """[(channel, shift_hz, begin, end), ...] or ScRange objects -> a C array of sc_range (None when empty)."""
+    rs = [r if isinstance(r, ScRange) else ScRange(*(int(v) for v in r)) for r in ranges]
+    return ((ScRange * len(rs))(*rs) if rs else None), len(rs)
 
 
 def _bind(lib):
@@ -49,6 +60,9 @@ def _bind(lib):
     lib.sc_process.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, i32p, C.c_int32]
     lib.sc_process_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, i32p, C.c_int32]
     lib.sc_sync.argtypes = [C.c_void_p]
+    if hasattr(lib, "sc_process_ranges"):  # (A/B builds of older trees, scripts/ab: measurement runs only)
+        lib.sc_process_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ScRange), C.c_int32, C.c_void_p, C.c_void_p, i32p, i32p, C.c_int32]
+        lib.sc_process_ranges_device.argtypes = lib.sc_process_ranges.argtypes
     lib.sc_set_input_format.argtypes = [C.c_void_p, C.c_int32, C.c_float]
     lib.sc_transmission_payload.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
     lib._sc_bound = True
@@ -174,6 +188,42 @@ class Channelizer:
         self._check(self._lib.sc_process_device(self._h, p(iq), int(nsamples), p(out_i8), p(out_cf32),
                                                 counts.ctypes.data_as(C.POINTER(C.c_int32)), int(cap)))
         return counts
+
+    def process_ranges(self, iq: np.ndarray, ranges, want_cf32: bool = True, cap: int | None = None):
+        """sc_process_ranges: iq as process() takes it; ranges = [(channel, shift_hz, begin, end), ...] in samples of iq.
+        Returns ({channel: (int8 [m, 2], complex64 [m] or None)} for every channel with a range, range_counts): a channel's
+        ranges concatenated, range_counts[i] outputs from ranges[i]. With cap below a channel's total only cap are kept."""
+        x, nsamples = self._host_input(iq)
+        arr, n = _ranges(ranges)
+        cap = max(self.output_capacity(nsamples), 1) if cap is None else int(cap)
+        nch = self.cfg.channels
+        i8 = np.zeros((nch, max(cap, 1), 2), np.int8)
+        cf = np.zeros((nch, max(cap, 1)), np.complex64) if want_cf32 else None
+        counts = np.zeros(nch, np.int32)
+        rc = np.zeros(max(n, 1), np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._check(self._lib.sc_process_ranges(self._h, x.ctypes.data, nsamples, arr, n, i8.ctypes.data, cf.ctypes.data if want_cf32 else None,
+                                                counts.ctypes.data_as(i32p), rc.ctypes.data_as(i32p), cap))
+        kept = np.minimum(counts, cap)
+        chans = sorted({int(arr[i].channel) for i in range(n)})
+        return ({ch: (i8[ch, :kept[ch]].copy(), cf[ch, :kept[ch]].copy() if want_cf32 else None) for ch in chans}, rc[:n].copy())
+
+    def process_ranges_device(self, iq, nsamples: int, ranges, out_i8=None, out_cf32=None, cap: int = 0):
+        """sc_process_ranges_device: tensors as process_device() takes them. Returns (counts, range_counts) (numpy); async: sync()."""
+        if iq is not None:
+            import torch
+            want = {abi.SS_FMT_CS8: (torch.int8,), abi.SS_FMT_CU8: (torch.uint8,), abi.SS_FMT_CS16: (torch.int16,)}.get(
+                self.in_format, (torch.float32, torch.complex64))
+            if iq.dtype not in want:
+                raise TypeError(f"input format {self.in_format} takes a {want[0]} tensor, not {iq.dtype}")
+        arr, n = _ranges(ranges)
+        counts = np.zeros(self.cfg.channels, np.int32)
+        rc = np.zeros(max(n, 1), np.int32)
+        i32p = C.POINTER(C.c_int32)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self._check(self._lib.sc_process_ranges_device(self._h, p(iq), int(nsamples), arr, n, p(out_i8), p(out_cf32),
+                                                       counts.ctypes.data_as(i32p), rc.ctypes.data_as(i32p), int(cap)))
+        return counts, rc[:n].copy()
 
     def sync(self):
         self._check(self._lib.sc_sync(self._h))

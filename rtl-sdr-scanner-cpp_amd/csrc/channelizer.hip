@@ -32,6 +32,7 @@
 
 #include "../../include/specscan.h"
 #include "../../include/specscan_channelizer.h"
+#include "chan_ranges.h"
 
 namespace {
 
@@ -166,6 +167,8 @@ struct Slot {
   double df = 0.0;                     // angle of the fp32 increment, in revolutions
   int ctr[SC_MAX_STAGES] = {};         // d_ctr of every resampler
   int skip[SC_MAX_STAGES] = {};        // input samples to pass before the next output's window ends
+  bool ptab_valid = false;             // d_ptab of this slot holds the table of ptab_df
+  double ptab_df = 0.0;
 };
 
 }  // namespace
@@ -234,6 +237,10 @@ struct ChanArgs {
   int slot[SC_MAX_CHANNELS];
   int ctr0[SC_MAX_CHANNELS], skip0[SC_MAX_CHANNELS], nin[SC_MAX_CHANNELS], nout[SC_MAX_CHANNELS];
   double f0[SC_MAX_CHANNELS], df[SC_MAX_CHANNELS];
+  // sc_process_ranges*: a slot's range of this launch is an address offset. in0 = its first raw sample in in_raw; out0 = the
+  // outputs it has already written to the caller's planes in this call. Everything else (tile numbering, n_lo, the phase,
+  // ptab and hist0 indices, the stage buffers) stays relative to the slot's own range. sc_process*: both zero.
+  int in0[SC_MAX_CHANNELS], out0[SC_MAX_CHANNELS];
 };
 
 // rotator phase of stream sample n of this call: exp(2*pi*i*(f0 + n*df)), the fraction reduced in fp64
@@ -272,8 +279,8 @@ __device__ __forceinline__ float2 raw_to_f2(typename RawIq<FMT>::T r, float s) {
 }
 
 template <int FMT>
-__device__ __forceinline__ float2 load_raw(const ChanArgs& a, int n) {
-  return raw_to_f2<FMT>(static_cast<const typename RawIq<FMT>::T*>(a.in_raw)[n], a.in_scale);
+__device__ __forceinline__ float2 load_raw(const ChanArgs& a, int s, int n) {  // sample n of slot s's range
+  return raw_to_f2<FMT>(static_cast<const typename RawIq<FMT>::T*>(a.in_raw)[a.in0[s] + n], a.in_scale);
 }
 
 // volk_32f_s32f_convert_8i: r = in * scalar; saturate to [-128, 127]; rintf (round to nearest even)
@@ -311,7 +318,7 @@ __global__ __launch_bounds__(256) void k_chan_stage(ChanArgs a) {
     float2 v;
     if (ROTATE) {
       if (n < 0) v = a.hist0[(size_t)slot * a.hist0_stride + (h + n)];
-      else v = rotate(load_raw<FMT>(a, n), phase_of(a.f0[s], a.df[s], n));
+      else v = rotate(load_raw<FMT>(a, s, n), phase_of(a.f0[s], a.df[s], n));
     } else {
       v = a.in_buf[(size_t)slot * a.in_stride + (h + n)];
     }
@@ -352,13 +359,14 @@ __global__ __launch_bounds__(256) void k_chan_stage(ChanArgs a) {
     y.y += part[3][o].y;
     const int m = m0 + o;
     if (a.next_buf) a.next_buf[(size_t)slot * a.next_stride + a.next_hist + m] = y;
-    if (m < a.cap) {
-      if (a.out_cf32) a.out_cf32[(size_t)slot * a.cap + m] = y;
+    const int mo = a.out0[s] + m;  // place in the caller's plane
+    if (mo < a.cap) {
+      if (a.out_cf32) a.out_cf32[(size_t)slot * a.cap + mo] = y;
       if (a.out_i8) {
         char2 v;
         v.x = to_i8(y.x, a.pack_scale);
         v.y = to_i8(y.y, a.pack_scale);
-        reinterpret_cast<char2*>(a.out_i8)[(size_t)slot * a.cap + m] = v;
+        reinterpret_cast<char2*>(a.out_i8)[(size_t)slot * a.cap + mo] = v;
       }
     }
   }
@@ -434,7 +442,7 @@ __device__ __forceinline__ void chan_dec_tile(const ChanArgs& a, float2* __restr
     using Raw = typename RawIq<FMT>::T;
     constexpr int U = LOGG == 6 ? 24 : 12;  // smaller tiles keep four waves per SIMD: fewer registers
     const int TPB = (int)blockDim.x;  // 64, 128 or 256: as many waves as the span leaves LDS for
-    const Raw* src = static_cast<const Raw*>(a.in_raw) + n_lo;
+    const Raw* src = static_cast<const Raw*>(a.in_raw) + a.in0[s] + n_lo;
     const float2 q = cmulf(P0, ptab[threadIdx.x]);
     if (FULL && span == U * TPB) {
       // the span of a full tile at D = 64 is exactly 24 samples per thread: no clamps, no predicates
@@ -523,9 +531,10 @@ __device__ __forceinline__ void chan_dec_tile(const ChanArgs& a, float2* __restr
       if (FULL || blk * R + r < tcount) {
         const float y = v[i];
         if (a.next_buf) reinterpret_cast<float*>(a.next_buf + (size_t)slot * a.next_stride + a.next_hist + m)[comp] = y;
-        if (m < a.cap) {
-          if (a.out_cf32) reinterpret_cast<float*>(a.out_cf32 + (size_t)slot * a.cap + m)[comp] = y;
-          if (a.out_i8) a.out_i8[((size_t)slot * a.cap + m) * 2 + comp] = to_i8(y, a.pack_scale);
+        const int mo = a.out0[s] + m;  // place in the caller's plane
+        if (mo < a.cap) {
+          if (a.out_cf32) reinterpret_cast<float*>(a.out_cf32 + (size_t)slot * a.cap + mo)[comp] = y;
+          if (a.out_i8) a.out_i8[((size_t)slot * a.cap + mo) * 2 + comp] = to_i8(y, a.pack_scale);
         }
       }
     }
@@ -565,7 +574,7 @@ __global__ __launch_bounds__(256) void k_chan_keep(ChanArgs a) {
     float2 v;
     if (ROTATE) {
       if (n < 0) v = a.hist0[(size_t)slot * a.hist0_stride + (h + n)];
-      else v = rotate(load_raw<FMT>(a, n), phase_of(a.f0[s], a.df[s], n));
+      else v = rotate(load_raw<FMT>(a, s, n), phase_of(a.f0[s], a.df[s], n));
     } else {
       v = a.in_buf[(size_t)slot * a.in_stride + (h + n)];
     }
@@ -576,18 +585,7 @@ __global__ __launch_bounds__(256) void k_chan_keep(ChanArgs a) {
   for (int i = threadIdx.x; i < h; i += 256) dst[i] = lds[i];
 }
 
-// outputs of one resampler for n_in new samples given its (ctr, skip), and the state after them
-int stage_outputs(int interp, int decim, int ctr, int skip, int n_in, int* ctr_after, int* skip_after) {
-  long long nout = 0;
-  if (n_in > skip) {
-    const long long need = (long long)(n_in - skip) * interp - ctr;  // smallest m with ctr + m*D >= (n_in - skip) * I
-    nout = need <= 0 ? 0 : (need + decim - 1) / decim;
-  }
-  const long long total = (long long)ctr + nout * decim;
-  *ctr_after = (int)(total % interp);
-  *skip_after = (int)((long long)skip + total / interp - n_in);
-  return (int)nout;
-}
+using chan_ranges::stage_outputs;  // outputs of one resampler for n_in new samples given its (ctr, skip), and the state after them
 
 void free_sc(sc_ctx* c) {
   if (!c) return;
@@ -634,17 +632,20 @@ void launch_first_stage(const sc_ctx* c, const Stage& st, const ChanArgs& a, int
   if (st.nt > 1) hipLaunchKernelGGL((k_chan_keep<true, FMT>), dim3((unsigned)a.nslots), dim3(256), sizeof(float2) * (size_t)(st.nt - 1), c->stream, a);
 }
 
-int run_stages(sc_ctx* c, const void* d_iq, int nsamples, int8_t* d_out_i8, float* d_out_cf32, int32_t* counts, int cap) {
+// One set of launches (one per stage plus the history updates): slot[s] takes the n_raw[s] > 0 samples of d_iq from in0[s] on and
+// appends its outputs to the caller's planes behind the out0[s] it has there already. produced[s] = its output count.
+int run_round(sc_ctx* c, const void* d_iq, int nslots, const int* slot, const int* in0, const int* n_raw, const int* out0, int8_t* d_out_i8,
+              float* d_out_cf32, int cap, int* produced) {
   const int nst = (int)c->stages.size();
   ChanArgs a{};
-  a.nslots = 0;
-  for (int ch = 0; ch < c->cfg.channels; ++ch) {
-    if (counts) counts[ch] = 0;
-    if (c->slots[ch].active) a.slot[a.nslots++] = ch;
-  }
-  if (a.nslots == 0 || nsamples == 0) return SS_OK;
+  a.nslots = nslots;
   int nin[SC_MAX_CHANNELS];
-  for (int s = 0; s < a.nslots; ++s) nin[s] = nsamples;
+  for (int s = 0; s < nslots; ++s) {
+    a.slot[s] = slot[s];
+    a.in0[s] = in0[s];
+    a.out0[s] = out0[s];
+    nin[s] = n_raw[s];
+  }
   for (int k = 0; k < nst; ++k) {
     Stage& st = c->stages[(size_t)k];
     const bool last = k == nst - 1;
@@ -704,11 +705,120 @@ int run_stages(sc_ctx* c, const void* d_iq, int nsamples, int8_t* d_out_i8, floa
   }
   for (int s = 0; s < a.nslots; ++s) {
     Slot& sl = c->slots[a.slot[s]];
-    double f = sl.f0 + (double)nsamples * sl.df;
+    double f = sl.f0 + (double)n_raw[s] * sl.df;
     sl.f0 = f - std::floor(f);
-    if (counts) counts[a.slot[s]] = nin[s];
+    produced[s] = nin[s];
   }
   SC_HIP(c, hipGetLastError());
+  return SS_OK;
+}
+
+int run_stages(sc_ctx* c, const void* d_iq, int nsamples, int8_t* d_out_i8, float* d_out_cf32, int32_t* counts, int cap) {
+  int nslots = 0, slot[SC_MAX_CHANNELS], zero[SC_MAX_CHANNELS] = {}, n_raw[SC_MAX_CHANNELS], produced[SC_MAX_CHANNELS];
+  for (int ch = 0; ch < c->cfg.channels; ++ch) {
+    if (counts) counts[ch] = 0;
+    if (c->slots[ch].active) {
+      n_raw[nslots] = nsamples;
+      slot[nslots++] = ch;
+    }
+  }
+  if (nslots == 0 || nsamples == 0) return SS_OK;
+  const int st = run_round(c, d_iq, nslots, slot, zero, n_raw, zero, d_out_i8, d_out_cf32, cap, produced);
+  if (st != SS_OK) return st;
+  for (int s = 0; s < nslots; ++s)
+    if (counts) counts[slot[s]] = produced[s];
+  return SS_OK;
+}
+
+// sc_start's arithmetic and its table: the slot's rotator increment for shift_hz. (recorder.cpp:64: set_phase_inc(2.0l * M_PIl *
+// (double(-shift) / float(sampleRate))) -> rotator_cc_impl::set_phase_inc(double): exp(gr_complex(0, phase_inc)) -> the angle
+// becomes a float; rotator::set_phase_incr divides by the magnitude.) The table is a function of df alone, so it is rebuilt
+// only when df is not the one it holds.
+int set_shift(sc_ctx* c, int channel, int shift_hz) {
+  Slot& sl = c->slots[channel];
+  const double ratio = (double)(-shift_hz) / (float)c->cfg.sample_rate;
+  const double phase_inc = (double)(2.0L * 3.141592653589793238462643383279502884L * (long double)ratio);
+  const float ang = (float)phase_inc;
+  const float re = cosf(ang), im = sinf(ang);
+  const float mag = hypotf(re, im);
+  sl.inc_re = re / mag;
+  sl.inc_im = im / mag;
+  sl.df = atan2((double)sl.inc_im, (double)sl.inc_re) / (2.0 * M_PI);  // what one multiplication by the fp32 increment turns the phase by
+  if (c->d_ptab && !(sl.ptab_valid && sl.ptab_df == sl.df)) {
+    SC_HIP(c, hipSetDevice(c->cfg.device_id));
+    const int n = (int)c->ptab_stride;
+    hipLaunchKernelGGL(k_chan_ptab, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_ptab + (size_t)channel * c->ptab_stride, n, sl.df);
+    SC_HIP(c, hipGetLastError());
+    sl.ptab_df = sl.df;
+    sl.ptab_valid = true;
+  }
+  return SS_OK;
+}
+
+// The body of sc_process_ranges*, device pointers, the context locked and the device set. Everything that can refuse the call
+// comes before the first launch and before any state is touched.
+int run_ranges(sc_ctx* c, const void* d_iq, int nsamples, const sc_range* ranges, int nranges, int8_t* d_out_i8, float* d_out_cf32, int32_t* counts,
+               int32_t* range_counts, int cap) {
+  if (const char* why = chan_ranges::validate(ranges, nranges, c->cfg.channels, nsamples)) return sc_fail(c, SS_ERR_INVALID, "%s", why);
+  for (int ch = 0; ch < c->cfg.channels; ++ch)
+    if (c->slots[ch].active) return sc_fail(c, SS_ERR_INVALID, "channel %d is recording (sc_start): ranges and start/stop are not mixed", ch);
+  chan_ranges::Plan plan;
+  chan_ranges::plan(ranges, nranges, &plan);
+  int written[SC_MAX_CHANNELS] = {};  // outputs of this call so far, per channel
+  for (int ch = 0; ch < c->cfg.channels; ++ch)
+    if (counts) counts[ch] = 0;
+  for (int r = 0; r < plan.nrounds; ++r) {
+    int nslots = 0, slot[SC_MAX_CHANNELS], in0[SC_MAX_CHANNELS], n_raw[SC_MAX_CHANNELS], out0[SC_MAX_CHANNELS], which[SC_MAX_CHANNELS], produced[SC_MAX_CHANNELS];
+    for (int i = plan.first[r]; i < plan.first[r + 1]; ++i) {
+      const sc_range& g = ranges[plan.order[i]];
+      if (range_counts) range_counts[plan.order[i]] = 0;
+      if (g.begin == g.end) continue;  // a no-op, as a sc_process of no samples is
+      const int st = set_shift(c, g.channel, g.shift_hz);
+      if (st != SS_OK) return st;
+      which[nslots] = plan.order[i];
+      slot[nslots] = g.channel;
+      in0[nslots] = g.begin;
+      n_raw[nslots] = g.end - g.begin;
+      out0[nslots] = written[g.channel];
+      ++nslots;
+    }
+    if (nslots == 0) continue;
+    const int st = run_round(c, d_iq, nslots, slot, in0, n_raw, out0, d_out_i8, d_out_cf32, cap, produced);
+    if (st != SS_OK) return st;
+    for (int s = 0; s < nslots; ++s) {
+      written[slot[s]] += produced[s];
+      if (range_counts) range_counts[which[s]] = produced[s];
+      if (counts) counts[slot[s]] = written[slot[s]];
+    }
+  }
+  return SS_OK;
+}
+
+// the host entry points' staging buffers: the stream, and planes of cap outputs per channel
+int host_staging(sc_ctx* c, int cap) {
+  if (!c->d_in) SC_HIP(c, hipMalloc(&c->d_in, sizeof(float2) * (size_t)c->cfg.max_samples));  // CF32-sized: a format switch never reallocates
+  if (cap > c->out_cap_alloc) {
+    (void)hipFree(c->d_out_i8);
+    (void)hipFree(c->d_out_cf32);
+    c->d_out_i8 = nullptr;
+    c->d_out_cf32 = nullptr;
+    c->out_cap_alloc = 0;
+    SC_HIP(c, hipMalloc(&c->d_out_i8, (size_t)2 * (size_t)cap * (size_t)c->cfg.channels));
+    SC_HIP(c, hipMalloc(&c->d_out_cf32, sizeof(float2) * (size_t)cap * (size_t)c->cfg.channels));
+    c->out_cap_alloc = cap;
+  }
+  return SS_OK;
+}
+
+// min(counts, cap) outputs per channel from the staging planes to the caller's, and the wait for them
+int host_results(sc_ctx* c, int8_t* out_i8, float* out_cf32, const int32_t* counts, int cap) {
+  for (int ch = 0; ch < c->cfg.channels; ++ch) {
+    const int n = counts[ch] < cap ? counts[ch] : cap;
+    if (n <= 0) continue;
+    if (out_i8) SC_HIP(c, hipMemcpyAsync(out_i8 + (size_t)2 * (size_t)cap * (size_t)ch, c->d_out_i8 + (size_t)2 * (size_t)cap * (size_t)ch, (size_t)2 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (out_cf32) SC_HIP(c, hipMemcpyAsync(out_cf32 + (size_t)2 * (size_t)cap * (size_t)ch, c->d_out_cf32 + (size_t)2 * (size_t)cap * (size_t)ch, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  }
+  SC_HIP(c, hipStreamSynchronize(c->stream));
   return SS_OK;
 }
 
@@ -888,24 +998,9 @@ int sc_start(sc_ctx* c, int32_t channel, int32_t shift_hz) {
   if (!c) return SS_ERR_INVALID;
   std::lock_guard<std::mutex> lock(c->mtx);
   if (channel < 0 || channel >= c->cfg.channels) return sc_fail(c, SS_ERR_INVALID, "channel %d out of range", channel);
-  Slot& sl = c->slots[channel];
-  // recorder.cpp:64: set_phase_inc(2.0l * M_PIl * (double(-shift) / float(sampleRate))) -> rotator_cc_impl::set_phase_inc(double):
-  // exp(gr_complex(0, phase_inc)) -> the angle becomes a float; rotator::set_phase_incr divides by the magnitude
-  const double ratio = (double)(-shift_hz) / (float)c->cfg.sample_rate;
-  const double phase_inc = (double)(2.0L * 3.141592653589793238462643383279502884L * (long double)ratio);
-  const float ang = (float)phase_inc;
-  const float re = cosf(ang), im = sinf(ang);
-  const float mag = hypotf(re, im);
-  sl.inc_re = re / mag;
-  sl.inc_im = im / mag;
-  sl.df = atan2((double)sl.inc_im, (double)sl.inc_re) / (2.0 * M_PI);  // what one multiplication by the fp32 increment turns the phase by
-  if (c->d_ptab) {
-    SC_HIP(c, hipSetDevice(c->cfg.device_id));
-    const int n = (int)c->ptab_stride;
-    hipLaunchKernelGGL(k_chan_ptab, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_ptab + (size_t)channel * c->ptab_stride, n, sl.df);
-    SC_HIP(c, hipGetLastError());
-  }
-  sl.active = true;
+  const int st = set_shift(c, channel, shift_hz);
+  if (st != SS_OK) return st;
+  c->slots[channel].active = true;
   return SS_OK;
 }
 
@@ -959,28 +1054,40 @@ int sc_process(sc_ctx* c, const void* iq, int32_t nsamples, int8_t* out_i8, floa
   if (nsamples < 0 || (nsamples > 0 && !iq) || cap < 0 || !counts) return sc_fail(c, SS_ERR_INVALID, "bad iq/nsamples/cap/counts");
   if (nsamples > c->cfg.max_samples) return sc_fail(c, SS_ERR_BATCH, "nsamples %d > max_samples %d", nsamples, c->cfg.max_samples);
   SC_HIP(c, hipSetDevice(c->cfg.device_id));
-  if (!c->d_in) SC_HIP(c, hipMalloc(&c->d_in, sizeof(float2) * (size_t)c->cfg.max_samples));  // CF32-sized: a format switch never reallocates
-  if (cap > c->out_cap_alloc) {
-    (void)hipFree(c->d_out_i8);
-    (void)hipFree(c->d_out_cf32);
-    c->d_out_i8 = nullptr;
-    c->d_out_cf32 = nullptr;
-    c->out_cap_alloc = 0;
-    SC_HIP(c, hipMalloc(&c->d_out_i8, (size_t)2 * (size_t)cap * (size_t)c->cfg.channels));
-    SC_HIP(c, hipMalloc(&c->d_out_cf32, sizeof(float2) * (size_t)cap * (size_t)c->cfg.channels));
-    c->out_cap_alloc = cap;
-  }
+  const int ready = host_staging(c, cap);
+  if (ready != SS_OK) return ready;
   if (nsamples > 0) SC_HIP(c, hipMemcpyAsync(c->d_in, iq, (size_t)SS_FMT_BYTES(c->in_format) * (size_t)nsamples, hipMemcpyHostToDevice, c->stream));
   const int st = run_stages(c, c->d_in, nsamples, out_i8 ? c->d_out_i8 : nullptr, out_cf32 ? c->d_out_cf32 : nullptr, counts, cap);
   if (st != SS_OK) return st;
-  for (int ch = 0; ch < c->cfg.channels; ++ch) {
-    const int n = counts[ch] < cap ? counts[ch] : cap;
-    if (n <= 0) continue;
-    if (out_i8) SC_HIP(c, hipMemcpyAsync(out_i8 + (size_t)2 * (size_t)cap * (size_t)ch, c->d_out_i8 + (size_t)2 * (size_t)cap * (size_t)ch, (size_t)2 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (out_cf32) SC_HIP(c, hipMemcpyAsync(out_cf32 + (size_t)2 * (size_t)cap * (size_t)ch, c->d_out_cf32 + (size_t)2 * (size_t)cap * (size_t)ch, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  }
-  SC_HIP(c, hipStreamSynchronize(c->stream));
-  return SS_OK;
+  return host_results(c, out_i8, out_cf32, counts, cap);
+}
+
+int sc_process_ranges_device(sc_ctx* c, const void* d_iq, int32_t nsamples, const sc_range* ranges, int32_t nranges, int8_t* d_out_i8,
+                             float* d_out_cf32, int32_t* counts, int32_t* range_counts, int32_t cap) {
+  if (!c) return SS_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (nsamples < 0 || (nsamples > 0 && !d_iq) || cap < 0) return sc_fail(c, SS_ERR_INVALID, "bad iq/nsamples/cap");
+  if (nsamples > c->cfg.max_samples) return sc_fail(c, SS_ERR_BATCH, "nsamples %d > max_samples %d", nsamples, c->cfg.max_samples);
+  if (c->in_format != SS_FMT_CF32 && reinterpret_cast<uintptr_t>(d_iq) % SS_FMT_BYTES(c->in_format) != 0)
+    return sc_fail(c, SS_ERR_INVALID, "d_iq is not aligned to the %d-byte sample", SS_FMT_BYTES(c->in_format));
+  SC_HIP(c, hipSetDevice(c->cfg.device_id));
+  return run_ranges(c, d_iq, nsamples, ranges, nranges, d_out_i8, d_out_cf32, counts, range_counts, cap);
+}
+
+int sc_process_ranges(sc_ctx* c, const void* iq, int32_t nsamples, const sc_range* ranges, int32_t nranges, int8_t* out_i8, float* out_cf32,
+                      int32_t* counts, int32_t* range_counts, int32_t cap) {
+  if (!c) return SS_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (nsamples < 0 || (nsamples > 0 && !iq) || cap < 0 || !counts) return sc_fail(c, SS_ERR_INVALID, "bad iq/nsamples/cap/counts");
+  if (nsamples > c->cfg.max_samples) return sc_fail(c, SS_ERR_BATCH, "nsamples %d > max_samples %d", nsamples, c->cfg.max_samples);
+  if (const char* why = chan_ranges::validate(ranges, nranges, c->cfg.channels, nsamples)) return sc_fail(c, SS_ERR_INVALID, "%s", why);  // before the upload
+  SC_HIP(c, hipSetDevice(c->cfg.device_id));
+  const int ready = host_staging(c, cap);
+  if (ready != SS_OK) return ready;
+  if (nsamples > 0 && nranges > 0) SC_HIP(c, hipMemcpyAsync(c->d_in, iq, (size_t)SS_FMT_BYTES(c->in_format) * (size_t)nsamples, hipMemcpyHostToDevice, c->stream));
+  const int st = run_ranges(c, c->d_in, nsamples, ranges, nranges, out_i8 ? c->d_out_i8 : nullptr, out_cf32 ? c->d_out_cf32 : nullptr, counts, range_counts, cap);
+  if (st != SS_OK) return st;
+  return host_results(c, out_i8, out_cf32, counts, cap);
 }
 
 int sc_transmission_payload(uint64_t time_ms, int32_t frequency, int32_t sample_rate, const int8_t* iq_i8, int32_t nsamples, uint8_t* out,

@@ -25,6 +25,7 @@
 #include "../../include/specscan.h"
 #include "../../include/specscan_track.h"
 #include "../../include/specscan_track_feed.h"
+#include "../../include/specscan_record_feed.h"
 #include "detect_fused.h"
 #include "detect_kernels.h"
 #include "fft1024_kernels.h"
@@ -3358,7 +3359,7 @@ struct ss_feed_slot {
   hipEvent_t ev_h2d = nullptr, ev_done = nullptr;
   int nframes = 0;
   int64_t tag = 0;
-  int state = 0;  // 0 free, 1 acquired (being filled), 2 submitted
+  int state = 0;  // 0 free, 1 acquired (being filled), 2 submitted, 3 collected and held for the recorder (srf_*)
 };
 
 struct ss_feed {
@@ -3369,12 +3370,15 @@ struct ss_feed {
   int next_acquire = 0, next_collect = 0, pending = 0, acquired = -1;
   hipStream_t copy_stream = nullptr, d2h_stream = nullptr;
   stf_ctx* tracker = nullptr;  // stf_create: every batch is digested behind its chain (include/specscan_track_feed.h)
+  srf_ctx* recorder = nullptr;  // srf_create: a collected slot stays held until its samples are recorded or let go (include/specscan_record_feed.h)
+  int held = -1;                // the held slot
 };
 
 namespace {
 // (the tracked feed, further down)
 int stf_enqueue(ss_feed* f, int slot, int nframes);
 void stf_feed_gone(stf_ctx* t);
+void srf_feed_gone(srf_ctx* t);
 int feed_collect(ss_feed* f, ss_feed_result* out, stf_result* digest);
 
 void feed_free(ss_feed* f) {
@@ -3451,6 +3455,7 @@ void ss_feed_destroy(ss_feed* f) {
     (void)hipStreamSynchronize(f->c->stream);
     (void)hipStreamSynchronize(f->d2h_stream);
     if (f->tracker) stf_feed_gone(f->tracker);
+    if (f->recorder) srf_feed_gone(f->recorder);
   }
   feed_free(f);
 }
@@ -3995,6 +4000,7 @@ int feed_collect(ss_feed* f, ss_feed_result* out, stf_result* digest) {
   {
     std::lock_guard<std::mutex> lock(c->mtx);
     if (f->tracker && !digest) return fail(c, SS_ERR_INVALID, "ss_feed_collect on a tracked feed: collect through stf_collect");
+    if (f->held >= 0) return fail(c, SS_ERR_INVALID, "the batch collected last is held for the recorder: srf_record or srf_release first");
     if (f->pending == 0) return fail(c, SS_ERR_INVALID, "ss_feed_collect: nothing pending");
     slot_no = f->next_collect;
     s = &f->slots[(size_t)slot_no];
@@ -4051,7 +4057,8 @@ int feed_collect(ss_feed* f, ss_feed_result* out, stf_result* digest) {
   out->cand_idx = s->h_idx;
   out->cand_avg = s->h_avg;
   out->psd_db = f->want_psd ? s->h_psd : nullptr;
-  s->state = 0;
+  s->state = f->recorder ? 3 : 0;  // held: its d_in is what srf_record reads
+  if (f->recorder) f->held = slot_no;
   f->next_collect = (f->next_collect + 1) % f->depth;
   --f->pending;
   return SS_OK;
@@ -4163,6 +4170,188 @@ int stf_reset(stf_ctx* t) {
   if (t->feed->pending > 0 || t->feed->acquired >= 0) return stf_fail(t, SS_ERR_INVALID, "stf_reset with batches pending: collect them first");
   if (hipSetDevice(c->cfg.device_id) != hipSuccess || stf_clear(t) != hipSuccess) return stf_fail(t, SS_ERR_HIP, "clearing the kept rows and marks failed: %s", hipGetErrorString(hipGetLastError()));
   t->rows.tail_cur = 0;
+  return SS_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The recorder bound to the feed (include/specscan_record_feed.h): a channeliser of its own, run on the held slot's upload.
+// The slot bookkeeping (ss_feed::held, ss_feed_slot::state 3) is the scan context's, under its mutex; the channeliser, its planes
+// and the pinned results are the recorder's, under rec_mtx, which is held for a whole srf_record so that the scan context's
+// mutex is not: a producer thread acquires and submits the other slots meanwhile. Lock order: rec_mtx, then the context's.
+struct srf_ctx {
+  ss_ctx* scan = nullptr;
+  ss_feed* feed = nullptr;  // null once the feed has been destroyed: only srf_destroy / srf_last_error from then on
+  srf_config cfg{};
+  char err[512] = "";
+  std::mutex rec_mtx;
+  sc_ctx* chan = nullptr;
+  hipStream_t stream = nullptr;  // the copies of the outputs, behind sc_sync
+  int cap = 0;
+  int8_t* d_i8 = nullptr;
+  float* d_cf32 = nullptr;
+  int8_t* h_i8 = nullptr;  // pinned
+  float* h_cf32 = nullptr;
+  int32_t* h_counts = nullptr;
+  int32_t* h_rc = nullptr;
+};
+
+namespace {
+
+thread_local char g_srf_create_err[512] = "";
+
+template <class... A>
+int srf_fail(srf_ctx* t, int status, const char* fmt, A... a) {
+  return fail_to(t ? t->err : g_srf_create_err, status, fmt, a...);
+}
+
+void srf_free(srf_ctx* t) {
+  if (!t) return;
+  if (t->chan) sc_destroy(t->chan);
+  (void)hipFree(t->d_i8);
+  (void)hipFree(t->d_cf32);
+  if (t->h_i8) (void)hipHostFree(t->h_i8);
+  if (t->h_cf32) (void)hipHostFree(t->h_cf32);
+  if (t->h_counts) (void)hipHostFree(t->h_counts);
+  if (t->h_rc) (void)hipHostFree(t->h_rc);
+  if (t->stream) (void)hipStreamDestroy(t->stream);
+  delete t;
+}
+
+void srf_feed_gone(srf_ctx* t) { t->feed = nullptr; }
+
+// the held slot goes back to the producer (the context's mutex is held)
+void srf_let_go(ss_feed* f) {
+  f->slots[(size_t)f->held].state = 0;
+  f->held = -1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srf_create(ss_feed* f, const srf_config* cfg, srf_ctx** out) {
+  if (!f || !cfg || !out) return srf_fail(nullptr, SS_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (cfg->abi_version != SRF_ABI_VERSION) return srf_fail(nullptr, SS_ERR_INVALID, "abi_version %u, library has %u", cfg->abi_version, SRF_ABI_VERSION);
+  ss_ctx* c = f->c;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (c->cfg.decim != 1)
+    return srf_fail(nullptr, SS_ERR_INVALID, "the scan context has decim %d: a decimated feed uploads only the frames the scan reads, there is no stream to record from", c->cfg.decim);
+  if (f->recorder) return srf_fail(nullptr, SS_ERR_INVALID, "the feed already has a recorder");
+  if (f->pending > 0 || f->acquired >= 0) return srf_fail(nullptr, SS_ERR_INVALID, "the feed has batches pending: collect them first");
+  const long long max_samples = (long long)c->cfg.max_batch * c->n;
+  if (max_samples > 0x7fffffffLL) return srf_fail(nullptr, SS_ERR_INVALID, "max_batch * N = %lld samples do not fit one channeliser call", max_samples);
+  srf_ctx* t = new (std::nothrow) srf_ctx();
+  if (!t) return srf_fail(nullptr, SS_ERR_NOMEM, "out of memory");
+  t->scan = c;
+  t->feed = f;
+  t->cfg = *cfg;
+  sc_config sc;
+  sc_default_config(&sc, c->cfg.sample_rate, cfg->bandwidth);
+  sc.threshold = cfg->threshold;
+  sc.channels = cfg->channels;
+  sc.max_samples = (int32_t)max_samples;
+  sc.pack_scale = cfg->pack_scale;
+  sc.device_id = c->cfg.device_id;
+  int st = sc_create(&sc, &t->chan);
+  if (st != SS_OK) {
+    srf_fail(nullptr, st, "sc_create: %s", sc_last_error(nullptr));
+    srf_free(t);
+    return st;
+  }
+  st = sc_set_input_format(t->chan, c->cfg.in_format, c->cfg.int_scale);
+  if (st != SS_OK) {
+    srf_fail(nullptr, st, "sc_set_input_format: %s", sc_last_error(t->chan));
+    srf_free(t);
+    return st;
+  }
+  t->cap = sc_output_capacity(t->chan, (int32_t)max_samples);
+  const size_t plane = (size_t)2 * (size_t)t->cap * (size_t)cfg->channels;
+  bool ok = hipSetDevice(c->cfg.device_id) == hipSuccess && hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) == hipSuccess;
+  ok = ok && hipMalloc(&t->d_i8, plane) == hipSuccess && hipHostMalloc((void**)&t->h_i8, plane, hipHostMallocDefault) == hipSuccess;
+  if (cfg->want_cf32) ok = ok && hipMalloc(&t->d_cf32, sizeof(float) * plane) == hipSuccess && hipHostMalloc((void**)&t->h_cf32, sizeof(float) * plane, hipHostMallocDefault) == hipSuccess;
+  ok = ok && hipHostMalloc((void**)&t->h_counts, sizeof(int32_t) * SC_MAX_CHANNELS, hipHostMallocDefault) == hipSuccess;
+  ok = ok && hipHostMalloc((void**)&t->h_rc, sizeof(int32_t) * SC_MAX_RANGES, hipHostMallocDefault) == hipSuccess;
+  if (!ok) {
+    const hipError_t e = hipGetLastError();
+    srf_free(t);
+    return srf_fail(nullptr, SS_ERR_NOMEM, "allocating the recorder's buffers failed: %s", hipGetErrorString(e));
+  }
+  f->recorder = t;
+  *out = t;
+  return SS_OK;
+}
+
+void srf_destroy(srf_ctx* t) {
+  if (!t) return;
+  {
+    std::lock_guard<std::mutex> rec(t->rec_mtx);
+    std::lock_guard<std::mutex> lock(t->scan->mtx);
+    if (t->feed) {
+      if (t->feed->held >= 0) srf_let_go(t->feed);  // (without a recorder nothing is held)
+      t->feed->recorder = nullptr;
+    }
+    (void)hipSetDevice(t->scan->cfg.device_id);
+    if (t->stream) (void)hipStreamSynchronize(t->stream);
+  }
+  srf_free(t);
+}
+
+const char* srf_last_error(const srf_ctx* t) { return t ? t->err : g_srf_create_err; }
+
+int srf_release(srf_ctx* t) {
+  if (!t) return SS_ERR_INVALID;
+  std::lock_guard<std::mutex> rec(t->rec_mtx);
+  std::lock_guard<std::mutex> lock(t->scan->mtx);
+  if (!t->feed) return srf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
+  if (t->feed->held < 0) return srf_fail(t, SS_ERR_INVALID, "no batch is held: collect one first");
+  srf_let_go(t->feed);
+  return SS_OK;
+}
+
+int srf_record(srf_ctx* t, const sc_range* ranges, int32_t nranges, srf_result* out) {
+  if (!t) return SS_ERR_INVALID;
+  if (!out || nranges < 0 || (nranges > 0 && !ranges)) return srf_fail(t, SS_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> rec(t->rec_mtx);
+  const void* d_in = nullptr;
+  int nsamples = 0;
+  {
+    std::lock_guard<std::mutex> lock(t->scan->mtx);
+    ss_feed* f = t->feed;
+    if (!f) return srf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
+    if (f->held < 0) return srf_fail(t, SS_ERR_INVALID, "no batch is held: collect one first");
+    const ss_feed_slot& s = f->slots[(size_t)f->held];
+    d_in = s.d_in;  // the collect has waited for the batch's chain, which waited for the upload
+    nsamples = s.nframes * t->scan->n;
+  }
+  const int nch = t->cfg.channels;
+  out->nsamples = nsamples;
+  out->cap = t->cap;
+  out->counts = t->h_counts;
+  out->range_counts = t->h_rc;
+  out->out_i8 = t->h_i8;
+  out->out_cf32 = t->cfg.want_cf32 ? t->h_cf32 : nullptr;
+  for (int ch = 0; ch < nch; ++ch) t->h_counts[ch] = 0;
+  if (nranges > 0) {
+    // the held slot is not acquired and not submitted to while it is held, so its d_in stands still without the context's lock
+    int st = sc_process_ranges_device(t->chan, d_in, nsamples, ranges, nranges, t->d_i8, t->d_cf32, t->h_counts, t->h_rc, t->cap);
+    if (st != SS_OK) return srf_fail(t, st, "%s", sc_last_error(t->chan));
+    st = sc_sync(t->chan);
+    if (st != SS_OK) return srf_fail(t, st, "%s", sc_last_error(t->chan));
+    hipError_t e = hipSetDevice(t->scan->cfg.device_id);
+    for (int ch = 0; ch < nch && e == hipSuccess; ++ch) {
+      const size_t n = (size_t)(t->h_counts[ch] < t->cap ? t->h_counts[ch] : t->cap), at = (size_t)2 * (size_t)t->cap * (size_t)ch;
+      if (n == 0) continue;
+      e = hipMemcpyAsync(t->h_i8 + at, t->d_i8 + at, 2 * n, hipMemcpyDeviceToHost, t->stream);
+      if (e == hipSuccess && t->cfg.want_cf32) e = hipMemcpyAsync(t->h_cf32 + at, t->d_cf32 + at, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, t->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+    if (e != hipSuccess) return srf_fail(t, SS_ERR_HIP, "copying the recorded samples failed: %s", hipGetErrorString(e));
+  }
+  std::lock_guard<std::mutex> lock(t->scan->mtx);
+  if (t->feed && t->feed->held >= 0) srf_let_go(t->feed);
   return SS_OK;
 }
 

@@ -229,6 +229,13 @@ class Feed:
         from .tracker import TrackedFeed
         return TrackedFeed(self, group_size, self._e.cfg.start_level if start_level is None else start_level, max_watch)
 
+    def record(self, bandwidth: int, channels: int = 4, **kw):
+        """A recorder bound to this feed (include/specscan_record_feed.h; the engine needs ``decim=1``): from now on a collected
+        batch stays held, its samples still on the device, until the returned object's ``record(ranges)`` has channelised sample
+        ranges of it or ``release()`` has let it go. ``threshold``, ``pack_scale``, ``want_cf32`` as recorder.RecordedFeed takes them."""
+        from .recorder import RecordedFeed
+        return RecordedFeed(self, bandwidth, channels, **kw)
+
     def __del__(self):
         try:
             self.close()

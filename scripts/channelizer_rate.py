@@ -1,9 +1,12 @@
 """Throughput of the recorder channeliser on HBM-resident input (sc_process_device), next to the VALU bound, per input format;
-with --host also sc_process from pageable host memory (the PCIe copy of the raw stream included).
+with --host also sc_process from pageable host memory (the PCIe copy of the raw stream included); with --ranges also
+sc_process_ranges_device with one whole-call range per slot (a twin context: ranges and start / stop are not mixed), which must
+cost what sc_process_device costs.
     python scripts/channelizer_rate.py [--fs 2048000] [--bw 32000] [--samples 8388608] [--slots 1 4 8]
-                                       [--format cf32 cs8 cu8 cs16] [--host] [--repeats 5] [--steps 20] [--host-steps 20]
-The formats are timed in alternation, --repeats rounds of --steps (device) / --host-steps (host) calls each; the medians of the
-rounds are reported."""
+                                       [--format cf32 cs8 cu8 cs16] [--host] [--ranges] [--lib PATH]
+                                       [--repeats 5] [--steps 20] [--host-steps 20]
+The formats are timed in alternation, --repeats rounds of --steps (device, ranges) / --host-steps (host) calls each; the medians
+of the rounds are reported. --lib: another build of the library (an A/B build of an older tree, say) instead of csrc/libspecscan.so."""
 import argparse
 import ctypes as C
 import json
@@ -16,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rtl_sdr_scanner_cpp_amd import abi as A  # noqa: E402
+from rtl_sdr_scanner_cpp_amd import engine  # noqa: E402
 from rtl_sdr_scanner_cpp_amd.channelizer import Channelizer  # noqa: E402
 
 FORMATS = {"cf32": (A.SS_FMT_CF32, np.float32), "cs8": (A.SS_FMT_CS8, np.int8), "cu8": (A.SS_FMT_CU8, np.uint8), "cs16": (A.SS_FMT_CS16, np.int16)}
@@ -39,22 +43,30 @@ def main():
     ap.add_argument("--slots", type=int, nargs="+", default=[1, 4, 8])
     ap.add_argument("--format", nargs="+", default=["cf32"], choices=list(FORMATS))
     ap.add_argument("--host", action="store_true", help="also time sc_process from pageable host memory")
+    ap.add_argument("--ranges", action="store_true", help="also time sc_process_ranges_device, one whole-call range per slot")
+    ap.add_argument("--lib", default=None, help="path of another build of libspecscan.so to measure")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--host-steps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
+    if a.lib:
+        engine.use_diag_library(os.path.abspath(a.lib))
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
     host = {f: _stream(a.samples, f, rng) for f in a.format}
     d_iq = {f: torch.from_numpy(host[f]).to(dev) for f in a.format}
     for nslots in a.slots:
-        ctx, d_i8, h_i8 = {}, {}, {}
+        ctx, ctx_r, d_i8, h_i8 = {}, {}, {}, {}
+        shifts = [int((k - nslots / 2) * 0.9 * a.fs / max(nslots, 2)) for k in range(nslots)]
+        whole = [(k, shifts[k], 0, a.samples) for k in range(nslots)]
         counts = np.zeros(nslots, np.int32)
         for f in a.format:
             ch = Channelizer(a.fs, a.bw, in_format=FORMATS[f][0], channels=nslots, max_samples=a.samples)
             for k in range(nslots):
-                ch.start(k, int((k - nslots / 2) * 0.9 * a.fs / max(nslots, 2)))
+                ch.start(k, shifts[k])
             ctx[f] = ch
+            if a.ranges:
+                ctx_r[f] = Channelizer(a.fs, a.bw, in_format=FORMATS[f][0], channels=nslots, max_samples=a.samples)
         cap = ctx[a.format[0]].output_capacity(a.samples)
         for f in a.format:
             d_i8[f] = torch.zeros((nslots, cap, 2), dtype=torch.int8, device=dev)
@@ -63,25 +75,31 @@ def main():
         def dev_call(f):
             ctx[f].process_device(d_iq[f], a.samples, d_i8[f], None, cap)
 
+        def ranges_call(f):
+            ctx_r[f].process_ranges_device(d_iq[f], a.samples, whole, d_i8[f], None, cap)
+
         def host_call(f):
             ch = ctx[f]
             ch._check(ch._lib.sc_process(ch._h, host[f].ctypes.data, a.samples, h_i8[f].ctypes.data, None,
                                          counts.ctypes.data_as(C.POINTER(C.c_int32)), cap))
 
         def timed(f, call, steps):
-            ctx[f].sync()
+            c = ctx_r[f] if call is ranges_call else ctx[f]
+            c.sync()
             t0 = time.perf_counter()
             for _ in range(steps):
                 call(f)
-            ctx[f].sync()
+            c.sync()
             return (time.perf_counter() - t0) / steps
 
-        kinds = [("device", dev_call, a.steps)] + ([("host", host_call, a.host_steps)] if a.host else [])
+        kinds = [("device", dev_call, a.steps)] + ([("ranges", ranges_call, a.steps)] if a.ranges else []) + ([("host", host_call, a.host_steps)] if a.host else [])
         for f in a.format:  # warm-up: code objects, staging buffers
             for _kind, call, _steps in kinds:
                 for _ in range(3):
                     call(f)
             ctx[f].sync()
+            if a.ranges:
+                ctx_r[f].sync()
         runs = {(f, kind): [] for f in a.format for kind, _, _ in kinds}
         for _ in range(a.repeats):  # alternating rounds
             for kind, call, steps in kinds:
@@ -97,11 +115,14 @@ def main():
                    "ms_per_call_runs": [round(t * 1e3, 4) for t in runs[(f, "device")]], "input_GSps": round(a.samples / dt / 1e9, 2),
                    "slot_GSps": round(a.samples * nslots / dt / 1e9, 2), "fir_TFLOPs": round(flops / dt / 1e12, 2),
                    "taps_per_input_sample": round(float(taps_per_in), 2)}
+            if a.ranges:
+                rt = float(np.median(runs[(f, "ranges")]))
+                rec.update(ranges_ms_per_call=round(rt * 1e3, 4), ranges_ms_per_call_runs=[round(t * 1e3, 4) for t in runs[(f, "ranges")]])
             if a.host:
                 ht = float(np.median(runs[(f, "host")]))
                 rec.update(host_ms_per_call=round(ht * 1e3, 4), host_ms_per_call_runs=[round(t * 1e3, 4) for t in runs[(f, "host")]])
             print(json.dumps(rec), flush=True)
-        for c in ctx.values():
+        for c in list(ctx.values()) + list(ctx_r.values()):
             c.close()
 
 

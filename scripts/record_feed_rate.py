@@ -1,0 +1,76 @@
+"""One batch recorded from the feed's own upload (srf_record) against the second-upload route (sc_process of the same samples from
+pageable host memory), both synchronous and with the int8 outputs back on the host.
+    python scripts/record_feed_rate.py [--fs 2048000] [--bw 32000] [--fft 8192] [--frames 1024] [--slots 4] [--format cf32 cs8]
+                                       [--repeats 9]
+Per format one JSON line: the medians of --repeats alternating calls, and their ratio."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import rtl_sdr_scanner_cpp_amd as pkg  # noqa: E402
+from rtl_sdr_scanner_cpp_amd import abi as A  # noqa: E402
+from rtl_sdr_scanner_cpp_amd.channelizer import Channelizer  # noqa: E402
+
+FORMATS = {"cf32": (A.SS_FMT_CF32, "frames_cf32"), "cs8": (A.SS_FMT_CS8, "frames_cs8"), "cu8": (A.SS_FMT_CU8, "frames_cu8"), "cs16": (A.SS_FMT_CS16, "frames_cs16")}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--fs", type=int, default=2_048_000)
+    ap.add_argument("--bw", type=int, default=32_000)
+    ap.add_argument("--fft", type=int, default=8192)
+    ap.add_argument("--frames", type=int, default=1024)
+    ap.add_argument("--slots", type=int, default=4)
+    ap.add_argument("--format", nargs="+", default=["cf32", "cs8"], choices=list(FORMATS))
+    ap.add_argument("--repeats", type=int, default=9)
+    a = ap.parse_args()
+    n, nsamples = a.fft, a.fft * a.frames
+    shifts = [int((k - a.slots / 2) * 0.9 * a.fs / max(a.slots, 2)) for k in range(a.slots)]
+    whole = [(k, shifts[k], 0, nsamples) for k in range(a.slots)]
+    for f in a.format:
+        fmt, frames = FORMATS[f]
+        tile = getattr(pkg.synth.SyntheticBand(n, seed=1), frames)(8)
+        batch = np.ascontiguousarray(np.concatenate([tile] * (a.frames // 8)))
+        eng = pkg.SpectrumEngine(a.fs, 145_000_000, fft_size=n, decim=1, max_batch=a.frames, in_format=fmt)
+        feed = eng.feed(depth=2, cand_cap=1 << 20)
+        rec = feed.record(a.bw, channels=a.slots)
+        ch = Channelizer(a.fs, a.bw, in_format=fmt, channels=a.slots, max_samples=nsamples)
+        for k in range(a.slots):
+            ch.start(k, shifts[k])
+        cap = ch.output_capacity(nsamples)
+        h_i8 = np.zeros((a.slots, cap, 2), np.int8)
+        counts = np.zeros(a.slots, np.int32)
+        t_feed, t_host, produced = [], [], 0
+        for it in range(a.repeats + 2):  # two warm-up rounds
+            feed.acquire()[:] = batch
+            feed.submit(a.frames)
+            feed.collect()
+            t0 = time.perf_counter()
+            out, rc = rec.record(whole)
+            t1 = time.perf_counter()
+            ch._check(ch._lib.sc_process(ch._h, batch.ctypes.data, nsamples, h_i8.ctypes.data, None, counts.ctypes.data_as(C.POINTER(C.c_int32)), cap))
+            t2 = time.perf_counter()
+            produced = int(rc.sum())
+            assert produced == int(counts.sum())
+            if it >= 2:
+                t_feed.append(t1 - t0)
+                t_host.append(t2 - t1)
+        mf, mh = float(np.median(t_feed)), float(np.median(t_host))
+        print(json.dumps({"fs": a.fs, "bw": a.bw, "format": f, "slots": a.slots, "samples": nsamples, "input_MB": round(batch.nbytes / 1e6, 1),
+                          "outputs": produced, "srf_record_ms": round(mf * 1e3, 4), "sc_process_ms": round(mh * 1e3, 4),
+                          "ratio_host_over_feed": round(mh / mf, 2), "srf_record_ms_runs": [round(t * 1e3, 4) for t in t_feed],
+                          "sc_process_ms_runs": [round(t * 1e3, 4) for t in t_host]}), flush=True)
+        rec.close()
+        feed.close()
+        ch.close()
+        eng.close()
+
+
+if __name__ == "__main__":
+    main()
