@@ -12,7 +12,7 @@ LIB = os.path.join(CSRC, "libspecscan.so")
 # Used by the A/B tests and the measurement scripts only; the product library never reads the environment.
 LIB_DIAG = os.path.join(CSRC, "libspecscan_diag.so")
 SOURCES = ["specscan.hip", "channelizer.hip"]
-HEADERS = ["fft_kernels.h", "fft8192_kernel.h", "fft8192_v2.h", "scan_step.h", "fft256_kernels.h", "detect_kernels.h", "detect_fused.h", "reference_nan.h", "fft1024_kernels.h", "ring_place.h",
+HEADERS = ["fft_kernels.h", "fft8192_kernel.h", "fft8192_v2.h", "scan_step.h", "fft256_kernels.h", "detect_kernels.h", "detect_fused.h", "reference_nan.h", "fft1024_kernels.h", "ring_place.h", "stage_slots.h",
            "track_digest.h", "track_digest_blocked.h", "track_feed.h", "chan_ranges.h", os.path.join("..", "..", "include", "specscan.h"), os.path.join("..", "..", "include", "specscan_channelizer.h"),
            os.path.join("..", "..", "include", "specscan_track.h"), os.path.join("..", "..", "include", "specscan_track_feed.h"), os.path.join("..", "..", "include", "specscan_record_feed.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC", "-shared", "-Wall", "-Wno-unused-result"]

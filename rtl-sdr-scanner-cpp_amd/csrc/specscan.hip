@@ -34,6 +34,7 @@
 #include "fft_kernels.h"
 #include "ring_place.h"
 #include "scan_step.h"
+#include "stage_slots.h"
 #include "track_digest.h"
 #include "track_digest_blocked.h"
 #include "track_feed.h"
@@ -302,31 +303,32 @@ struct ss_ctx {
   int ncnt = 3, nbuf = 1, npsd = 1, lag = 1;  // buffers in rotation: counters, mask / avg planes / offsets, internal PSD planes; launches between a call's stages
   float* d_relplane = nullptr;            // full rel plane, only when a caller asks for it (lazy)
   int last_n_learn = 0;
-  // Stage pipelining (8192 points, scan_step.h): the detect stage of the last call and the emit stage of the call before
-  // it are kept as arguments until the next launch carries them (or flush_stages drains them). Buffers a deferred stage
-  // reads while a later call already writes its own are doubled: mask bits, sparse avg plane, internal PSD plane.
+  // Stage pipelining (scan_step.h): the stages of the last calls are kept as arguments until a later launch carries them (or
+  // flush_stages drains them) — which stage waits for what, and the schedule of every form: stage_slots.h.
   bool step_path = false;
-  bool have_det = false, have_emit = false;
-  // 2^20 points in two passes: the plan of the last call (which of its tiles the detect stage must evaluate, k_plan_long) is not a
-  // launch of its own but rides at the front of the NEXT call's column launch (k_fft_cols1024_plan, detect_fused.h); until then
-  // — or until flush_stages launches it on its own — its arguments wait here. pend_det.tile_list points at the list it fills.
+  struct PendDet {
+    ss::DetectArgs a;  // (a.tile_list points at the list its plan fills)
+    int tiles;
+    ss::EmitArgs emit;  // the emit stage that follows it
+    long ready;  // deep pipelining: first launch that may carry it
+    bool spec;   // with the spectrogram branch (k_scan_step<..., SPEC = true>)
+  };
+  struct PendPlan {  // which tiles of a call the detect stage must evaluate (k_plan_long)
+    ss::PlanLongDet det;
+    ss::PlanLongArgs a;
+  };
+  struct PendRows {  // one launch per call: the row half that waits
+    ss::Rows256Args r256;
+    ss::Rows1024Args r1024;  // (262144 points, rows1024x256: the row stage that waits is one of 1024-point row tiles)
+    bool x1024;              // which of the two is filled
+    int tiles;
+  };
+  using Waiting = ss::StageSlots<PendDet, PendPlan, ss::EmitArgs, PendRows>;
+  Waiting wait;
   bool x256_tile = false;     // 262144 points: the row half through the 1024-point row tile (k_fft_rows1024_psd<8>) in every context, culled or not — the same bits either way
   bool rows1024x256 = false;  // 262144 points with tile culling (round 6): 256-point column tiles as k_scan_step's FFT role with the plan of the call before, detect(k - 2) and emit(k - 3); the rows as a launch of k_fft_rows1024_psd<8>
   bool rows256_step = false;  // 65536 points with tile culling: columns as their own launch, rows as k_scan_step's FFT role (see Diag::rows256_step)
-  bool have_plan = false;
-  ss::PlanLongDet pend_plan_det{};
-  ss::PlanLongArgs pend_plan{};
-  ss::DetectArgs pend_det{};
-  int pend_det_tiles = 0;
-  bool pend_det_spec = false;
-  ss::EmitArgs pend_det_emit{};  // the emit stage that follows pend_det
-  ss::EmitArgs pend_emit{};
-  // 65536 points with tile culling (det_lag2): a call's detect stage rides on the COLUMN launch two calls later — the longer of a
-  // call's two launches, where the quarter of a hundred workgroups that evaluate listed tiles (20 us apiece under the launch's
-  // streaming loads) end with the column tiles instead of being the row launch's tail — because the plan it needs rides on the
-  // column launch of the call in between. So two detect stages wait: pend_det (planned: rides on the next column launch) and
-  // pend_det2 (its plan is have_plan / pend_plan).
-  bool det_lag2 = false;
+  bool det_lag2 = false;      // a call's detect stage waits for its plan and rides on the column launch two calls later (the schedule headed DET_LAG2 in stage_slots.h)
   // 65536 points, int8 IQ (fft65536_dif8.h): calls that keep no plane go through the radix-8 fold — one launch of 8 x frames
   // workgroups (4 x frames since two residues share one) that leaves dB rows in the fold's BLOCKED order (32 Q bins per block,
   // fft65536_dif8.h: dif_bin_offset; ring_db_rows) in the averager ring's buffer and run maxima in the plan's layout 2; every other call (learning frames, planes handed out, stream-ordered contexts) takes the four-step form, whose rows
@@ -349,33 +351,12 @@ struct ss_ctx {
   const float* last_settled_hi = nullptr;  //     rows since (a retune or ss_reset_noise after the call) — ss_read_window must not subtract the ceiling twice
   float2* d_dif8_tab = nullptr;   // the fold's tables (dif8_host_tables)
   float* d_perm_tmp = nullptr;    // 35 rows: the window on its way from one order to the other
-  bool have_det2 = false;
-  ss::DetectArgs pend_det2{};
-  int pend_det2_tiles = 0;
-  bool pend_det2_spec = false;
-  ss::EmitArgs pend_det2_emit{};
   ss::RingPrev hist_prev{0, -1, 0};  // what the detect stage of the last call reads of the ring's buffer (ring_place.h)
   ss::RingPrev hist_prev2{0, -1, 0}; // ... of the call before it (merged contexts protect two)
-  // 65536 points, ONE launch per call (scan_step.h KIND 7; calls that keep no dB plane, up to 128 frames): the launch of call k carries
-  // the column half of call k, the ROW half of call k - 1 (two work buffers), the plan of call k - 2, detect(k - 3) and emit(k - 4).
-  // Waiting on the host besides pend_det / pend_det2 / pend_plan / pend_emit: the row stage of the last call, its plan (not ready
-  // before that row stage has run) and its detect stage.
-  bool merge = false;
+  bool merge = false;   // 65536 / 262144 points, ONE launch per call for calls that keep no dB plane (the schedule headed MERGED in stage_slots.h; two work buffers)
   int merge_max = 128;  // the largest call (frames) that is one launch
   float2* d_work2 = nullptr;
   int work_cur = 0;
-  bool have_rows = false;
-  ss::Rows256Args pend_rows{};
-  ss::Rows1024Args pend_rows1024{};  // (262144 points: the row stage that waits is one of 1024-point row tiles)
-  int pend_rows_tiles = 0;
-  bool have_plan2 = false;
-  ss::PlanLongDet pend_plan2_det{};
-  ss::PlanLongArgs pend_plan2{};
-  bool have_det3 = false;
-  ss::DetectArgs pend_det3{};
-  int pend_det3_tiles = 0;
-  bool pend_det3_spec = false;
-  ss::EmitArgs pend_det3_emit{};
   int buf_cur = 0;               // which of the rotating buffers the NEXT batch writes
   int psd_cur = 0;
   // Deep pipelining (8192 points; diag.deep). With the stages of three consecutive calls in one
@@ -413,13 +394,6 @@ struct ss_ctx {
   // written again while it runs, and nobody has to wait for it.
   bool deep_ring_safe = false;
   unsigned deep_forks = 0;
-  struct PendDet {
-    ss::DetectArgs a;
-    int tiles;
-    ss::EmitArgs emit;
-    long ready;  // first launch that may carry it
-    bool spec;   // with the spectrogram branch (k_scan_step<..., SPEC = true>)
-  };
   struct PendEmit {
     ss::EmitArgs a;
     long ready;
@@ -738,16 +712,17 @@ void launch_cols1024_fmt(ss_ctx* c, const void* d_iq, long long item_stride, int
     else hipLaunchKernelGGL(kernel, dim3(nframes * tiles), dim3(threads), lds, c->stream, g);
   };
   const bool wcalc = g.wtab != nullptr;
-  if (c->have_plan && c->diag.cols1024_wide) {  // the plan of the call before at the front of this launch (detect_fused.h)
-    const int plan_wgs = ss::plan_fused_wgs(ss::plan_long_blocks(c->pend_plan.layout, c->pend_plan.cols, c->n));
+  if (c->wait.plan_ready.have && c->diag.cols1024_wide) {  // the plan of the call before at the front of this launch (detect_fused.h)
+    const ss_ctx::PendPlan& plan = c->wait.plan_ready.v;
+    const int plan_wgs = ss::plan_fused_wgs(ss::plan_long_blocks(plan.a.layout, plan.a.cols, c->n));
     const dim3 grid((unsigned)(plan_wgs + nframes * 64)), block(1024);
     auto gop = [&](auto kernel) {
-      if (e0) hipExtLaunchKernelGGL(kernel, grid, block, ss::fft1024_cols_lds_bytes(4), c->stream, e0, e1, 0, g, c->pend_plan_det, c->pend_plan, plan_wgs);
-      else hipLaunchKernelGGL(kernel, grid, block, ss::fft1024_cols_lds_bytes(4), c->stream, g, c->pend_plan_det, c->pend_plan, plan_wgs);
+      if (e0) hipExtLaunchKernelGGL(kernel, grid, block, ss::fft1024_cols_lds_bytes(4), c->stream, e0, e1, 0, g, plan.det, plan.a, plan_wgs);
+      else hipLaunchKernelGGL(kernel, grid, block, ss::fft1024_cols_lds_bytes(4), c->stream, g, plan.det, plan.a, plan_wgs);
     };
     if (wcalc) gop(ss::k_fft_cols1024_plan<FMT, true>);
     else gop(ss::k_fft_cols1024_plan<FMT, false>);
-    c->have_plan = false;
+    c->wait.plan_ready.have = false;
     return;
   }
   if (c->diag.cols1024_wide && wcalc) go(ss::k_fft_cols1024<FMT, 4, true>, 64, 1024, ss::fft1024_cols_lds_bytes(4));
@@ -1008,10 +983,14 @@ struct FftRole {
   int n_halo = 0;
 };
 
-// fft / det / emit: null = role absent. Start/stop events ride on launches that carry an FFT role (the dominant work).
-void launch_step(ss_ctx* c, const FftRole* fft, const ss::DetectArgs* det, int n_det_tiles, bool spec, const ss::EmitArgs* emit, hipStream_t stream = nullptr,
-                 bool with_long_plan = false, const ss::Rows256Args* rows_role = nullptr, int n_rows = 0, const ss::Rows1024Args* rows1024_role = nullptr) {
+// fft: null = role absent; `ride`: the waiting stages this launch carries (ss_ctx::Waiting::riding, or the deep path's own). Start/stop
+// events ride on launches that carry an FFT role (the dominant work).
+void launch_step(ss_ctx* c, const FftRole* fft, const ss_ctx::Waiting::Riders& ride, hipStream_t stream = nullptr) {
   if (!stream) stream = c->stream;
+  const ss::DetectArgs* det = ride.det ? &ride.det->a : nullptr;
+  const int n_det_tiles = ride.det ? ride.det->tiles : 0;
+  const bool spec = ride.det && ride.det->spec;
+  const ss::EmitArgs* emit = ride.emit;
 #ifdef SS_DIAG
   if (c->diag.ablate_roles & 1) det = nullptr;
   if (c->diag.ablate_roles & 2) emit = nullptr;
@@ -1075,18 +1054,17 @@ void launch_step(ss_ctx* c, const FftRole* fft, const ss::DetectArgs* det, int n
     a.emit = *emit;
     a.n_emit = emit->nframes;
   }
-  if (rows_role && n_rows > 0) {  // one launch per call (KIND 7): the row half of the call before beside this call's column half
-    a.rows256 = *rows_role;
-    a.n_rows = n_rows;
-  } else if (rows1024_role && n_rows > 0) {  // ... of 262144-point frames (KIND 12)
-    a.rows = *rows1024_role;
-    a.n_rows = n_rows;
+  if (ride.rows && ride.rows->tiles > 0) {  // one launch per call: the row half of the call before beside this call's column half
+    if (ride.rows->x1024) a.rows = ride.rows->r1024;  // (262144-point frames, KIND 12)
+    else a.rows256 = ride.rows->r256;                // (KIND 7)
+    a.n_rows = ride.rows->tiles;
   }
-  if (with_long_plan && c->have_plan) {  // 65536 points: the plan of the call before as a role of this (column) launch
-    a.plan_det = c->pend_plan_det;
-    a.plan_long = c->pend_plan;
-    a.n_plan_long = (ss::plan_blocks_of(c->pend_plan_det, c->pend_plan, c->n) + 1) / 2;
-    c->have_plan = false;
+  if (ride.plan && c->wait.plan_ready.have) {  // 65536 points: the plan of the call before as a role of this (column) launch
+    const ss_ctx::PendPlan& plan = c->wait.plan_ready.v;
+    a.plan_det = plan.det;
+    a.plan_long = plan.a;
+    a.n_plan_long = (ss::plan_blocks_of(plan.det, plan.a, c->n) + 1) / 2;
+    c->wait.plan_ready.have = false;
   }
   if (ss::step_items(a) == 0) return;
   a.wait_limit = c->wait_limit;
@@ -1217,7 +1195,7 @@ void drain_deep(ss_ctx* c) {
         ee = *e;
         c->pe.erase(e);
       }
-      launch_step(c, nullptr, has_det ? &dd.a : nullptr, dd.tiles, dd.spec, has_emit ? &ee.a : nullptr, q);
+      launch_step(c, nullptr, {has_det ? &dd : nullptr, has_emit ? &ee.a : nullptr}, q);
       if (has_det) c->pe.push_back(ss_ctx::PendEmit{dd.emit, dd.ready});
     }
   }
@@ -1276,70 +1254,31 @@ void launch_nan_stage(ss_ctx* c, const NanStage& g) {
   hipLaunchKernelGGL(ss::k_nan_apply, dim3(g.nframes), dim3(256), 0, c->stream, (const int*)c->d_bad_from, c->n, g.maskbits, g.counts, g.avg_full);
 }
 
-// The plan of the last call as a launch of its own (it would have ridden on the next call's column launch, ss_ctx::have_plan).
-void launch_pending_plan(ss_ctx* c) {
-  if (!c->have_plan) return;
-  const int plan_wgs = ss::plan_blocks_of(c->pend_plan_det, c->pend_plan, c->n);  // (groups past the band's end find no column)
-  hipLaunchKernelGGL((ss::k_plan_long<21, 21, kFusedTF, 256>), dim3(plan_wgs), dim3(256), 0, c->stream, c->pend_plan_det, c->pend_plan);
-  c->have_plan = false;
-}
-
-// A launch has carried the planned detect stage and the emit stage that waited: the detect stage's emit waits now, and the detect
-// stage whose plan has run (det_lag2 contexts; none elsewhere) is the planned one.
-void shift_pending(ss_ctx* c) {
-  c->have_emit = c->have_det;
-  c->pend_emit = c->pend_det_emit;
-  c->have_det = c->have_det2;
-  if (c->have_det2) {
-    c->pend_det = c->pend_det2;
-    c->pend_det_tiles = c->pend_det2_tiles;
-    c->pend_det_spec = c->pend_det2_spec;
-    c->pend_det_emit = c->pend_det2_emit;
-    c->have_det2 = false;
-  }
-  // one launch per call: the row stage that waited has run — the detect stage behind it waits for its plan now, and that plan is ready
-  if (c->have_det3) {
-    c->have_det2 = true;
-    c->pend_det2 = c->pend_det3;
-    c->pend_det2_tiles = c->pend_det3_tiles;
-    c->pend_det2_spec = c->pend_det3_spec;
-    c->pend_det2_emit = c->pend_det3_emit;
-    c->have_det3 = false;
-  }
-  if (c->have_plan2) {  // (launch_step took the ready plan, if there was one)
-    c->have_plan = true;
-    c->pend_plan = c->pend_plan2;
-    c->pend_plan_det = c->pend_plan2_det;
-    c->have_plan2 = false;
-  }
-  c->have_rows = false;
-}
-
 // Drain the deferred stages: detect (+ the emit stage before it), then the last emit. Nothing is synchronised.
 void flush_stages(ss_ctx* c) {
   if (c->deep) {
     if (c->deep_L > 0 || !c->pd.empty() || !c->pe.empty()) ++c->stats.drains;
     return drain_deep(c);
   }
-  if (c->have_det || c->have_det2 || c->have_det3 || c->have_emit || c->have_rows) ++c->stats.drains;
-  if (c->have_rows || c->have_plan2 || c->have_det3) {
-    // one launch per call (KIND 7): row stage, ready plan, planned detect stage and emit stage of four different calls per launch until
-    // nothing waits (a plan is a ROLE of these launches: a launch boundary orders it ahead of the detect stage it plans)
-    while (c->have_rows || c->have_plan || c->have_plan2 || c->have_det || c->have_det2 || c->have_det3 || c->have_emit) {
-      launch_step(c, nullptr, c->have_det ? &c->pend_det : nullptr, c->pend_det_tiles, c->pend_det_spec, c->have_emit ? &c->pend_emit : nullptr, nullptr, true,
-                  (c->have_rows && !c->rows1024x256) ? &c->pend_rows : nullptr, c->have_rows ? c->pend_rows_tiles : 0, (c->have_rows && c->rows1024x256) ? &c->pend_rows1024 : nullptr);
-      shift_pending(c);
-    }
-    return;
+  using W = ss_ctx::Waiting;
+  W& w = c->wait;
+  if (w.det_planned.have || w.det_wants_plan.have || w.det_wants_rows.have || w.emit.have || w.rows.have) ++c->stats.drains;
+  // Stages that wait for a row stage (one launch per call): row stage, ready plan, planned detect stage and emit stage of four different
+  // calls per launch — a plan is a ROLE of these launches, a launch boundary orders it ahead of the detect stage it plans. Otherwise the
+  // ready plan (it would have ridden on the next call's column launch) goes first, as a launch of its own, and none becomes ready behind it.
+  if (!w.any_merged() && w.plan_ready.have) {
+    const ss_ctx::PendPlan& plan = w.plan_ready.v;
+    const int plan_wgs = ss::plan_blocks_of(plan.det, plan.a, c->n);  // (groups past the band's end find no column)
+    hipLaunchKernelGGL((ss::k_plan_long<21, 21, kFusedTF, 256>), dim3(plan_wgs), dim3(256), 0, c->stream, plan.det, plan.a);
+    w.plan_ready.have = false;
   }
-  launch_pending_plan(c);  // (the detect stage that waits reads its list)
-  while (c->have_det || c->have_det2 || c->have_emit) {
-    launch_step(c, nullptr, c->have_det ? &c->pend_det : nullptr, c->pend_det_tiles, c->pend_det_spec, c->have_emit ? &c->pend_emit : nullptr);
-    if (c->have_det && c->ref_nan) {  // (such contexts never defer a stage across calls: no emit stage rode on that launch)
+  while (w.any()) {
+    launch_step(c, nullptr, w.riding(W::ALL));
+    if (w.det_planned.have && c->ref_nan) {  // (such contexts never defer a stage across calls: no emit stage rode on that launch)
       launch_nan_stage(c, c->nan_pending);
       c->nan_pending = NanStage{};
     }
-    shift_pending(c);
+    w.shift();
   }
 }
 
@@ -1350,7 +1289,7 @@ int launch_fft_fmt(ss_ctx* c, const void* d_iq, long long item_stride, int nfram
     FftRole role;
     role.frames = &g;
     role.n = nframes;
-    launch_step(c, &role, nullptr, 0, false, nullptr);
+    launch_step(c, &role, {});
     return SS_OK;
   }
   switch (c->logn) {
@@ -1524,8 +1463,7 @@ RingPlace place_ring(ss_ctx* c, int nframes) {
 }
 
 int run_backend_fused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, NoiseState* z, SpecState* spec, float* d_rel_out,
-                      float* d_avg_out, int32_t* d_cand_off, int32_t* d_cand_idx, float* d_cand_avg, int cand_cap, bool deferred,
-                      ss::DetectArgs* det_out, int* det_tiles_out, ss::EmitArgs* emit_out) {
+                      float* d_avg_out, int32_t* d_cand_off, int32_t* d_cand_idx, float* d_cand_avg, int cand_cap, ss_ctx::PendDet* deferred) {
   const int n = c->n;
   constexpr int G = 21, GX = 21, TF = kFusedTF, TB = 256;  // measured against 32-frame and 128-bin tiles: 16 x 256 is fastest
   constexpr int H = kHistRows;
@@ -1618,10 +1556,11 @@ int run_backend_fused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, N
     ns.counts = counts;
     ns.avg_full = avg_full;
   }
-  if (deferred) {
-    *det_out = da;
-    *det_tiles_out = tiles;
-    *emit_out = ea;
+  if (deferred) {  // the caller's slot takes the two stages instead of the stream
+    deferred->a = da;
+    deferred->tiles = tiles;
+    deferred->emit = ea;
+    deferred->spec = spec != nullptr;
     c->nan_pending = ns;  // (flush_stages puts it between the two)
     return SS_OK;
   }
@@ -1814,7 +1753,7 @@ int run_call_deep(ss_ctx* c, const void* d_iq, long long item_stride, int nframe
       has_emit = true;
     }
   }
-  launch_step(c, &role, has_det ? &d.a : nullptr, d.tiles, d.spec, has_emit ? &e.a : nullptr, q);
+  launch_step(c, &role, {has_det ? &d : nullptr, has_emit ? &e.a : nullptr}, q);
 #ifdef SS_DIAG
   c->diag.canary_prev_slot = -1;
   if (overlap && c->diag.d_canary && nframes >= kHistRows && c->diag.canary_pairs.size() < 60) {
@@ -1836,8 +1775,7 @@ int run_call_deep(ss_ctx* c, const void* d_iq, long long item_stride, int nframe
     if (c->cull || c->cull_long) hipLaunchKernelGGL(ss::k_thr_tilemin, dim3(c->n / 256), dim3(64), 0, c->stream, (const float*)z->d_thr, c->n, z->d_thr + c->n);
   }
   ss_ctx::PendDet mine_det{};
-  st = run_backend_fused(c, d_psd, nframes, n_learn, z, nullptr, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg, cand_cap, true,
-                         &mine_det.a, &mine_det.tiles, &mine_det.emit);
+  st = run_backend_fused(c, d_psd, nframes, n_learn, z, nullptr, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg, cand_cap, &mine_det);
   if (st != SS_OK) return st;
   if (role.n_halo) {
     mine_det.a.halo_psd = role.halo_psd;
@@ -2030,12 +1968,14 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
       const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
       return a && b && pa < pb + bbytes && pb < pa + abytes;
     };
-    const auto clashes = [&](const ss::DetectArgs& pd, const ss::EmitArgs& pe) {
-      const size_t pend_bytes = sizeof(float) * (size_t)pd.nframes * (size_t)c->n;
-      return clash(d_psd, plane_bytes, pd.psd, pend_bytes) || clash(d_avg_out, plane_bytes, pe.avg, pend_bytes) || clash(d_psd, plane_bytes, pd.rel_out, pend_bytes) ||
-             clash(d_rel_out, plane_bytes, pd.psd, pend_bytes);
+    const auto clashes = [&](const ss_ctx::PendDet& p) {
+      const size_t pend_bytes = sizeof(float) * (size_t)p.a.nframes * (size_t)c->n;
+      return clash(d_psd, plane_bytes, p.a.psd, pend_bytes) || clash(d_avg_out, plane_bytes, p.emit.avg, pend_bytes) || clash(d_psd, plane_bytes, p.a.rel_out, pend_bytes) ||
+             clash(d_rel_out, plane_bytes, p.a.psd, pend_bytes);
     };
-    const bool reused = (c->have_det && clashes(c->pend_det, c->pend_det_emit)) || (c->have_det2 && clashes(c->pend_det2, c->pend_det2_emit));
+    using W = ss_ctx::Waiting;
+    W& w = c->wait;
+    const bool reused = (w.det_planned.have && clashes(w.det_planned.v)) || (w.det_wants_plan.have && clashes(w.det_wants_plan.v));  // (a detect stage that waits for its rows keeps no plane)
     if (!overlap || reused) flush_stages(c);
     const bool rows_by_step = (c->two_pass && c->diag.cols1024_wide) || c->rows256_step || c->rows1024x256;
     // one launch per call (SS_MERGE_65536): calls that keep no dB plane, in one piece, with stages allowed to overlap; any other call
@@ -2043,7 +1983,7 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
     // (up to 128 frames: two 64 MiB work buffers in flight are what the Infinity Cache holds beside the rest — 256-frame calls lose a tenth
     // this way and have two rounds of workgroups per launch anyway, profiles/r04/s34_summary.txt)
     const bool merged_call = c->merge && (c->rows256_step || c->rows1024x256) && overlap && ring_only && !spec && nframes <= c->merge_max;
-    if (c->merge && !merged_call && (c->have_rows || c->have_plan2 || c->have_det3)) flush_stages(c);
+    if (c->merge && !merged_call && w.any_merged()) flush_stages(c);
     if (dif_call) {
       if (!ring_only || !rx.hist_out) return fail(c, SS_ERR_INVALID, "internal: a fold call without a place for its rows");
       ss::Fft8192Args gf{};
@@ -2066,24 +2006,18 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
       const bool single = c->dif_logq == 3 && nframes <= c->diag.dif8_single_max;
       drole.n = (c->dif_logq == 4 || single ? 8 : SS_DIF8_W) * nframes;
       // the plan of the call before, the planned detect stage (of the call before that) and the emit stage behind it ride on the launch
-      launch_step(c, &drole, c->have_det ? &c->pend_det : nullptr, c->pend_det_tiles, c->pend_det_spec, c->have_emit ? &c->pend_emit : nullptr, nullptr, true);
+      launch_step(c, &drole, w.riding(W::DET | W::EMIT | W::PLAN));
     } else if (merged_call) {
       ss::ColsArgs gcm = gc;
       gcm.work = c->work_cur ? c->d_work2 : c->d_work;
       FftRole crole;
       crole.cols = &gcm;
       crole.n = nframes * (c->n >> 13);
-      launch_step(c, &crole, c->have_det ? &c->pend_det : nullptr, c->pend_det_tiles, c->pend_det_spec, c->have_emit ? &c->pend_emit : nullptr, nullptr, true,
-                  (c->have_rows && !c->rows1024x256) ? &c->pend_rows : nullptr, c->have_rows ? c->pend_rows_tiles : 0, (c->have_rows && c->rows1024x256) ? &c->pend_rows1024 : nullptr);
+      launch_step(c, &crole, w.riding(W::ALL));
     } else if (c->rows256_step) {
-      // 65536 points with tile culling: both halves of the FFT as FFT roles of k_scan_step, the deferred stages shared out between
-      // them — the column launch of call k carries the plan of call k - 1 (which of its tiles the detect stage must evaluate) and
-      // emit(k - 2), the row launch right behind it detect(k - 1) on the tiles that plan listed. (All of them on the row launch:
-      // 29.5 us for a launch that takes 17 alone; on the column launch the plan would have to be a launch of its own between the
-      // two, 6.5 us: profiles/r04/s17_summary.txt.)
-      // det_lag2 (what ships): the planned detect stage — detect(k - 2), whose plan rode on the column launch of call k - 1 — rides on
-      // the COLUMN launch as well, and the row launch carries nothing: a workgroup that evaluates a pair of tiles lives ~20 us under
-      // the streaming loads of its neighbours, longer than the row launch (17 us) and shorter than the column launch (24).
+      // 65536 points with tile culling: both halves of the FFT as FFT roles of k_scan_step. What ships (det_lag2, stage_slots.h): plan,
+      // planned detect stage and emit stage on the column launch, nothing on the row launch. SS_DET_LAG2=0: plan and emit stage on the
+      // column launch, the detect stage on the row launch (29.5 us for a launch that takes 17 alone: profiles/r04/s17_summary.txt).
       const bool det_on_cols = c->det_lag2;
 #ifdef SS_DIAG
       const bool emit_on_rows = c->diag.emit_on_rows;
@@ -2104,8 +2038,7 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
         FftRole crole;
         crole.cols = &gcc;
         crole.n = nf * (c->n >> 13);
-        launch_step(c, &crole, (first && det_on_cols && c->have_det) ? &c->pend_det : nullptr, c->pend_det_tiles, c->pend_det_spec,
-                    (first && !emit_on_rows && c->have_emit) ? &c->pend_emit : nullptr, nullptr, first);
+        launch_step(c, &crole, w.riding(first ? W::PLAN | (det_on_cols ? W::DET : 0) | (emit_on_rows ? 0 : W::EMIT) : 0));
         ss::RowsExtra rxc = rx;
         rxc.abs0 += f0;
         rxc.first_hist -= f0;                 // (hist_out takes the call's frames >= first_hist; the tile sees chunk-local frame numbers)
@@ -2114,13 +2047,11 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
         FftRole rrole;
         rrole.rows256 = &gr;
         rrole.n = nf * 8;
-        launch_step(c, &rrole, (first && !det_on_cols && c->have_det) ? &c->pend_det : nullptr, c->pend_det_tiles, c->pend_det_spec,
-                    (first && emit_on_rows && c->have_emit) ? &c->pend_emit : nullptr);
+        launch_step(c, &rrole, w.riding(first ? (det_on_cols ? 0 : W::DET) | (emit_on_rows ? W::EMIT : 0) : 0));
       }
     } else if (c->rows1024x256) {
-      // 262144 points (round 6): the 65536-point two-launch pipeline — the column launch of call k (256-point column tiles as k_scan_step's
-      // FFT role) carries the plan of call k - 1, detect(k - 2) on the tiles that plan listed and emit(k - 3); the row half is a launch of
-      // k_fft_rows1024_psd<8> that carries nothing. Calls of more than 64 frames go through in chunks (a chunk's work buffer: 128 MiB).
+      // 262144 points (round 6): the 65536-point two-launch pipeline (256-point column tiles as k_scan_step's FFT role); the row half is a launch
+      // of k_fft_rows1024_psd<8> that carries nothing. Calls of more than 64 frames go through in chunks (a chunk's work buffer: 128 MiB).
       const size_t sample = in_bytes_per_sample(c->cfg.in_format);
       const int chunk = std::min(nframes, 64);
       for (int f0 = 0; f0 < nframes; f0 += chunk) {
@@ -2133,7 +2064,7 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
         FftRole crole;
         crole.cols = &gcc;
         crole.n = nf * (c->n >> 13);
-        launch_step(c, &crole, (first && c->have_det) ? &c->pend_det : nullptr, c->pend_det_tiles, c->pend_det_spec, (first && c->have_emit) ? &c->pend_emit : nullptr, nullptr, first);
+        launch_step(c, &crole, w.riding(first ? W::DET | W::EMIT | W::PLAN : 0));
         ss::RowsExtra rxc = rx;
         rxc.abs0 += f0;
         rxc.first_hist -= f0;
@@ -2163,22 +2094,25 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
         rrole.rows1024 = &gr;
         rrole.n = nf * 128;
         const bool first = f0 == 0;
-        launch_step(c, &rrole, (first && c->have_det) ? &c->pend_det : nullptr, c->pend_det_tiles, c->pend_det_spec, (first && c->have_emit) ? &c->pend_emit : nullptr);
+        launch_step(c, &rrole, w.riding(first ? W::DET | W::EMIT : 0));
       }
     } else
-    launch_step(c, &role, c->have_det ? &c->pend_det : nullptr, c->pend_det_tiles, c->pend_det_spec, c->have_emit ? &c->pend_emit : nullptr);
-    shift_pending(c);
-    if (merged_call && c->rows1024x256) {  // (262144 points: 32 row tiles of 8 rows x 1024 points per frame)
-      c->pend_rows1024 = rows1024x256_args(c, nullptr, rx);
-      c->pend_rows1024.work = c->work_cur ? c->d_work2 : c->d_work;
-      c->pend_rows_tiles = nframes * 32;
-      c->have_rows = true;
-      c->work_cur ^= 1;
-    } else if (merged_call) {  // this call's row half waits for the next launch; it reads the work buffer this call's column half has just been told to fill
-      c->pend_rows = rows256_args(c, nullptr, rx);
-      c->pend_rows.work = c->work_cur ? c->d_work2 : c->d_work;
-      c->pend_rows_tiles = nframes * 8;
-      c->have_rows = true;
+    launch_step(c, &role, w.riding(W::DET | W::EMIT));
+    w.shift();
+    if (merged_call) {  // this call's row half waits for the next launch; it reads the work buffer this call's column half has just been told to fill
+      ss_ctx::PendRows& rows = w.rows.v;
+      float2* work = c->work_cur ? c->d_work2 : c->d_work;
+      rows.x1024 = c->rows1024x256;
+      if (rows.x1024) {  // (262144 points: 32 row tiles of 8 rows x 1024 points per frame)
+        rows.r1024 = rows1024x256_args(c, nullptr, rx);
+        rows.r1024.work = work;
+        rows.tiles = nframes * 32;
+      } else {
+        rows.r256 = rows256_args(c, nullptr, rx);
+        rows.r256.work = work;
+        rows.tiles = nframes * 8;
+      }
+      w.rows.have = true;
       c->work_cur ^= 1;
     }
     if (!c->use_fft8192 && !rows_by_step && !dif_call) {
@@ -2195,21 +2129,11 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
       if (c->cull || c->cull_long) hipLaunchKernelGGL(ss::k_thr_tilemin, dim3(c->n / 256), dim3(64), 0, c->stream, (const float*)z->d_thr, c->n, z->d_thr + c->n);
     }
     // (det_lag2: this call's detect stage waits for its plan, behind the planned one — which, if there is one, rode on this call's column launch)
-    ss::DetectArgs& nd = merged_call ? c->pend_det3 : c->det_lag2 ? c->pend_det2 : c->pend_det;
-    st = run_backend_fused(c, d_psd, nframes, n_learn, z, c->spec_in_detect ? spec : nullptr, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg,
-                           cand_cap, true, &nd, merged_call ? &c->pend_det3_tiles : c->det_lag2 ? &c->pend_det2_tiles : &c->pend_det_tiles,
-                           merged_call ? &c->pend_det3_emit : c->det_lag2 ? &c->pend_det2_emit : &c->pend_det_emit);
+    ss::StageSlot<ss_ctx::PendDet>& slot = w.new_detect(merged_call, c->det_lag2);
+    st = run_backend_fused(c, d_psd, nframes, n_learn, z, c->spec_in_detect ? spec : nullptr, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg, cand_cap, &slot.v);
     if (st != SS_OK) return st;
-    if (merged_call) {
-      c->have_det3 = true;
-      c->pend_det3_spec = false;
-    } else if (c->det_lag2) {
-      c->have_det2 = true;
-      c->pend_det2_spec = c->spec_in_detect && spec != nullptr;
-    } else {
-      c->have_det = true;
-      c->pend_det_spec = c->spec_in_detect && spec != nullptr;
-    }
+    slot.have = true;
+    ss::DetectArgs& nd = slot.v.a;
     if (cull_call) {
       nd.hist_by_fft = ring_by_rows ? 1 : 0;
       nd.tile_list = nullptr;
@@ -2238,14 +2162,11 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
         pl.logn = c->logn;
         pl.list = list;
         pl.layout = c->two_pass ? 1 : dif_call ? 2 : c->rows1024x256 ? 3 : 0;
-        if (merged_call) {  // (not ready before this call's row half has run: one launch from now)
-          c->have_plan2 = true;
-          c->pend_plan2 = pl;
-          c->pend_plan2_det = ss::plan_long_det(nd);
-        } else if (plan_fused) {
-          c->have_plan = true;
-          c->pend_plan = pl;
-          c->pend_plan_det = ss::plan_long_det(nd);
+        if (merged_call || plan_fused) {  // (a merged call's is not ready before the call's row half has run: one launch from now)
+          ss::StageSlot<ss_ctx::PendPlan>& plan = w.new_plan(merged_call);
+          plan.have = true;
+          plan.v.a = pl;
+          plan.v.det = ss::plan_long_det(nd);
         } else {
           const int plan_wgs = ss::plan_blocks_of(ss::plan_long_det(nd), pl, c->n);  // (groups past the band's end find no column)
           SS_LAUNCH_SLOT(c, SS_KSLOT_PLAN, (ss::k_plan_long<21, 21, kFusedTF, 256>), dim3(plan_wgs), dim3(256), 0, ss::plan_long_det(nd), pl);
@@ -2267,8 +2188,7 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
     }
     if (c->fused) {
       if (n_learn > 0) hipLaunchKernelGGL(ss::k_noise_learn, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, (const float*)d_psd, c->n, n_learn, z->d_thr);
-      st = run_backend_fused(c, d_psd, nframes, n_learn, z, c->spec_in_detect ? spec : nullptr, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg,
-                             cand_cap, false, nullptr, nullptr, nullptr);
+      st = run_backend_fused(c, d_psd, nframes, n_learn, z, c->spec_in_detect ? spec : nullptr, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg, cand_cap, nullptr);
     } else {
       st = run_backend_unfused(c, d_psd, nframes, n_learn, z, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg, cand_cap);
     }

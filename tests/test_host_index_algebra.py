@@ -35,3 +35,17 @@ def test_the_averager_ring_never_hands_out_rows_that_are_still_to_be_read(tmp_pa
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.strip().endswith("bad 0")
+
+
+def test_every_waiting_stage_rides_once_at_its_lag_and_in_its_calls_order(tmp_path):
+    """csrc/stage_slots.h — the stages of earlier calls that wait for a later launch in the in-order step pipeline — against its four
+    schedules, the drain from every reachable state and mixed sessions of merged and two-launch calls (tests/host/stage_slots_check.cpp;
+    plain C++, no HIP)."""
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("g++ not found")
+    exe = tmp_path / "stage_slots_check"
+    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-o", str(exe), os.path.join(ROOT, "tests", "host", "stage_slots_check.cpp")], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stdout.strip().endswith("bad 0")
