@@ -76,8 +76,12 @@ typedef enum ss_plane {
  * PSD per centre frequency; read it back with ss_spectrogram_read. */
 #define SS_FLAG_SPECTROGRAM 2u
 /* 8192-, 65536-, 131072- (int8), 262144- and 2^20-point frames: evaluate every averaging tile, also those whose per-frame maxima show that no window
- * mean of the tile can reach start_level (csrc/detect_fused.h, tile culling). Results are identical either way; the flag
- * exists so that the data-independent cost of the chain can be measured (bench.py reports both). */
+ * mean of the tile can reach start_level (csrc/detect_fused.h, tile culling). Results are identical either way — lists and
+ * cand_avg bit for bit, at any start_level (tests/test_gpu_detect_settings.py) —; the flag exists so that the data-independent
+ * cost of the chain can be measured (bench.py reports both). The transform is the same with and without the flag: int8 frames
+ * of 65536 and 131072 points go through the radix-8 / radix-16 fold either way, every tile listed untested (the flag used to
+ * send them through the four-step form, whose dB values round differently: cand_avg was off by an ulp); ss_get_stats then
+ * reports no culling and no tile tested. */
 #define SS_FLAG_NO_CULL 4u
 /* ss_process_device keeps to the context's stream: every stage of a call — FFT + dB, averaging / threshold, candidate lists — is
  * enqueued on ss_stream, in order, before the call returns, and work the caller enqueues there afterwards (a producer refilling

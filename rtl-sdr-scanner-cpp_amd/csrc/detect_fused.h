@@ -578,7 +578,7 @@ __host__ __device__ inline int plan_long_blocks(int layout, int C, int n) {  // 
 // 2^20-point frame — whose first workgroups may run the plan of the call before, k_fft_cols1024_plan — has no use for).
 struct PlanLongDet {
   int n, nframes, shift, n_learn;
-  int planes_out;  // a rel or avg plane is wanted: nothing is tested, every tile is listed
+  int planes_out;  // a rel or avg plane is wanted (or SS_FLAG_NO_CULL on the fold's context, ss_ctx::plan_all): nothing is tested, every tile is listed
   float start_level;
   const float* thr_tilemin;
   unsigned long long* stats;

@@ -336,6 +336,11 @@ struct ss_ctx {
   // drains what waits and has the window's 35 rows rewritten first (set_ring_form).
   bool dif8 = false;
   int dif_logq = 3;               // log2 of the fold's radix: 3 (65536 points) or 4 (131072 points: sixteen residues, KIND 9)
+  // SS_FLAG_NO_CULL where the fold runs: the fold IS the culling context's transform (its rows go to the ring's buffer, the plan hands its
+  // tiles out), and the four-step form the flag used to fall back to rounds its dB values differently — the lists agreed, cand_avg
+  // was off by an ulp in a third of the candidates (tests/test_gpu_detect_settings.py). So the flag keeps the context there and the
+  // plan lists every tile untested (PlanLongDet::planes_out): the same transform, the same bits.
+  bool plan_all = false;
   bool cull_fold_only = false;    // 131072 points: the culling machinery (run maxima, plan, ring rows by the FFT stage) serves the fold's calls only — the four-step form of that size has no such epilogue
   bool ring_perm8 = false;
   bool last_rows_perm8 = false;   // ... and the rows ss_read_window serves (last_hist, last_rel_rows)
@@ -2162,14 +2167,16 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
         pl.logn = c->logn;
         pl.list = list;
         pl.layout = c->two_pass ? 1 : dif_call ? 2 : c->rows1024x256 ? 3 : 0;
+        ss::PlanLongDet pdet = ss::plan_long_det(nd);
+        if (c->plan_all) pdet.planes_out = 1;  // (SS_FLAG_NO_CULL on the fold's context: every tile listed, none tested)
         if (merged_call || plan_fused) {  // (a merged call's is not ready before the call's row half has run: one launch from now)
           ss::StageSlot<ss_ctx::PendPlan>& plan = w.new_plan(merged_call);
           plan.have = true;
           plan.v.a = pl;
-          plan.v.det = ss::plan_long_det(nd);
+          plan.v.det = pdet;
         } else {
-          const int plan_wgs = ss::plan_blocks_of(ss::plan_long_det(nd), pl, c->n);  // (groups past the band's end find no column)
-          SS_LAUNCH_SLOT(c, SS_KSLOT_PLAN, (ss::k_plan_long<21, 21, kFusedTF, 256>), dim3(plan_wgs), dim3(256), 0, ss::plan_long_det(nd), pl);
+          const int plan_wgs = ss::plan_blocks_of(pdet, pl, c->n);  // (groups past the band's end find no column)
+          SS_LAUNCH_SLOT(c, SS_KSLOT_PLAN, (ss::k_plan_long<21, 21, kFusedTF, 256>), dim3(plan_wgs), dim3(256), 0, pdet, pl);
         }
         nd.tile_list = list;
       }
@@ -2479,7 +2486,9 @@ int ss_create(const ss_config* cfg, ss_ctx** out) {
   const bool fold_ok = c->diag.dif8 && c->diag.emit_wide && c->diag.ring_only && (cfg->in_format == SS_FMT_CS8 || cfg->in_format == SS_FMT_CU8) && !cfg->window &&
                        !(cfg->flags & (SS_FLAG_STREAM_ORDERED | SS_FLAG_REFERENCE_NAN | SS_FLAG_KEEP_PLANES | SS_FLAG_SPECTROGRAM));
   const bool x256_ok = n == 262144 && c->diag.rows1024x256 && c->diag.emit_wide && c->diag.fft_rows_r < 0 && c->diag.fft_sub < 0 && !(cfg->flags & SS_FLAG_SPECTROGRAM);
-  c->det_lag2 = !c->deep && c->step_path && (n == 65536 || (n == 131072 && fold_ok) || x256_ok) && !c->diag.fft_generic && c->diag.cull_65536 && c->diag.cull && !(cfg->flags & SS_FLAG_NO_CULL) &&
+  c->plan_all = (cfg->flags & SS_FLAG_NO_CULL) && fold_ok && (n == 65536 || n == 131072);  // (see ss_ctx::plan_all)
+  const bool no_cull = (cfg->flags & SS_FLAG_NO_CULL) && !c->plan_all;
+  c->det_lag2 = !c->deep && c->step_path && (n == 65536 || (n == 131072 && fold_ok) || x256_ok) && !c->diag.fft_generic && c->diag.cull_65536 && c->diag.cull && !no_cull &&
                 c->diag.rows256_step && c->diag.step_long && c->diag.det_lag2 && c->fused;
   c->merge = c->det_lag2 && (n == 65536 || x256_ok) && c->diag.merge_65536 && c->diag.emit_wide;  // (one launch per call: scan_step.h KIND 7 / KIND 12, whose emit role is the wide one)
   c->merge_max = std::max(1, (int)((long long)c->diag.merge_max_frames * 65536 / n));  // (128 frames of 65536 points, 32 of 262144: 64 MiB of work buffer either way)
@@ -2745,7 +2754,7 @@ int ss_create(const ss_config* cfg, ss_ctx** out) {
   c->x256_tile = n == 262144 && c->use_fft256 && c->d_tw_rowsR != nullptr && c->diag.rows1024x256 && c->diag.fft_rows_r < 0 && c->diag.fft_sub < 0;
   c->rows1024x256 = c->det_lag2 && c->x256_tile;
   c->cull_long = c->step_path && c->use_fft256 && ((n == 65536 && c->diag.cull_65536) || (n > 65536 && c->d_tw_sub && !c->d_tw_rowsR) || c->two_pass || c->cull_fold_only || c->rows1024x256) &&
-                 !(cfg->flags & SS_FLAG_NO_CULL) && c->diag.cull;
+                 !no_cull && c->diag.cull;
   if (!c->cull_long) c->rows1024x256 = false;
   if (n == 262144 && !c->rows1024x256) c->merge = false;  // (never: decided from the same switches; the second work buffer and the rotating sets sized for it do no harm)
   // 65536 points: with the plan of call k at the front of call k + 1's column launch — which therefore is a launch of its own, the
@@ -2850,7 +2859,7 @@ int ss_get_stats(ss_ctx* c, ss_stats* out) {
     st.tiles_culled += dev[k * ss::kStatShardStride + ss::kStatCulled];
     st.wait_fallbacks += dev[k * ss::kStatShardStride + ss::kStatWaitFallbacks];
   }
-  st.state = (c->cull || c->cull_long ? SS_STATE_CULLING : 0u) | (c->deep ? SS_STATE_OVERLAP : 0u) | (c->deep && c->deep_iq_recycled ? SS_STATE_DEMOTED : 0u) |
+  st.state = (c->cull || (c->cull_long && !c->plan_all) ? SS_STATE_CULLING : 0u) | (c->deep ? SS_STATE_OVERLAP : 0u) | (c->deep && c->deep_iq_recycled ? SS_STATE_DEMOTED : 0u) |
              (c->deep && c->deep_eager ? SS_STATE_EAGER : 0u);
   const uint32_t want = out->size < sizeof(ss_stats) ? out->size : (uint32_t)sizeof(ss_stats);
   st.size = want;

@@ -84,6 +84,59 @@ def cand_set(off, idx):
     return set(zip(frames.tolist(), np.asarray(idx).tolist()))
 
 
+def pass_mask(n, fs, range_lo, range_hi, ignored=()):
+    """Which bins a chain lists at all: isIndexInRange && !isIndexIgnored (sdr_device.cpp:153-158, transmission.cpp:156-164) — the
+    bin's frequency, centre of the scanned range plus (int32)(fs / N * (i + 0.5)) - fs / 2, lies inside the range and in no ignored one
+    (both ends inclusive). Anchored against the oracle's own lists by tests/test_cull_bound_math.py."""
+    shift = (np.float64(fs) / n * (np.arange(n) + 0.5)).astype(np.int32) - fs // 2
+    f = (int(range_lo) + int(range_hi)) // 2 + shift.astype(np.int64)
+    ok = (range_lo <= f) & (f <= range_hi)
+    ig = np.asarray(ignored, dtype=np.int64).reshape(-1, 2)
+    for lo, hi in ig:
+        ok &= ~((lo <= f) & (f <= hi))
+    return ok
+
+
+def lists_at_level(ref_avg, level, passes):
+    """The reference's candidate lists at ANOTHER start level from one run's avg plane (which does not depend on the level):
+    float32(level) <= avg[f, i] for the bins that pass (transmission.cpp:90-94; a NaN never passes). Returns (cand_off, cand_idx)
+    as the chains hand them out — the set is cand_set(cand_off, cand_idx)."""
+    with np.errstate(invalid="ignore"):
+        hit = (np.float32(level) <= ref_avg) & np.asarray(passes, bool)[None, :]
+    off = np.concatenate([[0], np.cumsum(hit.sum(axis=1))]).astype(np.int64)
+    return off, np.nonzero(hit)[1].astype(np.int32)
+
+
+def tile_bounds(psd, thr, learn, reach="runs", frames_per_tile=16, bins_per_tile=256, g=21):
+    """csrc/detect_fused.h's culling bound restated on a reference's planes, for every 16-frame x 256-bin tile (frame tiles aligned
+    to frame 0) whose 36 rows all lie behind the `learn` learning frames: max over the tile's frames f of mean(M_{f-20} .. M_f) - m,
+    with M_g the largest dB value of frame g over the tile's reach and m the smallest noise ceiling over the column's 256 bins and
+    32 more on either side. reach = "runs": those 320 bins (8192 points; the long rows' 32-bin runs); "columns": the column and both
+    whole neighbours (the radix-8 / radix-16 fold keeps a maximum per column and residue). Returns [frame tiles, columns] float64,
+    NaN for the tiles that are never tested."""
+    nframes, n = psd.shape
+    cols, side = n // bins_per_tile, (32 if reach == "runs" else bins_per_tile)
+    nft = nframes // frames_per_tile
+    out = np.full((nft, cols), np.nan)
+    colmax = psd.astype(np.float64).reshape(nframes, cols, bins_per_tile)
+    edge_lo, edge_hi = colmax[:, :, -side:].max(axis=2), colmax[:, :, :side].max(axis=2)
+    m_all = colmax.max(axis=2)
+    m_all[:, 1:] = np.maximum(m_all[:, 1:], edge_lo[:, :-1])
+    m_all[:, :-1] = np.maximum(m_all[:, :-1], edge_hi[:, 1:])
+    t = thr.astype(np.float64).reshape(cols, bins_per_tile)
+    tm = t.min(axis=1)
+    tm[1:] = np.minimum(tm[1:], t[:-1, -32:].min(axis=1))
+    tm[:-1] = np.minimum(tm[:-1], t[1:, :32].min(axis=1))
+    csum = np.vstack([np.zeros((1, cols)), np.cumsum(m_all, axis=0)])
+    for ft in range(nft):
+        f0 = ft * frames_per_tile
+        if f0 - (g - 1) < learn:
+            continue
+        f = np.arange(f0, f0 + frames_per_tile)
+        out[ft] = ((csum[f + 1] - csum[f + 1 - g]) / g).max(axis=0) - tm
+    return out
+
+
 def check_candidates(got_off, got_idx, ref_off, ref_idx, ref_avg, start_level, got_avg_plane=None):
     """Returns (n_reference_candidates, n_dont_care)."""
     a, b = cand_set(got_off, got_idx), cand_set(ref_off, ref_idx)
