@@ -26,6 +26,7 @@
 #include "../../include/specscan_track.h"
 #include "../../include/specscan_track_feed.h"
 #include "../../include/specscan_record_feed.h"
+#include "../../include/specscan_spectrogram_feed.h"
 #include "detect_fused.h"
 #include "detect_kernels.h"
 #include "fft1024_kernels.h"
@@ -34,6 +35,8 @@
 #include "fft_kernels.h"
 #include "ring_place.h"
 #include "scan_step.h"
+#include "spectrogram_gate.h"
+#include "spectrogram_rows.h"
 #include "stage_slots.h"
 #include "track_digest.h"
 #include "track_digest_blocked.h"
@@ -3301,6 +3304,19 @@ struct ss_feed {
   stf_ctx* tracker = nullptr;  // stf_create: every batch is digested behind its chain (include/specscan_track_feed.h)
   srf_ctx* recorder = nullptr;  // srf_create: a collected slot stays held until its samples are recorded or let go (include/specscan_record_feed.h)
   int held = -1;                // the held slot
+  sgf_ctx* spectrogram = nullptr;  // sgf_create: every batch leaves the spectrogram rows it closes (include/specscan_spectrogram_feed.h)
+  int last_collected = -1;         // the slot of the batch collected last: what sgf_rows reads
+};
+
+// What a batch's clock decides for the spectrogram rows, worked out on copies before anything is enqueued (sgf_plan_batch) and
+// taken over once the batch's chain is in the stream (sgf_enqueue).
+struct sgf_plan {
+  int32_t center = 0;
+  int64_t last_send = 0;  // the centre's gate behind the batch
+  int32_t have_last = 0;
+  int32_t ncuts = 0;
+  int32_t cut[SGF_MAX_ROWS];   // the closing frames
+  int64_t time[SGF_MAX_ROWS];  // and their t_ms
 };
 
 namespace {
@@ -3308,6 +3324,9 @@ namespace {
 int stf_enqueue(ss_feed* f, int slot, int nframes);
 void stf_feed_gone(stf_ctx* t);
 void srf_feed_gone(srf_ctx* t);
+void sgf_feed_gone(sgf_ctx* t);
+int sgf_plan_batch(ss_feed* f, int nframes, const int64_t* t_ms, sgf_plan* plan);
+int sgf_enqueue(ss_feed* f, int slot, int nframes, const sgf_plan& plan);
 int feed_collect(ss_feed* f, ss_feed_result* out, stf_result* digest);
 
 void feed_free(ss_feed* f) {
@@ -3385,6 +3404,7 @@ void ss_feed_destroy(ss_feed* f) {
     (void)hipStreamSynchronize(f->d2h_stream);
     if (f->tracker) stf_feed_gone(f->tracker);
     if (f->recorder) srf_feed_gone(f->recorder);
+    if (f->spectrogram) sgf_feed_gone(f->spectrogram);
   }
   feed_free(f);
 }
@@ -3419,6 +3439,11 @@ int ss_feed_submit(ss_feed* f, int32_t nframes, const int64_t* t_ms, int64_t use
   if (f->acquired < 0) return fail(c, SS_ERR_INVALID, "ss_feed_submit without ss_feed_acquire");
   if (nframes <= 0) return fail(c, SS_ERR_INVALID, "nframes %d", nframes);
   if (nframes > c->cfg.max_batch) return fail(c, SS_ERR_BATCH, "nframes %d > max_batch %d", nframes, c->cfg.max_batch);
+  sgf_plan rows_plan;
+  if (f->spectrogram) {  // refusals of the spectrogram rows come before anything is enqueued: the slot stays acquired
+    const int planned = sgf_plan_batch(f, nframes, t_ms, &rows_plan);
+    if (planned != SS_OK) return planned;
+  }
   SS_HIP(c, hipSetDevice(c->cfg.device_id));
   ss_feed_slot& s = f->slots[(size_t)f->acquired];
   const int n = c->n;
@@ -3439,6 +3464,10 @@ int ss_feed_submit(ss_feed* f, int32_t nframes, const int64_t* t_ms, int64_t use
   if (f->want_psd) SS_HIP(c, hipMemcpyAsync(s.h_psd, c->last_psd, sizeof(float) * (size_t)n * (size_t)nframes, hipMemcpyDeviceToHost, c->stream));
   if (f->tracker) {  // the digest: behind the chain and the result copies, in front of ev_done; nothing in it waits on the host
     st = stf_enqueue(f, f->acquired, nframes);
+    if (st != SS_OK) return st;
+  }
+  if (f->spectrogram) {  // the rows this batch closes: one kernel on the dB plane, then exactly their bytes to the slot's pinned memory
+    st = sgf_enqueue(f, f->acquired, nframes, rows_plan);
     if (st != SS_OK) return st;
   }
   SS_HIP(c, hipEventRecord(s.ev_done, c->stream));
@@ -3988,6 +4017,7 @@ int feed_collect(ss_feed* f, ss_feed_result* out, stf_result* digest) {
   out->psd_db = f->want_psd ? s->h_psd : nullptr;
   s->state = f->recorder ? 3 : 0;  // held: its d_in is what srf_record reads
   if (f->recorder) f->held = slot_no;
+  f->last_collected = slot_no;
   f->next_collect = (f->next_collect + 1) % f->depth;
   --f->pending;
   return SS_OK;
@@ -4281,6 +4311,232 @@ int srf_record(srf_ctx* t, const sc_range* ranges, int32_t nranges, srf_result* 
   }
   std::lock_guard<std::mutex> lock(t->scan->mtx);
   if (t->feed && t->feed->held >= 0) srf_let_go(t->feed);
+  return SS_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The spectrogram rows of the feed (include/specscan_spectrogram_feed.h): the reference's per-frame send gate on the host
+// (spectrogram_gate.h) and its arithmetic, in its order, in one kernel behind every batch (spectrogram_rows.h). Everything here is
+// the scan context's, under its mutex. The kernel is on the context's stream behind flush_stages, like the tracked feed's digest
+// (see there for why the next batch's chain cannot overtake it): it reads c->last_psd before the next batch rotates the planes.
+struct sgf_container {  // Spectrogram::Container (spectrogram.h:10-16), one per centre frequency: the sum on the device, the rest here
+  int32_t center = 0;
+  float* d_sum = nullptr;
+  int64_t last_send = 0;
+  int32_t have_last = 0;  // the container's first frame stamps last_send
+  int32_t count = 0;      // m_counter
+};
+
+struct sgf_slot {
+  int8_t* d_rows = nullptr;
+  float* d_mean = nullptr;
+  int8_t* h_rows = nullptr;  // pinned
+  float* h_mean = nullptr;
+  int64_t* h_time = nullptr;
+  int32_t *h_frame = nullptr, *h_count = nullptr;
+  int32_t nrows = 0, frequency = 0, open_count = 0;
+};
+
+struct sgf_ctx {
+  ss_ctx* scan = nullptr;
+  ss_feed* feed = nullptr;  // null once the feed has been destroyed: only sgf_destroy / sgf_last_error from then on
+  sgf_config cfg{};
+  int size = 0, log2_m = 0;
+  std::vector<sgf_container> containers;
+  std::vector<sgf_slot> slots;
+  char err[512] = "";
+};
+
+namespace {
+
+thread_local char g_sgf_create_err[512] = "";
+
+template <class... A>
+int sgf_fail(sgf_ctx* t, int status, const char* fmt, A... a) {
+  return fail_to(t ? t->err : g_sgf_create_err, status, fmt, a...);
+}
+
+void sgf_free(sgf_ctx* t) {
+  if (!t) return;
+  for (auto& g : t->containers) (void)hipFree(g.d_sum);
+  for (auto& s : t->slots) {
+    (void)hipFree(s.d_rows);
+    (void)hipFree(s.d_mean);
+    for (void* p : {(void*)s.h_rows, (void*)s.h_mean, (void*)s.h_time, (void*)s.h_frame, (void*)s.h_count})
+      if (p) (void)hipHostFree(p);
+  }
+  delete t;
+}
+
+void sgf_feed_gone(sgf_ctx* t) { t->feed = nullptr; }
+
+sgf_container* sgf_container_for(sgf_ctx* t, int32_t center) {
+  for (auto& g : t->containers)
+    if (g.center == center) return &g;
+  return nullptr;
+}
+
+// ss_feed_submit, under the context's lock, in front of the upload: the gate of the centre in force over the batch's clock, on
+// copies. A refusal leaves every state as it was.
+int sgf_plan_batch(ss_feed* f, int nframes, const int64_t* t_ms, sgf_plan* plan) {
+  sgf_ctx* t = f->spectrogram;
+  ss_ctx* c = f->c;
+  if (!t_ms) return fail(c, SS_ERR_INVALID, "ss_feed_submit without t_ms: the feed's spectrogram rows close on the frames' clock");
+  plan->center = (c->range_lo + c->range_hi) / 2;
+  if (const sgf_container* g = sgf_container_for(t, plan->center)) {
+    plan->last_send = g->last_send;
+    plan->have_last = g->have_last;
+  }
+  const int rows = ss::spectrogram_gate_plan(&plan->last_send, &plan->have_last, t_ms, nframes, plan->cut, t->cfg.max_rows);
+  if (rows > t->cfg.max_rows) return fail(c, SS_ERR_INVALID, "the batch's clock closes %d spectrogram rows, max_rows is %d: submit fewer frames at a time", rows, t->cfg.max_rows);
+  plan->ncuts = rows;
+  for (int k = 0; k < rows; ++k) plan->time[k] = t_ms[plan->cut[k]];
+  return SS_OK;
+}
+
+// ss_feed_submit, behind flush_stages and the result copies, in front of ev_done: the batch's rows, and the plan taken over.
+int sgf_enqueue(ss_feed* f, int slot_no, int nframes, const sgf_plan& plan) {
+  sgf_ctx* t = f->spectrogram;
+  ss_ctx* c = f->c;
+  sgf_slot& s = t->slots[(size_t)slot_no];
+  if (!c->last_psd || ((uintptr_t)c->last_psd & 15u)) return fail(c, SS_ERR_INVALID, "spectrogram rows: the batch left no (16-byte aligned) dB plane");
+  sgf_container* g = sgf_container_for(t, plan.center);
+  if (!g) {  // first use of a centre: a zeroed sum row (Container's constructor)
+    sgf_container fresh;
+    fresh.center = plan.center;
+    SS_HIP(c, hipMalloc(&fresh.d_sum, sizeof(float) * (size_t)t->size));
+    const hipError_t e = hipMemsetAsync(fresh.d_sum, 0, sizeof(float) * (size_t)t->size, c->stream);
+    if (e != hipSuccess) {
+      (void)hipFree(fresh.d_sum);
+      return fail(c, SS_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
+    }
+    t->containers.push_back(fresh);
+    g = &t->containers.back();
+  }
+  ss::SpecRowsArgs a{};
+  a.psd = c->last_psd;
+  a.sum = g->d_sum;
+  a.rows = s.d_rows;
+  a.mean = t->cfg.want_mean ? s.d_mean : nullptr;
+  a.n = c->n;
+  a.nframes = nframes;
+  a.size = t->size;
+  a.log2_m = t->log2_m;
+  a.count0 = g->count;
+  a.ncuts = plan.ncuts;
+  for (int k = 0; k < plan.ncuts; ++k) a.cut[k] = plan.cut[k];
+  const dim3 grid((unsigned)(c->n >> std::max(t->log2_m, 6)));
+  if (t->log2_m <= 2) hipLaunchKernelGGL(ss::k_spec_rows<false>, grid, dim3(256), 0, c->stream, a);
+  else hipLaunchKernelGGL(ss::k_spec_rows<true>, grid, dim3(256), 0, c->stream, a);
+  SS_HIP(c, hipGetLastError());
+  if (plan.ncuts > 0) {
+    const size_t cells = (size_t)plan.ncuts * (size_t)t->size;
+    SS_HIP(c, hipMemcpyAsync(s.h_rows, s.d_rows, cells, hipMemcpyDeviceToHost, c->stream));
+    if (t->cfg.want_mean) SS_HIP(c, hipMemcpyAsync(s.h_mean, s.d_mean, sizeof(float) * cells, hipMemcpyDeviceToHost, c->stream));
+  }
+  int32_t count = g->count, prev = -1;
+  for (int k = 0; k < plan.ncuts; ++k) {  // m_counter at each send: the closing frame is part of its row
+    s.h_time[k] = plan.time[k];
+    s.h_frame[k] = plan.cut[k];
+    s.h_count[k] = count + (plan.cut[k] - prev);
+    count = 0;
+    prev = plan.cut[k];
+  }
+  g->count = count + (nframes - 1 - prev);
+  g->last_send = plan.last_send;
+  g->have_last = plan.have_last;
+  s.nrows = plan.ncuts;
+  s.frequency = plan.center;
+  s.open_count = g->count;
+  return SS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t sgf_gate_plan(int64_t* last_send, int32_t* have_last, const int64_t* t_ms, int32_t nframes, int32_t* cut_frame, int32_t cap) {
+  if (!last_send || !have_last || nframes < 0 || (nframes > 0 && !t_ms) || cap < 0 || (cap > 0 && !cut_frame)) return SS_ERR_INVALID;
+  return ss::spectrogram_gate_plan(last_send, have_last, t_ms, nframes, cut_frame, cap);
+}
+
+int sgf_create(ss_feed* f, const sgf_config* cfg, sgf_ctx** out) {
+  if (!f || !cfg || !out) return sgf_fail(nullptr, SS_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (cfg->abi_version != SGF_ABI_VERSION) return sgf_fail(nullptr, SS_ERR_INVALID, "abi_version %u, library has %u", cfg->abi_version, SGF_ABI_VERSION);
+  if (cfg->max_rows < 1 || cfg->max_rows > SGF_MAX_ROWS) return sgf_fail(nullptr, SS_ERR_INVALID, "max_rows %d outside 1..%d", cfg->max_rows, SGF_MAX_ROWS);
+  ss_ctx* c = f->c;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (c->spec_n <= 0) return sgf_fail(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_SPECTROGRAM (it fixes the row size and keeps every batch's dB plane)");
+  if (f->spectrogram) return sgf_fail(nullptr, SS_ERR_INVALID, "the feed already has a spectrogram object");
+  if (f->pending > 0 || f->acquired >= 0) return sgf_fail(nullptr, SS_ERR_INVALID, "the feed has batches pending: collect them first");
+  int log2_m = 0;
+  while (log2_m < 30 && ((long long)c->spec_n << log2_m) < c->n) ++log2_m;
+  if (((long long)c->spec_n << log2_m) != c->n || c->spec_m != (1 << log2_m) || c->n % 64 != 0)
+    return sgf_fail(nullptr, SS_ERR_INVALID, "%d points into %d spectrogram bins: the rows need a power-of-two ratio and a multiple of 64 points", c->n, c->spec_n);
+  sgf_ctx* t = new (std::nothrow) sgf_ctx();
+  if (!t) return sgf_fail(nullptr, SS_ERR_NOMEM, "out of memory");
+  t->scan = c;
+  t->feed = f;
+  t->cfg = *cfg;
+  t->size = c->spec_n;
+  t->log2_m = log2_m;
+  t->slots.resize((size_t)f->depth);
+  const size_t cells = (size_t)cfg->max_rows * (size_t)t->size, rows = (size_t)cfg->max_rows;
+  bool ok = hipSetDevice(c->cfg.device_id) == hipSuccess;
+  for (auto& s : t->slots) {
+    ok = ok && hipMalloc(&s.d_rows, cells) == hipSuccess && hipHostMalloc((void**)&s.h_rows, cells, hipHostMallocDefault) == hipSuccess;
+    if (cfg->want_mean) ok = ok && hipMalloc(&s.d_mean, sizeof(float) * cells) == hipSuccess && hipHostMalloc((void**)&s.h_mean, sizeof(float) * cells, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&s.h_time, sizeof(int64_t) * rows, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&s.h_frame, sizeof(int32_t) * rows, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&s.h_count, sizeof(int32_t) * rows, hipHostMallocDefault) == hipSuccess;
+  }
+  if (!ok) {
+    const hipError_t e = hipGetLastError();
+    sgf_free(t);
+    return sgf_fail(nullptr, SS_ERR_NOMEM, "allocating the spectrogram rows' buffers failed: %s", hipGetErrorString(e));
+  }
+  f->spectrogram = t;
+  f->last_collected = -1;
+  *out = t;
+  return SS_OK;
+}
+
+void sgf_destroy(sgf_ctx* t) {
+  if (!t) return;
+  {
+    std::lock_guard<std::mutex> lock(t->scan->mtx);
+    (void)hipSetDevice(t->scan->cfg.device_id);
+    if (t->feed) {  // (a destroyed feed has waited for its streams already)
+      (void)hipStreamSynchronize(t->scan->stream);
+      t->feed->spectrogram = nullptr;
+    }
+  }
+  sgf_free(t);
+}
+
+const char* sgf_last_error(const sgf_ctx* t) { return t ? t->err : g_sgf_create_err; }
+
+int sgf_rows(sgf_ctx* t, sgf_result* out) {
+  if (!t) return SS_ERR_INVALID;
+  if (!out) return sgf_fail(t, SS_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(t->scan->mtx);
+  const ss_feed* f = t->feed;
+  if (!f) return sgf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
+  if (f->last_collected < 0) return sgf_fail(t, SS_ERR_INVALID, "no batch has been collected since sgf_create");
+  const sgf_slot& s = t->slots[(size_t)f->last_collected];
+  out->nrows = s.nrows;
+  out->size = t->size;
+  out->frequency = s.frequency;
+  out->sample_rate = t->scan->cfg.sample_rate;
+  out->open_count = s.open_count;
+  out->time_ms = s.h_time;
+  out->frame = s.h_frame;
+  out->count = s.h_count;
+  out->rows = s.h_rows;
+  out->mean = t->cfg.want_mean ? s.h_mean : nullptr;
   return SS_OK;
 }
 

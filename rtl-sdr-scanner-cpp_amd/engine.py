@@ -236,6 +236,13 @@ class Feed:
         from .recorder import RecordedFeed
         return RecordedFeed(self, bandwidth, channels, **kw)
 
+    def spectrogram(self, max_rows: int = 8, want_mean: bool = False):
+        """The spectrogram rows behind this feed (include/specscan_spectrogram_feed.h; the engine needs ``flags=SS_FLAG_SPECTROGRAM``):
+        from now on every ``submit`` needs ``t_ms``, a row closes at every frame whose clock is more than 1000 ms past the last send —
+        the reference's per-frame gate — and the returned object's ``rows()`` gives the rows of the batch collected last."""
+        from .spectrogram import SpectrogramFeed
+        return SpectrogramFeed(self, max_rows, want_mean)
+
     def __del__(self):
         try:
             self.close()

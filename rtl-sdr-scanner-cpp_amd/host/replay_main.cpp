@@ -6,16 +6,23 @@
 // dump would (`..._power.raw`, sdr_device.cpp:173-176).
 //
 //   specscan_replay <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track [--bandwidth HZ]]
+//                   [--spectrogram-out FILE [--spectrogram-max-rows R]]
 // Prints one JSON line: frames, batches, candidates, seconds, MS/s (file + PCIe inclusive).
 //
 // --track: the feed is a tracked one (include/specscan_track_feed.h) — every batch is digested on the device behind its chain, and
 // the consumer thread owns a specscan::SignalTracker (host/signal_tracker.h): after each stf_collect it runs the batch's frames
 // through processFrameDigest (frame time 1000 * frame_index * N * D / fs ms, the stream's own clock) and posts its keys. The reader
 // thread is unchanged. The JSON line gains `transmissions` (entries of the per-frame lists, summed) and `tracked_frames`.
+// --spectrogram-out FILE: the feed delivers the spectrogram rows (include/specscan_spectrogram_feed.h; the context gets
+// SS_FLAG_SPECTROGRAM). Frame k carries the time nearbyint(k * period), period = 1000 * N * D / fs ms — the clock the reference's
+// per-frame send gate runs on — and every row a batch closes is written to FILE as its DataController::pushSpectrogram payload
+// (ss_spectrogram_payload) behind its length as a little-endian uint32. The JSON line gains `spectrogram_rows`.
 #include <specscan.h>
+#include <specscan_spectrogram_feed.h>
 #include <specscan_track_feed.h>
 
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -31,7 +38,8 @@
 namespace {
 
 struct Options {
-  std::string path, power_dir;
+  std::string path, power_dir, spectrogram_out;
+  int spectrogram_max_rows = 8;
   int fft = 0, decim = 0, batch = 1024, depth = 3, learn_frames = -1;
   bool track = false;
   int bandwidth = 32000;  // Config::recordingBandwidth: the tracker's windows are ceil(bandwidth / (fs / N)) bins wide
@@ -59,6 +67,11 @@ bool parse_args(int argc, char** argv, Options* o) {
       o->track = true;
     } else if (a == "--bandwidth") {
       if (!next(&o->bandwidth) || o->bandwidth <= 0) return false;
+    } else if (a == "--spectrogram-out") {
+      if (i + 1 >= argc) return false;
+      o->spectrogram_out = argv[++i];
+    } else if (a == "--spectrogram-max-rows") {
+      if (!next(&o->spectrogram_max_rows)) return false;
     } else if (a == "--power-dir") {
       if (i + 1 >= argc) return false;
       o->power_dir = argv[++i];
@@ -76,7 +89,7 @@ bool parse_args(int argc, char** argv, Options* o) {
 int main(int argc, char** argv) {
   Options opt;
   if (!parse_args(argc, argv, &opt)) {
-    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track [--bandwidth HZ]]\n", argv[0]);
+    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R]]\n", argv[0]);
     return 2;
   }
   specscan::RawFileInfo info;
@@ -90,6 +103,8 @@ int main(int argc, char** argv) {
   if (opt.decim > 0) cfg.decim = opt.decim;
   if (opt.learn_frames >= 0) cfg.learn_frames = opt.learn_frames;
   if (opt.track) cfg.flags |= SS_FLAG_KEEP_PLANES;  // the digest reads the kept dB and avg planes
+  const bool want_rows = !opt.spectrogram_out.empty();
+  if (want_rows) cfg.flags |= SS_FLAG_SPECTROGRAM;
   cfg.max_batch = opt.batch;
   if (info.kind == specscan::RawKind::CS8 || info.kind == specscan::RawKind::CU8) {
     cfg.in_format = info.kind == specscan::RawKind::CS8 ? SS_FMT_CS8 : SS_FMT_CU8;
@@ -126,6 +141,21 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  sgf_ctx* rows = nullptr;
+  FILE* rows_file = nullptr;
+  if (want_rows) {
+    sgf_config rcfg{SGF_ABI_VERSION, opt.spectrogram_max_rows, 0};
+    if (sgf_create(feed, &rcfg, &rows) != SS_OK) fprintf(stderr, "sgf_create: %s\n", sgf_last_error(nullptr));
+    else if (!(rows_file = fopen(opt.spectrogram_out.c_str(), "wb"))) fprintf(stderr, "%s: cannot open for writing\n", opt.spectrogram_out.c_str());
+    if (!rows_file) {
+      sgf_destroy(rows);
+      stf_destroy(tracked);
+      ss_feed_destroy(feed);
+      ss_destroy(ctx);
+      return 1;
+    }
+  }
+  const double frame_period_ms = 1000.0 * cfg.fft_size * cfg.decim / info.sample_rate;
   int rc = 0;
   try {
     specscan::RawIqReader reader(opt.path, info.kind, cfg.fft_size, cfg.decim);
@@ -157,7 +187,10 @@ int main(int argc, char** argv) {
         try {
           if (ss_feed_acquire(feed, &frames) != SS_OK) throw std::runtime_error(ss_last_error(ctx));
           got = reader.readFramesParallel(frames, cfg.max_batch, 4);
-          if (got > 0 && ss_feed_submit(feed, got, nullptr, reader.position() - got) != SS_OK) throw std::runtime_error(ss_last_error(ctx));
+          std::vector<int64_t> t_ms;
+          if (want_rows)  // (round to even, as numpy's round: replay.replay_file gives the same clock)
+            for (int k = 0; k < got; ++k) t_ms.push_back((int64_t)std::nearbyint((double)(reader.position() - got + k) * frame_period_ms));
+          if (got > 0 && ss_feed_submit(feed, got, want_rows ? t_ms.data() : nullptr, reader.position() - got) != SS_OK) throw std::runtime_error(ss_last_error(ctx));
         } catch (const std::exception& e) {
           std::lock_guard<std::mutex> lock(mtx);
           failed = true;
@@ -174,7 +207,8 @@ int main(int argc, char** argv) {
       }
     });
 
-    long long frames = 0, batches = 0, candidates = 0, transmissions = 0, tracked_frames = 0;
+    long long frames = 0, batches = 0, candidates = 0, transmissions = 0, tracked_frames = 0, spectrogram_rows = 0;
+    std::vector<uint8_t> payload;
     specscan::SignalTracker tracker(tc);
     const auto frame_time_ms = [&](long long index) { return (int64_t)(1000ll * index * cfg.fft_size * cfg.decim / info.sample_rate); };
     for (;;) {
@@ -205,6 +239,20 @@ int main(int argc, char** argv) {
         }
       } else if (ss_feed_collect(feed, &r) != SS_OK) {
         why = ss_last_error(ctx);
+      }
+      if (why.empty() && rows) {
+        sgf_result g;
+        if (sgf_rows(rows, &g) != SS_OK) why = sgf_last_error(rows);
+        for (int k = 0; why.empty() && k < g.nrows; ++k) {
+          const int8_t* row = g.rows + (size_t)k * (size_t)g.size;
+          const int len = ss_spectrogram_payload((uint64_t)g.time_ms[k], g.frequency, g.sample_rate, row, g.size, nullptr, 0);
+          if (len > 0) payload.resize((size_t)len);
+          const uint8_t head[4] = {(uint8_t)len, (uint8_t)(len >> 8), (uint8_t)(len >> 16), (uint8_t)(len >> 24)};
+          if (len <= 0 || ss_spectrogram_payload((uint64_t)g.time_ms[k], g.frequency, g.sample_rate, row, g.size, payload.data(), len) != len ||
+              fwrite(head, 1, 4, rows_file) != 4 || fwrite(payload.data(), 1, (size_t)len, rows_file) != (size_t)len)
+            why = "writing the spectrogram payloads failed";
+          else ++spectrogram_rows;
+        }
       }
       if (!why.empty()) {
         std::lock_guard<std::mutex> lock(mtx);
@@ -242,12 +290,15 @@ int main(int argc, char** argv) {
              opt.path.c_str(), cfg.fft_size, cfg.decim, (long long)reader.items(), frames, batches, candidates, seconds,
              seconds > 0 ? (double)frames * cfg.fft_size / seconds / 1e6 : 0.0);
       if (tracked) printf(", \"transmissions\": %lld, \"tracked_frames\": %lld", transmissions, tracked_frames);
+      if (rows) printf(", \"spectrogram_rows\": %lld", spectrogram_rows);
       printf("}\n");
     }
   } catch (const std::exception& e) {
     fprintf(stderr, "%s\n", e.what());
     rc = 1;
   }
+  if (rows_file && fclose(rows_file) != 0) rc = 1;
+  sgf_destroy(rows);
   stf_destroy(tracked);
   ss_feed_destroy(feed);
   ss_destroy(ctx);

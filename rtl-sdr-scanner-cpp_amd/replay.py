@@ -21,6 +21,7 @@ import time
 import numpy as np
 
 from . import abi
+from .spectrogram import frame_payloads
 from .tracker import load_host_library
 
 KIND_CF32, KIND_CS8, KIND_CU8, KIND_F32, KIND_CS16 = 0, 1, 2, 3, 4
@@ -185,13 +186,20 @@ def engine_overrides_for(info: RawFileInfo) -> dict:
 
 
 def replay_file(engine, path: str, kind: int | None = None, batch: int | None = None, depth: int = 3, cand_cap: int = 1 << 20,
-                want_psd: bool = False, frame_period_ms: float | None = None, stats: ReplayStats | None = None, read_threads: int = 4):
+                want_psd: bool = False, frame_period_ms: float | None = None, stats: ReplayStats | None = None, read_threads: int = 4,
+                spectrogram=None, spectrogram_max_rows: int = 8):
     """Generator: streams the dump through ``engine`` (a SpectrumEngine whose in_format matches the file) and yields
     one result dict per batch, in order (copies: safe to keep). A reader thread fills pinned slots; up to ``depth - 1``
     batches are in flight behind the one being read.
 
     frame_period_ms: when given, frame k carries the timestamp round(k * period) — the clock the NoiseLearner's
-    2000 ms window runs on (noise_learner.cpp:23); otherwise learning counts ``learn_frames``."""
+    2000 ms window runs on (noise_learner.cpp:23); otherwise learning counts ``learn_frames``.
+
+    spectrogram: a callable taking bytes (a file's ``write``, say; the engine needs ``flags=SS_FLAG_SPECTROGRAM``). The feed then
+    delivers the spectrogram rows (``Feed.spectrogram``), and every row a batch closes is handed over as its
+    DataController::pushSpectrogram payload behind its length as a little-endian uint32, in order — the file
+    ``specscan_replay --spectrogram-out`` writes. The rows close on the frames' clock, so without ``frame_period_ms`` the
+    stream's own period, 1000 * fft_size * decim / sample_rate ms, is taken."""
     cfg = engine.cfg
     if kind is None:
         kind = parse_raw_file_name(path).kind
@@ -203,6 +211,11 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
         raise ValueError("batch must be in 1..max_batch")
     reader = RawIqReader(path, kind, cfg.fft_size, cfg.decim)
     feed = engine.feed(depth=depth, cand_cap=cand_cap, want_psd=want_psd)
+    rows = None
+    if spectrogram is not None:
+        rows = feed.spectrogram(max_rows=spectrogram_max_rows)
+        if frame_period_ms is None:
+            frame_period_ms = 1000.0 * cfg.fft_size * cfg.decim / cfg.sample_rate
     st = stats if stats is not None else ReplayStats()
     frame_bytes = cfg.fft_size * abi.SS_FMT_BYTES[want_fmt]
     submitted: queue.Queue = queue.Queue()
@@ -243,6 +256,9 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
             r = feed.collect()
             out = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
             out["first_frame"] = out.pop("tag")
+            if rows is not None:
+                for payload in rows.payloads():
+                    spectrogram(frame_payloads([payload]))
             free.release()
             st.frames += out["nframes"]
             st.batches += 1
@@ -256,5 +272,7 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
             free.release()  # unblock the reader if the consumer stopped early
         th.join(timeout=10)
         st.seconds = time.perf_counter() - t_start
+        if rows is not None:
+            rows.close()
         feed.close()
         reader.close()
