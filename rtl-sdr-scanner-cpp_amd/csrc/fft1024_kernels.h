@@ -8,17 +8,18 @@
 //   step A (k_fft_cols1024):      for every n2 the 1024-point FFT over n1, times W_N^(n2 k1)   -> work[k1 * 1024 + n2]
 //   step B (k_fft_rows1024_psd):  for every k1 the 1024-point FFT over n2 -> X[k1 + 1024 k2]   -> dB
 // What a workgroup of 8192 points can do about coalescing is bounded — C columns in and R rows out with C * R = 64 — so both
-// kernels sit in the middle: the column tiles are 8 columns wide (64-byte runs of CF32 in, 64-byte runs of the work buffer out),
-// the row tiles 8 rows (32-byte runs of dB values out), and the block index is decoded so that the tiles that share a 128-byte
-// line run on the same XCD at about the same time (block b runs on XCD b mod 8 — observed, not promised: it only matters for speed)
-// and meet in that XCD's L2.
+// kernels sit in the middle: the row tiles are 8 rows (32-byte runs of dB values out), and the block index is decoded so that the
+// tiles that share a 128-byte line run on the same XCD at about the same time (block b runs on XCD b mod 8 — observed, not
+// promised: it only matters for speed) and meet in that XCD's L2. The column tiles take 16 columns with 1024 threads: whole
+// 128-byte lines on either side. (They were 8 columns by 512 threads once and rode k_scan_step as its FFT role; the 16-column form
+// replaced that one, and it is gone: profiles/r04/s4_summary.txt has the figures.)
 //
 // A 1024-point FFT in registers is four interleaved 256-point FFTs (fft256_passes: two radix-16 passes, one exchange) and a
 // radix-4 step across them — n = 4 m + q: X[k' + 256 kap] = sum_q W_4^(q kap) W_1024^(q k') Z_q[k'] — with a second exchange
-// through LDS in between, the shape of k_fft256xR_psd<., 2>. 16 points per thread, 512 threads, <= 61 VGPRs, 39-40 KiB of LDS (the
-// W_256 and W_1024 tables sit there too: a table read from global memory waits behind the CU's streaming loads, fft8192_v2.h):
-// four workgroups per CU, and the column tile is the FFT role of k_scan_step (KIND 3) like the 256-point column tiles of the
-// other long transforms, the deferred detect / emit stages of earlier calls riding on its launch.
+// through LDS in between, the shape of k_fft256xR_psd<., 2>. 16 points per thread, <= 61 VGPRs; the row tile has 512 threads and
+// 39-40 KiB of LDS (the W_256 and W_1024 tables sit there too: a table read from global memory waits behind the CU's streaming
+// loads, fft8192_v2.h): four workgroups per CU, and it is the FFT role of k_scan_step (kStepRows1024) with the deferred detect /
+// emit stages of earlier calls riding on its launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,9 +32,8 @@ constexpr int kFft1024Pitch2 = 261;  // second exchange of the column tiles, [su
 constexpr int kFft1024ColsPlaneBytes = 32 * kFft256PitchCols * 4;                 // 34 944 (>= 32 x 261 words)
 constexpr int kFft1024RowsPlaneBytes = 1024 * 9 * 4;                              // 36 864: the read-out tile [k2][row], pitch 9 (>= 32 x 273 words)
 constexpr int kFft1024TableBytes = (256 + 256) * 8;                               // W_256 [16][16], then W_1024^k' [256]
-constexpr int kFft1024ColsLdsBytes = kFft1024ColsPlaneBytes + kFft1024TableBytes; // 39 040: fits k_scan_step's 39 936 (the column tiles are its FFT role, KIND 3)
 // the row tiles' tables sit behind the EXCHANGE plane; the read-out tile, which is larger, overlays the front of them once the
-// transform is done with them: 39 040 bytes, and the row tile fits k_scan_step's 39 936 (it is its FFT role, KIND 4)
+// transform is done with them: 39 040 bytes, and the row tile fits k_scan_step's 39 936 (it is its FFT role, kStepRows1024)
 constexpr int kFft1024RowsLdsBytes = kFft1024ColsPlaneBytes + kFft1024TableBytes;
 static_assert(kFft1024RowsPlaneBytes <= kFft1024RowsLdsBytes, "the read-out tile fits");
 static_assert(32 * kFft1024Pitch2 * 4 <= kFft1024ColsPlaneBytes && 32 * kFft256PitchCols * 4 <= kFft1024RowsPlaneBytes, "exchange planes");
@@ -68,7 +68,8 @@ __host__ __device__ inline void cols1024_block(int block, int logc, int* f, int*
 
 // Host side: the window taps in the column tiles' own order — out[(tile * threads + t) * 16 + r] = the tap of the sample thread t
 // of tile `tile` loads as its r-th (sample n1 = 4 (j + 16 r) + q of column tile * COLS + c; sub = t mod 4 COLS = c + COLS q,
-// j = t div 4 COLS). logc = 3 (8 columns, 512 threads) or 4 (16 columns, 1024 threads).
+// j = t div 4 COLS). logc = 4 (16 columns, 1024 threads) is what ss_create asks for; the formula, like cols1024_block's decode, holds
+// for logc = 3 (8 columns, 512 threads) too, and tests/host/index_check.cpp checks both.
 inline void fft1024_window_order(const float* win, float* out, int logc) {
   const int cols = 1 << logc, nsub = 4 * cols, threads = 16 * nsub, tiles = 1024 / cols;
   for (int tile = 0; tile < tiles; ++tile)
@@ -78,11 +79,10 @@ inline void fft1024_window_order(const float* win, float* out, int logc) {
     }
 }
 
-// One column tile: 8 columns x 1024 rows; `block` = frame * 128 + w. XCD (w mod 8) takes the 16 neighbouring tiles
-// [16 (w mod 8), 16 (w mod 8) + 16): two tiles that share the 128-byte lines of the frame and of the work buffer are consecutive
-// blocks of one XCD. `g`: ColsArgs of fft256_kernels.h with twc = the block of fft1024_host_tables (logn2 is 10).
-// LOGC = 3: 8 columns by 512 threads (above). LOGC = 4: 16 columns by 1024 threads — whole 128-byte lines on either side, twice
-// the LDS (two workgroups per CU: the same threads per CU); too many threads for a role of k_scan_step, so a launch of its own.
+// One column tile: 2^LOGC columns x 1024 rows; `block` = frame * (1024 >> LOGC) + w (cols1024_block). `g`: ColsArgs of
+// fft256_kernels.h with twc = the block of fft1024_host_tables (logn2 is 10).
+// LOGC = 4, the only form that is instantiated: 16 columns by 1024 threads — whole 128-byte lines on either side, 74 KiB of LDS (two
+// workgroups per CU); too many threads for a role of k_scan_step, so a launch of its own.
 // WCALC: the Hamming taps are not loaded but formed (ss_create: only for the default window). A thread's sixteen samples are
 // n = m + 65536 r with m = 1024 (4 j + q) + column < 65536, so
 //   w[n] = 0.54 - 0.46 cos(theta_m + phi_r) = 0.54 + (-0.46 cos phi_r) cos theta_m + (0.46 sin phi_r) sin theta_m,   theta_m = 2 pi m / (N - 1),  phi_r = 2 pi 65536 r / (N - 1):
@@ -104,7 +104,7 @@ inline void fft1024_window_rotation_table(float2* out) {
   }
 }
 
-template <int FMT, int LOGC = 3, bool WCALC = false>
+template <int FMT, int LOGC = 4, bool WCALC = false>
 __device__ __forceinline__ void fft_cols1024_tile(const ColsArgs& g, int block, unsigned char* __restrict__ smem_raw, int t) {
   constexpr int COLS = 1 << LOGC, NSUB = 4 * COLS, THREADS = 16 * NSUB, TILES = 1024 / COLS;
   float* s = reinterpret_cast<float*>(smem_raw);
@@ -212,14 +212,14 @@ __device__ __forceinline__ void fft_cols1024_tile(const ColsArgs& g, int block, 
   }
 }
 
-// Stand-alone launch (contexts without the step kernel; and the 16-column form).
-template <int FMT, int LOGC = 3, bool WCALC = false>
+// Stand-alone launch (the column half of every 2^20-point call whose launch does not carry the plan of the call before).
+template <int FMT, int LOGC = 4, bool WCALC = false>
 __global__ __launch_bounds__(64 << LOGC, 8) void k_fft_cols1024(ColsArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   fft_cols1024_tile<FMT, LOGC, WCALC>(g, (int)blockIdx.x, smem_raw, (int)threadIdx.x);
 }
 constexpr int fft1024_cols_lds_bytes(int logc) { return (4 << logc) * kFft256PitchCols * 4 + kFft1024TableBytes; }
-static_assert(fft1024_cols_lds_bytes(3) == kFft1024ColsLdsBytes && (4 << 4) * kFft1024Pitch2 <= (4 << 4) * kFft256PitchCols, "column tile LDS");
+static_assert((4 << 4) * kFft1024Pitch2 <= (4 << 4) * kFft256PitchCols, "column tile LDS");
 
 // An order-preserving key for atomic maxima of dB values: larger float <-> larger unsigned; 0 = nothing seen (below -inf),
 // 0xffffffff = NaN (wins: "cannot be bounded").

@@ -30,19 +30,20 @@
 // with each other and fill each other's ramps and tails.
 //
 // Transforms of 16384 points and more are four-step (fft256_kernels.h): their column half — tiles of 32 columns x 256 rows,
-// one per 512-thread workgroup — takes the FFT role's place (KIND 1, 2), the row half follows as a launch of its own, and
+// one per 512-thread workgroup — takes the FFT role's place (kStepCols, kStepColsWide), the row half follows as a launch of its own, and
 // the deferred stages ride on the column launch in the same way. 65536 points (what ships since round 4): a detect-mode call of up
-// to 128 frames is ONE launch (KIND 7) — the column tiles of call k (the FFT role) and, dispatched behind them, the row tiles of
+// to 128 frames is ONE launch (kStepMerged65536) — the column tiles of call k (the FFT role) and, dispatched behind them, the row tiles of
 // call k - 1 (ROLE_ROWS, from the other of two work buffers), with the PLAN of call k - 2 (which of its averaging tiles can hold a
 // candidate: ROLE_PLAN, two blocks of k_plan_long's numbering per workgroup), detect(k - 3) on the tiles its plan listed and
 // emit(k - 4) ahead of both: two rounds of workgroups whose phases overlap. Longer calls and calls that keep a plane take two
 // launches: the column launch of call k with the plan of call k - 1, detect(k - 2) and emit(k - 3), and the row half as the FFT role
-// of a launch of its own (KIND 6) that carries nothing else.
+// of a launch of its own (kStepRows256) that carries nothing else.
 // 2^20 points: 1024 x 1024 in two passes (fft1024_kernels.h) — the column half is a kernel of its own (1024 threads; the plan of the
-// call before runs in its first workgroups), the row half the FFT role here (KIND 4) with detect(k - 1) and emit(k - 2) riding on it.
+// call before runs in its first workgroups), the row half the FFT role here (kStepRows1024) with detect(k - 1) and emit(k - 2) riding on it.
 //
 // Workgroup = 512 threads, <= 64 VGPRs, 39 KiB of LDS (the FFT role's; two detect tiles need 35 KiB, eight emit lists
-// 32 KiB): four workgroups per CU whatever their roles.
+// 32 KiB): four workgroups per CU whatever their roles. The forms the kernel is compiled in — which transform the FFT role is and
+// what rides along — are the table below (kStep...).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,9 +53,12 @@
 #include "fft256_kernels.h"
 #include "fft8192_v2.h"
 
-// KIND 8 (65536 points, the radix-8 fold): workgroups per frame — 4: two residues each (one fold for both, 128 registers, four waves per
+// kStepFold8 (65536 points, the radix-8 fold): workgroups per frame — 4: two residues each (one fold for both, 128 registers, four waves per
 // SIMD); 8: one residue each (64 registers, eight waves per SIMD). Build-time so that the two can be timed against each other
-// (scripts/build_ab.py).
+// (scripts/build_ab.py). (One residue each for SHORT calls only, picked per call, was KIND 11: tried because the 4 x frames
+// two-residue workgroups of a short call leave most of the chip's 256 CUs idle for 18 us each, measured in round 6 and removed — a
+// workgroup folds the WHOLE frame for one residue as for two and lives as long: 16-frame calls 20.6 against 19.5 us, 32-frame calls
+// 26.0 against 20.3, profiles/r06/s13_summary.txt.)
 #ifndef SS_DIF8_W
 #define SS_DIF8_W 4
 #endif
@@ -66,22 +70,75 @@
 
 namespace ss {
 
+// The forms of k_scan_step: its template parameter KIND. The number is part of every kernel's name — profiles, bench.py and the
+// resource tests know the kernels by it — so a form keeps its number for good, and 3 and 11 stay unused: they were the 8-column tile of
+// 2^20-point frames as the FFT role and the radix-8 fold with one residue per workgroup, both measured, superseded and removed, and
+// old profiles still name them. Schedules (which earlier calls' stages a launch carries) are those of stage_slots.h; "deep" is the
+// 8192-point form of its own (ss_ctx::deep). Every form also runs as a drain, without its FFT role.
+//
+//  KIND name              points          FFT role (one work item)                      rides along                               schedule
+//  ---- ----------------- --------------- --------------------------------------------- ----------------------------------------- ---------------
+//     0 kStepFrames       8192            a whole frame: FFT + dB (fft8192_v2.h)        tile plan, detect, emit (a wave a frame)  PLAIN, deep
+//     1 kStepCols         16384, 32768    256-point column tile (fft256_kernels.h);     plan (plan_long_run), detect, emit (a     PLAIN
+//                                         the rows are the next launch                  wave a frame)
+//     2 kStepColsWide     65536 and more  the same                                      the same with the wide emit role          PLAIN, DET_LAG2
+//     4 kStepRows1024     2^20            1024-point ROW tile (fft1024_kernels.h); the  detect, wide emit                         PLAIN
+//                                         columns, with the plan, are the launch before
+//     5 kStepDrain1024    2^20            none: the drains of kStepRows1024             detect (the plan's list shared out in a   PLAIN
+//                                                                                       loop: StepArgs::list_loop), wide emit
+//     6 kStepRows256      65536           256-point ROW tile (fft_rows256_tile); the    detect, wide emit (in the product's       DET_LAG2, PLAIN
+//                                         columns are the launch before                 schedule: nothing)
+//     7 kStepMerged65536  65536           256-point column tile of call k               ROLE_ROWS: the 256-point row tiles of     MERGED
+//                                                                                       call k - 1; plan (plan_long_run), detect,
+//                                                                                       wide emit
+//     8 kStepFold8        65536, int8     two residues of a frame: radix-8 fold +       plan (plan_dif8_run), detect (tiles in    DET_LAG2
+//                                         8192-point transforms + dB, no work buffer    the fold's row order), wide emit
+//                                         (fft65536_dif8.h); 128 registers
+//     9 kStepFold16       131072, int8    the same at radix 16                          the same                                  DET_LAG2
+//    10 kStepColsX256     262144          256-point column tile                         plan (plan_x256_run), detect, wide emit   DET_LAG2
+//    12 kStepMergedX256   262144          256-point column tile of call k               ROLE_ROWS: the 1024-point row tiles of    MERGED
+//                                                                                       call k - 1; plan (plan_x256_run), detect,
+//                                                                                       wide emit
+constexpr int kStepFrames = 0, kStepCols = 1, kStepColsWide = 2, kStepRows1024 = 4, kStepDrain1024 = 5, kStepRows256 = 6, kStepMerged65536 = 7,
+              kStepFold8 = 8, kStepFold16 = 9, kStepColsX256 = 10, kStepMergedX256 = 12;
+
+// What the kernel branches on, per form. (A property that is a role gets an instantiation of its own so that the others keep their
+// registers: a role nobody can take still costs the kernel its registers.)
+constexpr bool step_is_long(int kind) { return kind != kStepFrames; }  // a long transform: the detect stage's tiles come from k_plan_long's list
+constexpr bool step_is_fold(int kind) { return kind == kStepFold8 || kind == kStepFold16; }
+// the plan role: none (the plan runs elsewhere — at the front of the column launch before), the 8192-point tile plan (plan_tiles), or two
+// blocks of a long transform's plan per workgroup by one of three routines
+enum { PLAN_NONE = 0, PLAN_TILES = 1, PLAN_LONG = 2, PLAN_FOLD = 3, PLAN_X256 = 4 };
+constexpr int step_plan_routine(int kind) {
+  return kind == kStepFrames                                                      ? PLAN_TILES
+         : kind == kStepCols || kind == kStepColsWide || kind == kStepMerged65536 ? PLAN_LONG  // plan_long_run
+         : step_is_fold(kind)                                                     ? PLAN_FOLD  // plan_dif8_run (the fold's rows: layout 2)
+         : kind == kStepColsX256 || kind == kStepMergedX256                       ? PLAN_X256  // plan_x256_run (262144 points: layout 3)
+                                                                                  : PLAN_NONE;
+}
+// the emit role: rows of 2048 mask words and more, the eight waves share one frame (false: one wave per frame)
+constexpr bool step_emit_wide(int kind) { return kind != kStepFrames && kind != kStepCols; }
+// ROLE_ROWS, the row half of the call before beside the column half of this one: its tile's points (0: the form has no such role)
+constexpr int step_row_role(int kind) { return kind == kStepMerged65536 ? 256 : kind == kStepMergedX256 ? 1024 : 0; }
+// detect_tile's layout argument: where a tile's rows sit (3, 4: the radix-8 / radix-16 fold's blocked order; 0: natural order)
+constexpr int step_detect_layout(int kind) { return kind == kStepFold8 ? 3 : kind == kStepFold16 ? 4 : 0; }
+
 struct StepArgs {
-  Fft8192Args fft;  // KIND 0: 8192-point frames
-  // KIND 0, deep pipelining (specscan.hip): FFT role frames [0, n_halo) are the last n_halo frames of the PREVIOUS call,
+  Fft8192Args fft;  // kStepFrames: 8192-point frames (the folds: the transform's tables and the rows' place)
+  // kStepFrames, deep pipelining (specscan.hip): FFT role frames [0, n_halo) are the last n_halo frames of the PREVIOUS call,
   // transformed again into a buffer of this launch's own, so that no stage has to read what the launch before wrote
   const void* halo_iq;  // first of those frames
   float* halo_psd;      // [n_halo][8192]
   float* halo_segsum;   // [32][kHaloSegPitch]: the halo frames' per-column maxima (null: none wanted)
   int n_halo;
-  Rows256Args rows256;  // KIND 6: 256-point ROW tiles of a long transform (fft256_kernels.h: fft_rows256_tile) — 65536 points with tile culling: the column half is a launch of its own right before, the plan of the call before at its front
-  Rows1024Args rows;  // KIND 4: 1024-point ROW tiles of a 2^20-point frame (fft1024_kernels.h) — the column half, 1024 threads per tile, is a launch of its own right before
-  ColsArgs cols;    // KIND 1, 2: 256-point column tiles of a long transform (fft256_kernels.h); KIND 3: 1024-point column tiles of a 2^20-point frame (fft1024_kernels.h)
+  Rows256Args rows256;  // kStepRows256 (the FFT role), kStepMerged65536 (ROLE_ROWS): 256-point ROW tiles of a 65536-point frame (fft256_kernels.h: fft_rows256_tile)
+  Rows1024Args rows;  // kStepRows1024 (the FFT role), kStepMergedX256 (ROLE_ROWS): 1024-point ROW tiles (fft1024_kernels.h)
+  ColsArgs cols;    // the column forms: 256-point column tiles of a long transform (fft256_kernels.h)
   DetectArgs det;
   EmitArgs emit;
-  int n_fft;   // frames (KIND 0, n_halo included) or column tiles (KIND 1) of the FFT role (0: role absent)
+  int n_fft;   // work items of the FFT role: frames (kStepFrames, n_halo included), column or row tiles, the folds' residue pairs (0: role absent)
   int n_det;   // detect TILES (two per workgroup)
-  // KIND 0, tile culling (detect_fused.h): the n_plan tiles of `det` are PLANNED by S = 32 / plan_cols plan workgroups,
+  // kStepFrames, tile culling (detect_fused.h): the n_plan tiles of `det` are PLANNED by S = 32 / plan_cols plan workgroups,
   // dispatched first, each listing those tiles of its plan_cols tile columns that must be evaluated; consumer p serves list
   // p mod S, entries 2 (p div S) and the next. Consumers are the launch's FFT workgroups once their frame is done
   // (plan_by_fft: the host makes sure there are enough of them) or, in a launch without an FFT role, detect workgroups of
@@ -93,7 +150,7 @@ struct StepArgs {
   // workgroup i is consumer plan_first + i): they wait for the plan at the START of the launch and evaluate their pair while the
   // frames stream — an FFT workgroup that finds a pair behind its frame lives twice as long as its neighbours.
   int plan_first;
-  // KIND 1, 2, tile culling (k_plan_long): the launch's column workgroups take the pairs of the detect stage's list once their
+  // long transforms, tile culling (k_plan_long): the launch's FFT workgroups take the pairs of the detect stage's list once their
   // tile is done, pair p to column workgroup p; detect workgroups of their own only for the pairs beyond (n_det counts those).
   // (Evaluated BEFORE the column tile the same pairs cost the launch 5 us more: the workgroups that find one finish last. And
   // without k_plan_long — every workgroup testing its own pair from the run maxima after its column tile: 360 values, five
@@ -106,37 +163,22 @@ struct StepArgs {
   // serves pair i (and leaves at once when the list is shorter), FFT workgroup p pair list_first + p, detect workgroup
   // i >= list_first pair n_fft + i.
   int list_first;
-  // KIND 5 — launches without an FFT role of a 2^20-point context (the drain of its deferred stages): the
+  // kStepDrain1024 — launches without an FFT role of a 2^20-point context (the drain of its deferred stages): the
   // detect workgroups share k_plan_long's list out in a loop, pair item, item + W, item + 2 W, ... — a workgroup per POSSIBLE pair
   // (4096 of them, of which a few dozen find one) cost the launch 17 us in dispatch alone
   int list_loop;
-  // KIND 1, 2 — a long transform's PLAN as a role (k_plan_long's blocks, two to a workgroup: block 2 item + tid / 256): 65536 points
-  // with tile culling, where the plan of call k - 1 rides at the front of the column launch of call k together with emit(k - 2), and
-  // the detect stage it plans on the row launch right behind (KIND 6). 0: no such role.
+  // a long transform's PLAN as a role (step_plan_routine: k_plan_long's blocks, two to a workgroup: block 2 item + tid / 256). 0: no such role.
   int n_plan_long;  // workgroups
   PlanLongDet plan_det;
   PlanLongArgs plan_long;
-  // KIND 7 — 65536 points, ONE launch per call (what ships for detect-mode calls of up to 128 frames): the column tiles of call k (the FFT role)
-  // beside the ROW tiles of call k - 1 (ROLE_ROWS: rows256, n_rows of them, reading the other of two work buffers), the plan of call
-  // k - 2, detect(k - 3) and emit(k - 4). 0: no such role.
+  // ROLE_ROWS (step_row_role): the row tiles of call k - 1, read from the other of two work buffers. 0: no such role.
   int n_rows;
-  // KIND 8 — 65536 points, int8 IQ, NO work buffer: the FFT role is TWO residues of a frame, r and r + 4 — the radix-8 fold in the load
-  // stage of the 8192-point transform, once for both, then the transform twice (fft65536_dif8.h: dif8_front2; 128 registers, so this
-  // instantiation runs four waves per SIMD) —, four workgroups per frame, n_fft = 4 x frames, item j -> dif8_item<4> — whose rows (dB
-  // values in the fold's blocked order: `fft.psd` is the ring's buffer) and run maxima the detect
-  // stage of two calls later reads; the plan of call k - 1, detect(k - 2) (PERM8 tiles) and emit(k - 3) ride on the launch as they ride
-  // on the column launch of the four-step form (KIND 2). `fft` carries the transform's tables and the rows' place, `dif` the fold's.
-  // KIND 9 — the same for 131072-point frames (what getFft picks at 20 MS/s): radix 16, residues r and r + 8 per workgroup, n_fft = 8 x frames.
-  // KIND 11 — KIND 8 with ONE residue per workgroup (fft65536_dif8.h: dif8_front, 64 registers, eight waves per SIMD), n_fft = 8 x frames: tried
-  // for short calls, whose 4 x frames two-residue workgroups leave most of the chip's 256 CUs idle for 18 us each (round 6) — no gain: a
-  // workgroup folds the WHOLE frame for one residue as for two and lives as long (SS_DIF8_SINGLE_MAX of the diagnostics build).
-  // KIND 12 — 262144 points, ONE launch per call (round 6): KIND 10's roles and the 1024-point ROW tiles of call k - 1 (ROLE_ROWS: `rows`, n_rows of
-  // them, from the other of two work buffers) behind the column tiles of call k — KIND 7's shape with this size's row tile and plan.
-  // KIND 10 — 262144 points (round 6): KIND 2 — 256-point column tiles as the FFT role, the plan of call k - 1, detect(k - 2), emit(k - 3) —
-  // whose plan role is plan_x256_run (PlanLongArgs::layout 3); an instantiation of its own so that the others keep their registers.
+  // the folds: item j -> dif8_item, n_fft = 4 x frames at radix 8 (residues r and r + 4 by one workgroup: one fold for both, then the
+  // transform twice — dif8_front2) and 8 x frames at radix 16 (r and r + 8). The rows are dB values in the fold's blocked order
+  // (`fft.psd` is the ring's buffer); the detect stage of two calls later reads them and their run maxima.
   Dif8Front dif;
   int n_emit;  // frames of the emit role
-  int emit_per_wg;  // 8: one wave per frame; 1 (KIND 2): rows of 2048 mask words and more, the eight waves share one frame
+  int emit_per_wg;  // 8: one wave per frame; 1 (step_emit_wide): rows of 2048 mask words and more, the eight waves share one frame
   // One workgroup per work item, dispatched in blockIdx order, four resident per CU. WHICH item a workgroup takes decides
   // what shares a CU when: `order` (device memory, one word per workgroup: role << 24 | item) is built by the host once
   // per launch shape. A launch with one role only passes null (items in blockIdx order). (Tried and dropped: the order as
@@ -159,7 +201,7 @@ constexpr int kStepThreads = 512;
 constexpr int kStepLdsBytes = kFft8192V2LdsBytes;
 static_assert(2 * (16 * DetectTile<21, 21, 16, 256>::P * 4 + 64) <= kFft8192V2LdsBytes, "two detect tiles per workgroup");
 static_assert((8 * kEmitList + 9) * 4 <= kFft8192V2LdsBytes, "eight emit lists per workgroup");
-static_assert(kFft256ColsLdsBytes <= kFft8192V2LdsBytes && kFft1024ColsLdsBytes <= kFft8192V2LdsBytes && kFft1024RowsLdsBytes <= kFft8192V2LdsBytes && kFft256RowsPsdLdsBytes <= kFft8192V2LdsBytes, "a column / row tile");
+static_assert(kFft256ColsLdsBytes <= kFft8192V2LdsBytes && kFft1024RowsLdsBytes <= kFft8192V2LdsBytes && kFft256RowsPsdLdsBytes <= kFft8192V2LdsBytes, "a column / row tile");
 static_assert((kPlanLdsFloats + 64) * 4 <= kFft8192V2LdsBytes, "a plan workgroup's staging area");
 static_assert(2 * (kPlanFusedFloats + kPlanLongInts) * 4 <= kFft8192V2LdsBytes, "two blocks of a long transform's plan");
 static_assert(kPlanDif8Floats <= kPlanFusedFloats && kPlanDif8Floats <= kPlanLongFloats, "a block of the fold's plan in a plan block's LDS");
@@ -188,20 +230,15 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
   // as it is known; the plan this workgroup makes (-1: none) — its own as a plan workgroup, or its list's when it has waited for
   // the plan workgroup in vain (detect_fused.h: nothing in a launch waits without bound)
   int consumer = -1, word = 0, plan_seg = -1;
-  if constexpr (KIND == 7) {  // (only this instantiation knows the role: the others keep their registers)
-    if (role == ROLE_ROWS) {
-      fft_rows256_tile(a.rows256, item, smem_raw, tid);  // the row half of the call before: its column half ran in the launch before
-      return;
-    }
-  }
-  if constexpr (KIND == 12) {  // 262144 points, one launch per call: the same with the 1024-point row tile (StepArgs::rows)
-    if (role == ROLE_ROWS) {
-      fft_rows1024_tile<8>(a.rows, item, smem_raw, tid);
+  if constexpr (step_row_role(KIND) != 0) {  // (only these instantiations know the role: the others keep their registers)
+    if (role == ROLE_ROWS) {  // the row half of the call before: its column half ran in the launch before
+      if constexpr (step_row_role(KIND) == 256) fft_rows256_tile(a.rows256, item, smem_raw, tid);
+      else fft_rows1024_tile<8>(a.rows, item, smem_raw, tid);  // (262144 points: StepArgs::rows)
       return;
     }
   }
   if (role == ROLE_EMIT) {
-    if constexpr (KIND >= 2) {
+    if constexpr (step_emit_wide(KIND)) {
       // ---- emit role, long rows: the eight waves share one frame ----
       cand_emit_frame_wide<8>(a.emit, item, tid, reinterpret_cast<int*>(smem_raw));
     } else {
@@ -212,7 +249,7 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
     }
   } else if (role == ROLE_DET) {
     // ---- detect role: two tiles ----
-    if constexpr (KIND == 5) {  // (an instantiation of its own: a loop around the tile evaluation costs every role of a kernel registers)
+    if constexpr (KIND == kStepDrain1024) {  // (an instantiation of its own: a loop around the tile evaluation costs every role of a kernel registers)
       if (a.det.tile_list && a.list_loop) {
         using T = DetectTile<21, 21, 16, 256>;
         const int n_tiles = (a.det.n / 256) * plan_frame_tiles(a.det.nframes, a.det.shift);
@@ -233,9 +270,9 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
         return;
       }
     }
-    if (KIND == 0 && a.n_plan) {  // the planned stage's lists (a launch without an FFT role)
+    if (!step_is_long(KIND) && a.n_plan) {  // the planned stage's lists (a launch without an FFT role)
       consumer = item;
-    } else if (KIND >= 1 && a.det.tile_list) {
+    } else if (step_is_long(KIND) && a.det.tile_list) {
       // long transforms: the tiles k_plan_long listed. With an FFT role in the launch its workgroups take pairs 0 .. n_fft - 1
       // (below) and the detect workgroups the pairs beyond (calls that are no multiple of 16 frames have a few); without one,
       // a workgroup per possible pair. Workgroups beyond the list's end leave at once.
@@ -245,22 +282,23 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
       tile_b = 2 * item + 1 < a.n_det ? 2 * item + 1 : -1;
     }
   } else if (role == ROLE_PLAN) {
-    if constexpr (KIND == 1 || KIND == 2 || KIND == 7 || KIND == 8 || KIND == 9 || KIND == 10 || KIND == 11 || KIND == 12) {  // a long transform's plan: two blocks of k_plan_long's numbering
+    constexpr int PLAN = step_plan_routine(KIND);
+    if constexpr (PLAN == PLAN_LONG || PLAN == PLAN_FOLD || PLAN == PLAN_X256) {  // a long transform's plan: two blocks of k_plan_long's numbering
       const int sub = tid >> 8;
       float* mrow = reinterpret_cast<float*>(smem_raw) + sub * (kPlanFusedFloats + kPlanLongInts);
-      if constexpr (KIND == 8 || KIND == 9 || KIND == 11) plan_dif8_run<21, 21, 16, 256>(a.plan_det, a.plan_long, 2 * item + sub, tid & 255, mrow, reinterpret_cast<int*>(mrow + kPlanFusedFloats));  // (the fold's rows: layout 2)
-      else if constexpr (KIND == 10 || KIND == 12) plan_x256_run<21, 21, 16, 256>(a.plan_det, a.plan_long, 2 * item + sub, tid & 255, mrow, reinterpret_cast<int*>(mrow + kPlanFusedFloats));  // (262144 points: layout 3)
+      if constexpr (PLAN == PLAN_FOLD) plan_dif8_run<21, 21, 16, 256>(a.plan_det, a.plan_long, 2 * item + sub, tid & 255, mrow, reinterpret_cast<int*>(mrow + kPlanFusedFloats));
+      else if constexpr (PLAN == PLAN_X256) plan_x256_run<21, 21, 16, 256>(a.plan_det, a.plan_long, 2 * item + sub, tid & 255, mrow, reinterpret_cast<int*>(mrow + kPlanFusedFloats));
       else plan_long_run<21, 21, 16, 256>(a.plan_det, a.plan_long, 2 * item + sub, tid & 255, mrow, reinterpret_cast<int*>(mrow + kPlanFusedFloats));
       return;
     }
-    if constexpr (KIND == 0) plan_seg = item;
+    if constexpr (PLAN == PLAN_TILES) plan_seg = item;
 #ifdef SS_DIAG
     if (a.hint_mode == 3) plan_seg = -1;  // test switch: the plan workgroups never publish anything — every consumer has to help itself
 #endif
-  } else if constexpr (KIND >= 1) {
-    // ---- FFT role, long transforms: one tile of 32 columns x 256 rows (KIND 3: 8 columns x 1024 rows of a 2^20-point frame) ----
-    if constexpr (KIND == 5) return;  // (the drain of a 2^20-point context: launches without an FFT role only)
-    else if constexpr (KIND == 8) {  // a residue of a 65536-point frame: fold + 8192-point transform + dB -> the ring's rows
+  } else if constexpr (step_is_long(KIND)) {
+    // ---- FFT role, long transforms: a row tile, the folds' pair of residues, or one tile of 32 columns x 256 rows ----
+    if constexpr (KIND == kStepDrain1024) return;  // (the drain of a 2^20-point context: launches without an FFT role only)
+    else if constexpr (KIND == kStepFold8) {  // a residue of a 65536-point frame: fold + 8192-point transform + dB -> the ring's rows
       if constexpr (fmt_int8(FMT)) {
         int f, r, hdr;
         dif8_item<SS_DIF8_W>(item, a.dif.nframes, &f, &r);  // (W = 4: residues r and r + 4 by this workgroup)
@@ -270,23 +308,15 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
         fft8192_v2_frame<FMT, 2, true, false, SS_DIF8_W == 4 ? (SS_DIF8_BFLY ? 5 : 3) : 2>(a.fft, (size_t)(8 * (f - a.dif.first_hist) + r), smem_raw, tid, &hdr, &a.dif, (size_t)f, r);
       }
     }
-    else if constexpr (KIND == 11) {  // a 65536-point frame's residue r alone: eight workgroups per frame (short calls, round 6)
-      if constexpr (fmt_int8(FMT)) {
-        int f, r, hdr;
-        dif8_item<8>(item, a.dif.nframes, &f, &r);
-        fft8192_v2_frame<FMT, 2, true, false, 2>(a.fft, (size_t)(8 * (f - a.dif.first_hist) + r), smem_raw, tid, &hdr, &a.dif, (size_t)f, r);
-      }
-    }
-    else if constexpr (KIND == 9) {  // 131072 points, radix 16: residues r (< 8) and r + 8 of a frame, eight workgroups per frame
+    else if constexpr (KIND == kStepFold16) {  // 131072 points, radix 16: residues r (< 8) and r + 8 of a frame, eight workgroups per frame
       if constexpr (fmt_int8(FMT)) {
         int f, r, hdr;
         dif8_item<8>(item, a.dif.nframes, &f, &r);
         fft8192_v2_frame<FMT, 2, true, false, SS_DIF8_BFLY ? 6 : 4>(a.fft, (size_t)(16 * (f - a.dif.first_hist) + r), smem_raw, tid, &hdr, &a.dif, (size_t)f, r);
       }
     }
-    else if constexpr (KIND == 6) fft_rows256_tile(a.rows256, item, smem_raw, tid);  // (the ROW half of call k: its column half ran as its own launch right before)
-    else if constexpr (KIND == 4) fft_rows1024_tile(a.rows, item, smem_raw, tid);  // (the ROW half of call k: its column half ran as its own launch right before)
-    else if constexpr (KIND == 3) fft_cols1024_tile<FMT>(a.cols, item, smem_raw, tid);
+    else if constexpr (KIND == kStepRows256) fft_rows256_tile(a.rows256, item, smem_raw, tid);  // (the ROW half of call k: its column half ran as its own launch right before)
+    else if constexpr (KIND == kStepRows1024) fft_rows1024_tile(a.rows, item, smem_raw, tid);  // (the ROW half of call k: its column half ran as its own launch right before)
     else fft_cols256_tile<FMT>(a.cols, item, smem_raw, tid);
     // ... then this workgroup's share of the tiles k_plan_long listed for the detect stage that rides on the launch. (The other
     // way round — the pairs first, while the memory system is still idle, then the column tile — was 5 us slower per launch at
@@ -315,7 +345,7 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
       word = hdr;
     }
   }
-  if constexpr (KIND == 0) {
+  if constexpr (!step_is_long(KIND)) {
     // ---- the planned stage's lists: consumer `consumer` serves list consumer mod nseg, entries 2 (consumer div nseg) and the next ----
     // Everything that decides a branch here is workgroup-uniform: the header word came out of LDS (or is still unknown for the
     // whole workgroup), and where somebody has to wait the first wave waits — a bounded number of polls — and tells the others
@@ -365,7 +395,7 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
       if (tile_a >= 0) __syncthreads();  // the frame's (or the plan's) last LDS reads are done
     }
   }
-  if constexpr (KIND >= 1) {
+  if constexpr (step_is_long(KIND)) {
     if (list_pair_no >= 0) {
       // (a tile number that is none must not become an address; the slot behind an odd count is not an entry)
       // (count and entries asked for together, the entries at an always-legal place — the list holds n_tiles + 2 words: one round trip
@@ -390,12 +420,12 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
     float* tile = reinterpret_cast<float*>(smem_raw) + half * (16 * T::P + 16);
     int* cnt = reinterpret_cast<int*>(tile + 16 * T::P);
     const int mine = half ? tile_b : tile_a;
-    detect_tile<21, 21, 16, 256, SPEC, (KIND == 8 || KIND == 11) ? 3 : KIND == 9 ? 4 : 0>(a.det, mine < 0 ? tile_a : mine, tid & 255, tile, cnt, mine >= 0);
+    detect_tile<21, 21, 16, 256, SPEC, step_detect_layout(KIND)>(a.det, mine < 0 ? tile_a : mine, tid & 255, tile, cnt, mine >= 0);
   }
 }
 
-template <int FMT, bool SPEC, int TW = 2, bool SWZ = true, bool PRIO = false, int KIND = 0>
-__global__ __launch_bounds__(kStepThreads, ((KIND == 8 && SS_DIF8_W == 4) || KIND == 9) ? 4 : 8) void k_scan_step(StepArgs a_by_value) {
+template <int FMT, bool SPEC, int TW = 2, bool SWZ = true, bool PRIO = false, int KIND = kStepFrames>
+__global__ __launch_bounds__(kStepThreads, ((KIND == kStepFold8 && SS_DIF8_W == 4) || KIND == kStepFold16) ? 4 : 8) void k_scan_step(StepArgs a_by_value) {
   // The arguments are read where they are used, straight from the kernel-argument segment (scalar loads from constant
   // memory): taken from the by-value parameter they are all loaded at the top of the kernel and kept alive through every
   // role — hundreds of scalar registers spilled into vector registers the 64-VGPR budget does not have.
@@ -416,7 +446,7 @@ __global__ __launch_bounds__(kStepThreads, ((KIND == 8 && SS_DIF8_W == 4) || KIN
 #ifndef SS_ORDER_FFT_FIRST  // (A/B builds, scripts/build_ab.py: 1 = plan, FFT, emit, detect, rows — the frames ahead of the candidate lists)
 #define SS_ORDER_FFT_FIRST 0
 #endif
-    if (SS_ORDER_FFT_FIRST && KIND == 0) {
+    if (SS_ORDER_FFT_FIRST && KIND == kStepFrames) {
       if (b < np) {
         role = ROLE_PLAN;
       } else if ((b -= np) < a.n_fft) {

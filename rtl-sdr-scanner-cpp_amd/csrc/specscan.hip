@@ -108,7 +108,6 @@ struct ss_ctx {
     int fft_sub = -1;              // 0 never / 1 always split N2 > 256 rows into radix-A step + 256-point rows (-1: from 2048)
     bool fft_twopass = true;       // 2^20 points as 1024 x 1024 in two passes (SS_FFT_TWOPASS=0: 256 x 4096 in three, as until round 3)
     bool ring_only = true;         // 2^20 points, detect mode, calls shorter than the ring: no dB plane is written (SS_RING_ONLY=0: written as ever)
-    bool cols1024_wide = true;     // 2^20 points: column tiles of 16 columns by 1024 threads as a launch of their own, the deferred stages in a launch without an FFT role (SS_C1024_WIDE=0: 8 columns by 512 threads as k_scan_step's FFT role, KIND 3)
     bool fft_xcd_map = true;       // XCD-aware tile order in k_fft_rows256xR_psd
     bool spec_standalone = false;  // spectrogram by its own two kernels instead of inside the detect tiles
     bool pipeline = true;          // 8192 points: defer detect / emit of a call into the next calls' launches (scan_step.h)
@@ -147,9 +146,7 @@ struct ss_ctx {
     int plan_first = 0;            // 8192 points: the first plan_first pairs of every list of the launch's tile plan on detect workgroups of their own ahead of the FFT role (SS_PLAN_FIRST=n; 0: every pair behind an FFT workgroup's frame)
     bool rows1024x256 = true;      // 262144 points (what getFft picks at 61.44 MS/s): rows through the 1024-point row tile with run maxima and ring rows — culled, no dB plane in detect mode, the 65536-point two-launch pipeline (SS_ROWS1024X256=0: round 2's path, k_fft_rows256xR_psd, every tile evaluated)
     long long abs_start = 0;       // SS_ABS_START=n: the frame counter starts at n instead of 0 at creation and after ss_reset — sessions that cross 2^30 frames (the counter's 30-bit form indexes the long transforms' run maxima) without the twenty seconds of scanning it takes to get there (tests/test_gpu_cull.py)
-    int drain_waiter_us = 0;       // 8192 points, deep pipelining (SS_DRAIN_WAITER_US=n): the drain's join behind a waiter on the public stream that sleeps at most n us (drain_deep) — measured in round 6 and not kept: 25.3-26.5 against 25.7-26.5 us per step with it, profiles/r06/s19_summary.txt
-    bool drain_tail_event = true;  // ... an event recorded behind the drain's last command on the public stream (SS_DRAIN_TAIL_EVENT=0: none, as until session 18 of round 6): the 20-step form 25.2 against 25.85 us per step, medians of eight alternating runs (s20)
-    int dif8_single_max = 0;       // 65536 points, the fold: calls of up to this many frames take ONE residue per workgroup (scan_step.h KIND 11; SS_DIF8_SINGLE_MAX=n) — measured in round 6 and not kept: a workgroup folds the whole frame whether it wants one residue of it or two, so it lives as long either way (16-frame calls 20.6 against 19.5 us, 32-frame calls 26.0 against 20.3: profiles/r06/s13_summary.txt)
+    bool drain_tail_event = true;  // 8192 points, deep pipelining: an event recorded behind the drain's last command on the public stream (SS_DRAIN_TAIL_EVENT=0: none, as until session 18 of round 6): the 20-step form 25.2 against 25.85 us per step, medians of eight alternating runs (s20)
     int chunk_65536 = 256;         // 65536 points with tile culling: calls of more frames go through in chunks of this many (SS_CHUNK_65536=0: in one piece)
     int chunk_long = 16;           // 2^20 points in two passes: calls of more frames go through in chunks of this many (SS_CHUNK_LONG=0: in one piece)
     bool halo_maxima = true;       // 8192 points, deep pipelining: the re-transformed halo frames leave per-column maxima, so that the tiles of a batch's first two frame tiles are tested like the others (SS_HALO_MAXIMA=0: evaluated whatever they hold, as until session 36 of round 5)
@@ -198,7 +195,6 @@ struct ss_ctx {
       fft_sub = tri("SS_FFT_SUB");
       fft_twopass = tri("SS_FFT_TWOPASS") != 0;
       ring_only = tri("SS_RING_ONLY") != 0;
-      cols1024_wide = tri("SS_C1024_WIDE") != 0;
       fft_xcd_map = tri("SS_FFT_XCDMAP") != 0;
       spec_standalone = is("SS_SPEC_IMPL", "standalone");
       pipeline = tri("SS_PIPELINE") != 0;
@@ -221,8 +217,6 @@ struct ss_ctx {
       chunk_long = num("SS_CHUNK_LONG", chunk_long);
       chunk_65536 = num("SS_CHUNK_65536", chunk_65536);
       rows1024x256 = tri("SS_ROWS1024X256") != 0;
-      dif8_single_max = num("SS_DIF8_SINGLE_MAX", dif8_single_max);
-      drain_waiter_us = num("SS_DRAIN_WAITER_US", drain_waiter_us);
       if (const char* v = getenv("SS_ABS_START")) abs_start = atoll(v);
       drain_tail_event = tri("SS_DRAIN_TAIL_EVENT") != 0;
       plan_first = num("SS_PLAN_FIRST", plan_first);
@@ -389,8 +383,6 @@ struct ss_ctx {
   int nq = 2;
   hipStream_t s_ab[kMaxQueues] = {};
   hipEvent_t ev_launch[32] = {}, ev_in[4] = {}, ev_join[kMaxQueues] = {}, ev_tail = nullptr;
-  unsigned* d_drain_done = nullptr;  // drain_deep: counts the queues' "my last stage has run" signals since ss_create (k_drain_signal), the waiter's word
-  unsigned drain_signals = 0;        // ... how many have been enqueued
   float* d_halo[2 * kMaxQueues] = {};  // [kHistRows][n] each: written by launch L, read by detect(L) in launch L + nq
   const void* deep_prev_iq = nullptr;  // the previous call's frames (caller's buffer: untouched until ss_sync by contract)
   long long deep_prev_stride = 0;
@@ -706,8 +698,8 @@ ss::ColsArgs cols256_args(ss_ctx* c, const void* d_iq, long long item_stride) {
   return g;
 }
 
-// N = 2^20 in two passes (fft1024_kernels.h): the column tiles are k_scan_step's FFT role (KIND 3) or, for contexts without the
-// step kernel, a launch of their own; the rows follow as their own launch either way.
+// N = 2^20 in two passes (fft1024_kernels.h): the column tiles are a launch of their own, and the rows follow as theirs (contexts
+// with the step kernel: as its FFT role).
 // frame0: the first of these frames within its call (a call of many frames goes through in chunks, run_batch)
 template <int FMT>
 void launch_cols1024_fmt(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, int frame0 = 0) {
@@ -720,7 +712,7 @@ void launch_cols1024_fmt(ss_ctx* c, const void* d_iq, long long item_stride, int
     else hipLaunchKernelGGL(kernel, dim3(nframes * tiles), dim3(threads), lds, c->stream, g);
   };
   const bool wcalc = g.wtab != nullptr;
-  if (c->wait.plan_ready.have && c->diag.cols1024_wide) {  // the plan of the call before at the front of this launch (detect_fused.h)
+  if (c->wait.plan_ready.have) {  // the plan of the call before at the front of this launch (detect_fused.h)
     const ss_ctx::PendPlan& plan = c->wait.plan_ready.v;
     const int plan_wgs = ss::plan_fused_wgs(ss::plan_long_blocks(plan.a.layout, plan.a.cols, c->n));
     const dim3 grid((unsigned)(plan_wgs + nframes * 64)), block(1024);
@@ -733,9 +725,8 @@ void launch_cols1024_fmt(ss_ctx* c, const void* d_iq, long long item_stride, int
     c->wait.plan_ready.have = false;
     return;
   }
-  if (c->diag.cols1024_wide && wcalc) go(ss::k_fft_cols1024<FMT, 4, true>, 64, 1024, ss::fft1024_cols_lds_bytes(4));
-  else if (c->diag.cols1024_wide) go(ss::k_fft_cols1024<FMT, 4>, 64, 1024, ss::fft1024_cols_lds_bytes(4));
-  else go(ss::k_fft_cols1024<FMT, 3>, 128, 512, ss::kFft1024ColsLdsBytes);
+  if (wcalc) go(ss::k_fft_cols1024<FMT, 4, true>, 64, 1024, ss::fft1024_cols_lds_bytes(4));
+  else go(ss::k_fft_cols1024<FMT, 4>, 64, 1024, ss::fft1024_cols_lds_bytes(4));
 }
 void launch_cols1024(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, int frame0 = 0) {
   const size_t sample = in_bytes_per_sample(c->cfg.in_format);
@@ -948,24 +939,24 @@ void launch_step_variant(ss_ctx* c, const ss::StepArgs& a, hipEvent_t e0, hipEve
     if (e0) hipExtLaunchKernelGGL(kernel, grid, block, ss::kStepLdsBytes, stream, e0, e1, 0, a);
     else hipLaunchKernelGGL(kernel, grid, block, ss::kStepLdsBytes, stream, a);
   };
-  // (2^20 points: rows of 32768 mask words, the emit role gives a frame to all eight waves; the FFT role is the row tiles — KIND 4,
-  // the column half being a launch of its own — or, behind a switch of the diagnostics build, 8-column column tiles, KIND 3)
-  // (KIND 5: a launch without an FFT role — the drain — whose detect workgroups share the plan's list out in a loop)
-  if (c->two_pass && a.list_loop) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, 5>);
-  if (c->two_pass) return c->diag.cols1024_wide ? go(ss::k_scan_step<FMT, SPEC, 2, true, false, 4>) : go(ss::k_scan_step<FMT, SPEC, 2, true, false, 3>);
+  // The forms are those of scan_step.h's table. Most of the choice follows from the context's form, fixed at ss_create — the
+  // drains take the same kernel as the calls whose stages they finish, without an FFT role.
+  // (2^20 points: rows of 32768 mask words, the emit role gives a frame to all eight waves; the FFT role is the row tiles, the column
+  // half being a launch of its own; a launch without an FFT role — the drain — shares the plan's list out in a loop)
+  if (c->two_pass && a.list_loop) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepDrain1024>);
+  if (c->two_pass) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepRows1024>);
   if constexpr (ss::fmt_int8(FMT) && !SPEC) {  // (the fold's launches, and the drains of the stages that wait behind them: their tiles read the fold's rows)
 #ifdef SS_DIAG
-    if (!c->use_fft8192 && c->ring_perm8 && c->dif_logq == 3 && (c->diag.prio_fft || c->diag.prio_other)) return go(ss::k_scan_step<FMT, SPEC, 2, true, true, 8>);
+    if (!c->use_fft8192 && c->ring_perm8 && c->dif_logq == 3 && (c->diag.prio_fft || c->diag.prio_other)) return go(ss::k_scan_step<FMT, SPEC, 2, true, true, ss::kStepFold8>);
 #endif
-    if (!c->use_fft8192 && c->ring_perm8 && c->dif_logq == 3 && a.dif.iq && a.n_fft == 8 * a.dif.nframes && SS_DIF8_W == 4) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, 11>);  // (a short call: one residue per workgroup)
-    if (!c->use_fft8192 && c->ring_perm8) return c->dif_logq == 4 ? go(ss::k_scan_step<FMT, SPEC, 2, true, false, 9>) : go(ss::k_scan_step<FMT, SPEC, 2, true, false, 8>);
+    if (!c->use_fft8192 && c->ring_perm8) return c->dif_logq == 4 ? go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepFold16>) : go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepFold8>);
   }
-  if (!c->use_fft8192 && a.n_fft && a.rows256.work && !a.n_rows) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, 6>);  // (65536 points: the row tiles as the FFT role; rows of 2048 mask words: the wide emit role)
+  if (!c->use_fft8192 && a.n_fft && a.rows256.work && !a.n_rows) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepRows256>);  // (65536 points: the row tiles as the FFT role; rows of 2048 mask words: the wide emit role)
   if constexpr (!SPEC) {
-    if (!c->use_fft8192 && c->rows1024x256) return c->merge ? go(ss::k_scan_step<FMT, SPEC, 2, true, false, 12>) : go(ss::k_scan_step<FMT, SPEC, 2, true, false, 10>);  // (262144 points: KIND 2 with the plan of layout 3; with the row tiles as one more role)
+    if (!c->use_fft8192 && c->rows1024x256) return c->merge ? go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepMergedX256>) : go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepColsX256>);  // (262144 points: the wide column form with the plan of layout 3; with the row tiles as one more role)
   }
-  if (!c->use_fft8192 && c->merge) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, 7>);  // (one launch per call: KIND 2's roles and the row tiles as one more; its drains too)
-  if (!c->use_fft8192) return a.emit_per_wg == 1 ? go(ss::k_scan_step<FMT, SPEC, 2, true, false, 2>) : go(ss::k_scan_step<FMT, SPEC, 2, true, false, 1>);
+  if (!c->use_fft8192 && c->merge) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepMerged65536>);  // (one launch per call: the wide column form's roles and the row tiles as one more; its drains too)
+  if (!c->use_fft8192) return a.emit_per_wg == 1 ? go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepColsWide>) : go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepCols>);
 #ifdef SS_DIAG
   if (c->diag.fft_tw == 0) return go(ss::k_scan_step<FMT, SPEC, 0, false>);
   if (c->diag.fft_tw == 1) return go(ss::k_scan_step<FMT, SPEC, 1, false>);
@@ -1210,17 +1201,10 @@ void drain_deep(ss_ctx* c) {
   if (!in_order) {
     // The join is a pair of barrier packets at the head of the public stream's queue, which is idle: the kernel behind them starts
     // 11-13 us after the stage they wait for has ended (scripts/ubench/sync_tail_lab.hip, profiles/r06/s18_timeline_k20_tail_all.txt).
-    // Measured and not kept (drain_waiter_us, off): a WAITER in front of them — one wave on the public stream that sleeps until each
-    // queue's last stage has said so in device memory (k_drain_signal, one wave behind it). In the lab, whose kernels are one wave
-    // each, the same 20 launches + drain end 16 us earlier on the device with it; in the product nothing moves — the ring fill still
-    // starts 14-19 us behind the last stage, and the two one-wave launches sit on the tail (profiles/r06/s19_summary.txt).
-    // Correctness never rested on it: the barriers behind it are the join.
-    const bool waiter = c->diag.drain_waiter_us > 0 && c->d_drain_done && launched_on_queues;
-    if (waiter) {
-      for (int q = 0; q < c->nq; ++q) hipLaunchKernelGGL(ss::k_drain_signal, dim3(1), dim3(64), 0, c->s_ab[q], c->d_drain_done);
-      c->drain_signals += (unsigned)c->nq;
-      hipLaunchKernelGGL(ss::k_drain_wait, dim3(1), dim3(64), 0, c->stream, (const unsigned*)c->d_drain_done, c->drain_signals, (long long)c->diag.drain_waiter_us * 100);
-    }
+    // Tried, measured, removed: a WAITER in front of them — one wave on the public stream that slept until each queue's last stage
+    // had said so in device memory (one more wave behind it). In the lab, whose kernels are one wave each, the same 20 launches +
+    // drain ended 16 us earlier on the device with it; in the product nothing moved — the ring fill still started 14-19 us behind the
+    // last stage, and the two one-wave launches sat on the tail: 25.3-26.5 against 25.7-26.5 us per step (profiles/r06/s19_summary.txt).
     join();
   }
   // the spectrogram partial sums still waiting join their containers, and the public stream waits for all of them
@@ -1243,8 +1227,10 @@ void drain_deep(ss_ctx* c) {
     }
     if (owed) hipLaunchKernelGGL(ss::k_ring_fill, dim3((unsigned)((size_t)kHistRows * c->n / 1024), owed), dim3(256), 0, c->stream, rf, c->n, kHistRows);
   }
-  // (a device-wide synchronisation that finds an event behind every stream's last command waits for those; otherwise it puts a marker
-  // of its own on each stream first: 27 against 17 us from the device's last word to the host's return in the lab)
+  // Nothing in this library waits for ev_tail: its consumer is the runtime's device-wide synchronisation (hipDeviceSynchronize, with
+  // which a caller ends a run of calls). One that finds an event behind every stream's last command waits for those; otherwise it puts
+  // a marker of its own on each stream first: 27 against 17 us from the device's last word to the host's return in the lab
+  // (scripts/ubench/sync_tail_lab.hip), 25.2 against 25.85 us per step in the 20-step form (Diag::drain_tail_event).
   if (launched_on_queues && c->diag.drain_tail_event && c->ev_tail) (void)hipEventRecord(c->ev_tail, c->stream);
   c->deep_L = 0;
   c->deep_barrier = -10;
@@ -1985,7 +1971,7 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
     W& w = c->wait;
     const bool reused = (w.det_planned.have && clashes(w.det_planned.v)) || (w.det_wants_plan.have && clashes(w.det_wants_plan.v));  // (a detect stage that waits for its rows keeps no plane)
     if (!overlap || reused) flush_stages(c);
-    const bool rows_by_step = (c->two_pass && c->diag.cols1024_wide) || c->rows256_step || c->rows1024x256;
+    const bool rows_by_step = c->two_pass || c->rows256_step || c->rows1024x256;
     // one launch per call (SS_MERGE_65536): calls that keep no dB plane, in one piece, with stages allowed to overlap; any other call
     // drains what waits in that form and goes the two-launch way
     // (up to 128 frames: two 64 MiB work buffers in flight are what the Infinity Cache holds beside the rest — 256-frame calls lose a tenth
@@ -2009,10 +1995,9 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
       FftRole drole;
       drole.frames = &gf;
       drole.dif = &df;
-      // (two residues per workgroup: four per frame at radix 8, eight at radix 16; a radix-8 call of up to dif8_single_max frames — 0 in the
-      // product — takes one residue per workgroup, eight per frame: KIND 11, a switch of the diagnostics build)
-      const bool single = c->dif_logq == 3 && nframes <= c->diag.dif8_single_max;
-      drole.n = (c->dif_logq == 4 || single ? 8 : SS_DIF8_W) * nframes;
+      // (two residues per workgroup: four per frame at radix 8, eight at radix 16. One residue per workgroup for short calls was tried,
+      // measured and removed: 16-frame calls 20.6 against 19.5 us, 32-frame calls 26.0 against 20.3, profiles/r06/s13_summary.txt)
+      drole.n = (c->dif_logq == 4 ? 8 : SS_DIF8_W) * nframes;
       // the plan of the call before, the planned detect stage (of the call before that) and the emit stage behind it ride on the launch
       launch_step(c, &drole, w.riding(W::DET | W::EMIT | W::PLAN));
     } else if (merged_call) {
@@ -2286,7 +2271,6 @@ void free_ctx(ss_ctx* c) {
   for (hipEvent_t e : c->ev_join)
     if (e) (void)hipEventDestroy(e);
   if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
-  (void)hipFree(c->d_drain_done);
   for (auto& z : c->noise) (void)hipFree(z.d_thr);
   for (auto& g : c->spec) (void)hipFree(g.d_sum);
   (void)hipFree(c->d_spec_partial);
@@ -2571,8 +2555,6 @@ int ss_create(const ss_config* cfg, ss_ctx** out) {
     for (auto& e : c->ev_in) CREATE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     for (auto& e : c->ev_join) CREATE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     CREATE_HIP(hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming));
-    CREATE_HIP(hipMalloc(&c->d_drain_done, 64));
-    CREATE_HIP(hipMemset(c->d_drain_done, 0, 64));
   }
   if (c->step_path) {
     hipDeviceProp_t prop;
@@ -2718,10 +2700,10 @@ int ss_create(const ss_config* cfg, ss_ctx** out) {
     CREATE_HIP(hipMemcpy(c->d_win, win.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
     if (c->two_pass) {  // the same taps in the 1024-point column tiles' own order (fft1024_kernels.h)
       std::vector<float> wk((size_t)n);
-      ss::fft1024_window_order(win.data(), wk.data(), c->diag.cols1024_wide ? 4 : 3);
+      ss::fft1024_window_order(win.data(), wk.data(), 4);
       CREATE_HIP(hipMalloc(&c->d_win1024, sizeof(float) * (size_t)n));
       CREATE_HIP(hipMemcpy(c->d_win1024, wk.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
-      if (!cfg->window && c->diag.cols1024_wide && c->diag.win_calc) {  // the default window: Hamming taps formed in the kernel
+      if (!cfg->window && c->diag.win_calc) {  // the default window: Hamming taps formed in the kernel
         std::vector<float2> wt(65536);
         ss::fft1024_window_rotation_table(wt.data());
         CREATE_HIP(hipMalloc(&c->d_wtab1024, sizeof(float2) * wt.size()));

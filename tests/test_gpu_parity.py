@@ -109,7 +109,6 @@ ALTERNATIVES = [  # (environment, fft size, sample rate, format): every measurem
     ({"SS_STEP_LONG": "0"}, 65536, 20_000_000, "cs8"),
     ({"SS_STEP_LONG": "0"}, 16384, 4_000_000, "cf32"),
     ({"SS_FFT_TWOPASS": "0"}, 1 << 20, 61_440_000, "cs8"),  # 2^20 points as 256 x 4096 in three passes (round 3's form; the product takes 1024 x 1024 in two)
-    ({"SS_C1024_WIDE": "0"}, 1 << 20, 61_440_000, "cs8"),   # ... in two passes with 8-column tiles as k_scan_step's FFT role (the product: 16-column tiles, a launch of their own, the ROW tiles as the role)
     ({"SS_PLAN_FUSED": "0", "SS_WIN_CALC": "0"}, 1 << 20, 61_440_000, "cf32"),  # the plan as a launch of its own, window taps from the table (round 4 before session 14)
     ({"SS_CULL_65536": "0"}, 65536, 20_000_000, "cs8"),     # 65536 points as until session 19 of round 4: every tile evaluated, columns as the FFT role with all passengers
     ({"SS_ROWS256_STEP": "0", "SS_WIN_CALC": "0"}, 65536, 20_000_000, "cs8"),  # ... culled, rows and plan as launches of their own
@@ -122,7 +121,6 @@ ALTERNATIVES = [  # (environment, fft size, sample rate, format): every measurem
     ({"SS_ROWS1024X256": "0"}, 262144, 61_440_000, "cf32"),  # 262144 points on round 2's path (k_fft_rows256xR_psd, every tile evaluated)
     ({"SS_MERGE_65536": "0"}, 262144, 61_440_000, "cs8"),   # ... culled, two launches per call (KIND 10 + k_fft_rows1024_psd<8>)
     ({"SS_PLAN_FUSED": "0", "SS_LIST_FIRST": "0"}, 262144, 61_440_000, "cf32"),  # ... the plan (plan_x256_run) as a launch of its own
-    ({"SS_DIF8_SINGLE_MAX": "32"}, 65536, 20_000_000, "cs8"),  # the fold with ONE residue per workgroup for short calls (KIND 11: measured, not kept)
 ]
 
 

@@ -183,11 +183,11 @@ def test_flush_then_stream_sync_completes_the_results():
     _flush_then_device_sync()
 
 
-@pytest.mark.parametrize("env", [{"SS_DRAIN_TAIL_EVENT": "0"}, {"SS_DRAIN_WAITER_US": "500"}, {"SS_DRAIN_WAITER_US": "1", "SS_DRAIN_TAIL_EVENT": "0"}],
+@pytest.mark.parametrize("env", [{"SS_DRAIN_TAIL_EVENT": "0"}],
                          ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()))
 def test_the_drains_join_in_its_measured_forms(monkeypatch, diag_lib, env):
-    """drain_deep (specscan.hip): without the event behind the drain's last command, and with the one-wave waiter in front of the join
-    (round 6, measured and not kept) — with time to spare and with a limit it runs into: the barriers behind it are the join either way."""
+    """drain_deep (specscan.hip): without the event behind the drain's last command — the barriers in front of it are the join either way.
+    (The one-wave waiter in front of the join, round 6's other measured form, is removed: profiles/r06/s19_summary.txt.)"""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     _flush_then_device_sync()
