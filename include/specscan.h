@@ -316,7 +316,15 @@ int ss_read_noise(ss_ctx* ctx, float* thr);
  *   ss_feed_collect  -> oldest submitted batch; blocks until it is done. Pointers are pinned host memory owned
  *                       by the feed, valid until that slot is handed out again by ss_feed_acquire.
  * Returns SS_ERR_INVALID from acquire when every slot is submitted-and-uncollected (collect first), and from
- * collect when nothing is pending. Not to be mixed with ss_process on the same context while batches are pending. */
+ * collect when nothing is pending. Not to be mixed with ss_process on the same context while batches are pending.
+ *
+ * ss_feed_create_items makes a whole-item feed: same arguments and rules, but ss_feed_acquire hands out a pinned buffer
+ * of max_batch items of N * decim samples each (in_format), which the producer fills with the stream as it arrives,
+ * undecimated. ss_feed_submit uploads the first N samples of every item (one strided copy); the device buffer, the
+ * chain and every result are those of an ordinary feed given the same frames. The items stay in the slot's pinned
+ * memory until the slot is handed out again, which is what a recorder bound to the feed records from
+ * (specscan_record_feed.h). Pinned footprint: depth * max_batch * N * decim * bytes per sample (an ordinary feed:
+ * the same without decim). With decim == 1 it is an ordinary feed in every respect. */
 typedef struct ss_feed ss_feed;
 typedef struct ss_feed_result {
   int32_t nframes;
@@ -329,6 +337,7 @@ typedef struct ss_feed_result {
 } ss_feed_result;
 
 int ss_feed_create(ss_ctx* ctx, int32_t depth, int32_t cand_cap, int32_t want_psd, ss_feed** out);
+int ss_feed_create_items(ss_ctx* ctx, int32_t depth, int32_t cand_cap, int32_t want_psd, ss_feed** out);
 void ss_feed_destroy(ss_feed* feed);
 int ss_feed_acquire(ss_feed* feed, void** frames);
 int ss_feed_submit(ss_feed* feed, int32_t nframes, const int64_t* t_ms, int64_t user_tag);

@@ -114,6 +114,16 @@ int sc_process_ranges(sc_ctx* ctx, const void* iq, int32_t nsamples, const sc_ra
 int sc_process_ranges_device(sc_ctx* ctx, const void* d_iq, int32_t nsamples, const sc_range* ranges, int32_t nranges, int8_t* d_out_i8,
                              float* d_out_cf32, int32_t* counts, int32_t* range_counts, int32_t cap);
 
+/* sc_process_ranges_device on a stream that is still in host memory, uploading only what the ranges read: the union of the
+ * non-empty ranges, merged into intervals, one copy per interval to the same offsets of the context's own input buffer
+ * (max_samples samples, allocated by the first host-form call). Definition, rules, outputs (device planes) and counts are
+ * sc_process_ranges_device's; the call is asynchronous on the context's stream, and iq must stay valid and unchanged until
+ * sc_sync has returned. Pinned memory makes the copies truly asynchronous; pageable memory works. *uploaded_bytes (nullable)
+ * is the bytes copied for this call: bytes per sample times the size of the union. Everything is validated before the first
+ * copy: a refused call changes nothing, *uploaded_bytes included. */
+int sc_process_ranges_upload(sc_ctx* ctx, const void* iq, int32_t nsamples, const sc_range* ranges, int32_t nranges, int8_t* d_out_i8,
+                             float* d_out_cf32, int32_t* counts, int32_t* range_counts, int32_t cap, uint64_t* uploaded_bytes);
+
 /* DataController::pushTransmission payload (data_controller.cpp:27-42): uint64 time ms, int32 start, int32 stop,
  * uint32 sample rate, then the samples as offset-binary bytes (int8 ^ 0x80). Host-side helper; returns the byte count
  * (out may be NULL to query it), or < 0 if cap is too small. */

@@ -16,7 +16,8 @@ SC_MAX_CHANNELS = 16
 
 EXPORTS = ("sc_default_config", "sc_create", "sc_destroy", "sc_last_error", "sc_stage_count", "sc_stage_info", "sc_stage_taps",
            "sc_output_capacity", "sc_start", "sc_stop", "sc_is_recording", "sc_process", "sc_process_device", "sc_sync",
-           "sc_transmission_payload", "sc_set_input_format", "sc_process_ranges", "sc_process_ranges_device")
+           "sc_transmission_payload", "sc_set_input_format", "sc_process_ranges", "sc_process_ranges_device",
+           "sc_process_ranges_upload")
 SC_MAX_RANGES = 64
 
 # what process() / process_device() take for each input format (ss_format): integers interleaved re,im
@@ -63,6 +64,8 @@ def _bind(lib):
     if hasattr(lib, "sc_process_ranges"):  # (A/B builds of older trees, scripts/ab: measurement runs only)
         lib.sc_process_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ScRange), C.c_int32, C.c_void_p, C.c_void_p, i32p, i32p, C.c_int32]
         lib.sc_process_ranges_device.argtypes = lib.sc_process_ranges.argtypes
+    if hasattr(lib, "sc_process_ranges_upload"):
+        lib.sc_process_ranges_upload.argtypes = lib.sc_process_ranges.argtypes + [C.POINTER(C.c_uint64)]
     lib.sc_set_input_format.argtypes = [C.c_void_p, C.c_int32, C.c_float]
     lib.sc_transmission_payload.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
     lib._sc_bound = True
@@ -224,6 +227,22 @@ class Channelizer:
         self._check(self._lib.sc_process_ranges_device(self._h, p(iq), int(nsamples), arr, n, p(out_i8), p(out_cf32),
                                                        counts.ctypes.data_as(i32p), rc.ctypes.data_as(i32p), int(cap)))
         return counts, rc[:n].copy()
+
+    def process_ranges_upload(self, iq: np.ndarray, ranges, out_i8=None, out_cf32=None, cap: int = 0):
+        """sc_process_ranges_upload: iq on the host as process() takes it, outputs as process_ranges_device() takes them; only the
+        union of the ranges is uploaded. Returns (counts, range_counts, uploaded_bytes). Waits (sync()) before it returns, so iq
+        need not outlive the call."""
+        x, nsamples = self._host_input(iq)
+        arr, n = _ranges(ranges)
+        counts = np.zeros(self.cfg.channels, np.int32)
+        rc = np.zeros(max(n, 1), np.int32)
+        up = C.c_uint64(0)
+        i32p = C.POINTER(C.c_int32)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        self._check(self._lib.sc_process_ranges_upload(self._h, x.ctypes.data, nsamples, arr, n, p(out_i8), p(out_cf32),
+                                                       counts.ctypes.data_as(i32p), rc.ctypes.data_as(i32p), int(cap), C.byref(up)))
+        self.sync()
+        return counts, rc[:n].copy(), int(up.value)
 
     def sync(self):
         self._check(self._lib.sc_sync(self._h))

@@ -99,6 +99,44 @@ inline void count_outputs(const sc_range* ranges, int nranges, const Ratio* stag
   }
 }
 
+// sc_process_ranges_upload: the parts of the call's stream that its ranges read, as intervals [begin, end) to copy. The
+// non-empty ranges sorted by begin, overlapping and abutting ones merged: at most nranges intervals, ascending, with a gap
+// between any two. The list must have passed validate().
+struct Interval {
+  int begin, end;
+};
+
+inline int upload_intervals(const sc_range* ranges, int nranges, Interval* out) {
+  int n = 0;
+  for (int i = 0; i < nranges; ++i) {  // insertion sort: SC_MAX_RANGES at most, and a channel's ranges ascend already
+    if (ranges[i].begin == ranges[i].end) continue;
+    int at = n++;
+    for (; at > 0 && out[at - 1].begin > ranges[i].begin; --at) out[at] = out[at - 1];
+    out[at].begin = ranges[i].begin;
+    out[at].end = ranges[i].end;
+  }
+  int m = 0;
+  for (int i = 0; i < n; ++i) {
+    if (m > 0 && out[i].begin <= out[m - 1].end) {
+      if (out[i].end > out[m - 1].end) out[m - 1].end = out[i].end;
+    } else {
+      out[m++] = out[i];
+    }
+  }
+  return m;
+}
+
+// samples of the largest batch of whole items, max_batch * n * decim; false when that does not fit a call's int32_t nsamples
+inline bool item_samples(int max_batch, int n, int decim, int32_t* out) {
+  if (max_batch < 0 || n < 0 || decim < 0) return false;
+  const unsigned long long frames = (unsigned long long)max_batch * (unsigned long long)n;  // < 2^62
+  if (frames > 0x7fffffffULL) return false;
+  const unsigned long long total = frames * (unsigned long long)decim;  // < 2^62
+  if (total > 0x7fffffffULL) return false;
+  *out = (int32_t)total;
+  return true;
+}
+
 }  // namespace chan_ranges
 
 #endif  // SPECSCAN_CHAN_RANGES_H

@@ -1090,6 +1090,33 @@ int sc_process_ranges(sc_ctx* c, const void* iq, int32_t nsamples, const sc_rang
   return host_results(c, out_i8, out_cf32, counts, cap);
 }
 
+int sc_process_ranges_upload(sc_ctx* c, const void* iq, int32_t nsamples, const sc_range* ranges, int32_t nranges, int8_t* d_out_i8,
+                             float* d_out_cf32, int32_t* counts, int32_t* range_counts, int32_t cap, uint64_t* uploaded_bytes) {
+  if (!c) return SS_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (nsamples < 0 || (nsamples > 0 && !iq) || cap < 0) return sc_fail(c, SS_ERR_INVALID, "bad iq/nsamples/cap");
+  if (nsamples > c->cfg.max_samples) return sc_fail(c, SS_ERR_BATCH, "nsamples %d > max_samples %d", nsamples, c->cfg.max_samples);
+  // what run_ranges refuses, before the first copy
+  if (const char* why = chan_ranges::validate(ranges, nranges, c->cfg.channels, nsamples)) return sc_fail(c, SS_ERR_INVALID, "%s", why);
+  for (int ch = 0; ch < c->cfg.channels; ++ch)
+    if (c->slots[ch].active) return sc_fail(c, SS_ERR_INVALID, "channel %d is recording (sc_start): ranges and start/stop are not mixed", ch);
+  SC_HIP(c, hipSetDevice(c->cfg.device_id));
+  if (!c->d_in) SC_HIP(c, hipMalloc(&c->d_in, sizeof(float2) * (size_t)c->cfg.max_samples));  // as host_staging
+  // Interval [b, e) of the stream goes to d_in + b: the ranges address d_in as they address the stream. What lies between the
+  // intervals is whatever an earlier call left there; no range reads it (every raw load is clamped into its range).
+  chan_ranges::Interval iv[SC_MAX_RANGES];
+  const int niv = chan_ranges::upload_intervals(ranges, nranges, iv);
+  const size_t bps = (size_t)SS_FMT_BYTES(c->in_format);
+  uint64_t bytes = 0;
+  for (int i = 0; i < niv; ++i) {
+    const size_t at = bps * (size_t)iv[i].begin, len = bps * (size_t)(iv[i].end - iv[i].begin);
+    SC_HIP(c, hipMemcpyAsync(reinterpret_cast<char*>(c->d_in) + at, static_cast<const char*>(iq) + at, len, hipMemcpyHostToDevice, c->stream));
+    bytes += len;
+  }
+  if (uploaded_bytes) *uploaded_bytes = bytes;
+  return run_ranges(c, c->d_in, nsamples, ranges, nranges, d_out_i8, d_out_cf32, counts, range_counts, cap);
+}
+
 int sc_transmission_payload(uint64_t time_ms, int32_t frequency, int32_t sample_rate, const int8_t* iq_i8, int32_t nsamples, uint8_t* out,
                             int32_t cap) {
   const int header = (int)(sizeof(uint64_t) + 2 * sizeof(int32_t) + sizeof(uint32_t));

@@ -27,6 +27,7 @@
 #include "../../include/specscan_track_feed.h"
 #include "../../include/specscan_record_feed.h"
 #include "../../include/specscan_spectrogram_feed.h"
+#include "chan_ranges.h"
 #include "detect_fused.h"
 #include "detect_kernels.h"
 #include "fft1024_kernels.h"
@@ -3280,6 +3281,7 @@ struct ss_feed {
   ss_ctx* c = nullptr;
   int depth = 0, cand_cap = 0;
   bool want_psd = false;
+  bool items = false;  // ss_feed_create_items on a decimated context: h_in holds whole items of n * decim samples, d_in their first n
   std::vector<ss_feed_slot> slots;
   int next_acquire = 0, next_collect = 0, pending = 0, acquired = -1;
   hipStream_t copy_stream = nullptr, d2h_stream = nullptr;
@@ -3330,11 +3332,8 @@ void feed_free(ss_feed* f) {
   if (f->d2h_stream) (void)hipStreamDestroy(f->d2h_stream);
   delete f;
 }
-}  // namespace
 
-extern "C" {
-
-int ss_feed_create(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd, ss_feed** out) {
+int feed_create(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd, bool items, ss_feed** out) {
   if (!c || !out) return SS_ERR_INVALID;
   std::lock_guard<std::mutex> lock(c->mtx);
   if (depth < 2 || depth > 8 || cand_cap < 0) return fail(c, SS_ERR_INVALID, "feed depth %d (2..8) / cand_cap %d", depth, cand_cap);
@@ -3344,8 +3343,10 @@ int ss_feed_create(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd,
   f->depth = depth;
   f->cand_cap = cand_cap;
   f->want_psd = want_psd != 0;
+  f->items = items && c->cfg.decim != 1;  // with decim == 1 the items are the frames: an ordinary feed
   f->slots.resize((size_t)depth);
   const size_t in_bytes = in_bytes_per_sample(c->cfg.in_format) * (size_t)c->n * (size_t)c->cfg.max_batch;
+  const size_t host_bytes = f->items ? in_bytes * (size_t)c->cfg.decim : in_bytes;
   const size_t plane = sizeof(float) * (size_t)c->n * (size_t)c->cfg.max_batch;
   const size_t ncand = (size_t)(cand_cap > 0 ? cand_cap : 1);
 #define FEED_HIP(call)                                                              \
@@ -3359,7 +3360,7 @@ int ss_feed_create(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd,
   FEED_HIP(hipStreamCreateWithFlags(&f->copy_stream, hipStreamNonBlocking));
   FEED_HIP(hipStreamCreateWithFlags(&f->d2h_stream, hipStreamNonBlocking));
   for (auto& s : f->slots) {
-    FEED_HIP(hipHostMalloc(&s.h_in, in_bytes, hipHostMallocDefault));
+    FEED_HIP(hipHostMalloc(&s.h_in, host_bytes, hipHostMallocDefault));
     FEED_HIP(hipMalloc(&s.d_in, in_bytes));
     FEED_HIP(hipHostMalloc((void**)&s.h_off, sizeof(int32_t) * ((size_t)c->cfg.max_batch + 1), hipHostMallocDefault));
     FEED_HIP(hipHostMalloc((void**)&s.h_idx, sizeof(int32_t) * ncand, hipHostMallocDefault));
@@ -3375,6 +3376,13 @@ int ss_feed_create(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd,
   *out = f;
   return SS_OK;
 }
+}  // namespace
+
+extern "C" {
+
+int ss_feed_create(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd, ss_feed** out) { return feed_create(c, depth, cand_cap, want_psd, false, out); }
+
+int ss_feed_create_items(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd, ss_feed** out) { return feed_create(c, depth, cand_cap, want_psd, true, out); }
 
 void ss_feed_destroy(ss_feed* f) {
   if (!f) return;
@@ -3430,7 +3438,10 @@ int ss_feed_submit(ss_feed* f, int32_t nframes, const int64_t* t_ms, int64_t use
   ss_feed_slot& s = f->slots[(size_t)f->acquired];
   const int n = c->n;
   const size_t row_bytes = in_bytes_per_sample(c->cfg.in_format) * (size_t)n;
-  SS_HIP(c, hipMemcpyAsync(s.d_in, s.h_in, row_bytes * (size_t)nframes, hipMemcpyHostToDevice, f->copy_stream));
+  if (f->items)  // the first n samples of every item: d_in stays compact, and everything behind the copy is an ordinary feed's
+    SS_HIP(c, hipMemcpy2DAsync(s.d_in, row_bytes, s.h_in, row_bytes * (size_t)c->cfg.decim, row_bytes, (size_t)nframes, hipMemcpyHostToDevice, f->copy_stream));
+  else
+    SS_HIP(c, hipMemcpyAsync(s.d_in, s.h_in, row_bytes * (size_t)nframes, hipMemcpyHostToDevice, f->copy_stream));
   SS_HIP(c, hipEventRecord(s.ev_h2d, f->copy_stream));
   SS_HIP(c, hipStreamWaitEvent(c->stream, s.ev_h2d, 0));
   NoiseState* z = nullptr;
@@ -4178,12 +4189,13 @@ int srf_create(ss_feed* f, const srf_config* cfg, srf_ctx** out) {
   if (cfg->abi_version != SRF_ABI_VERSION) return srf_fail(nullptr, SS_ERR_INVALID, "abi_version %u, library has %u", cfg->abi_version, SRF_ABI_VERSION);
   ss_ctx* c = f->c;
   std::lock_guard<std::mutex> lock(c->mtx);
-  if (c->cfg.decim != 1)
-    return srf_fail(nullptr, SS_ERR_INVALID, "the scan context has decim %d: a decimated feed uploads only the frames the scan reads, there is no stream to record from", c->cfg.decim);
+  if (c->cfg.decim != 1 && !f->items)
+    return srf_fail(nullptr, SS_ERR_INVALID, "the scan context has decim %d: an ordinary feed takes only the frames the scan reads, there is no stream to record from (ss_feed_create_items keeps the whole items)", c->cfg.decim);
   if (f->recorder) return srf_fail(nullptr, SS_ERR_INVALID, "the feed already has a recorder");
   if (f->pending > 0 || f->acquired >= 0) return srf_fail(nullptr, SS_ERR_INVALID, "the feed has batches pending: collect them first");
-  const long long max_samples = (long long)c->cfg.max_batch * c->n;
-  if (max_samples > 0x7fffffffLL) return srf_fail(nullptr, SS_ERR_INVALID, "max_batch * N = %lld samples do not fit one channeliser call", max_samples);
+  int32_t max_samples = 0;  // of the recorded stream: whole items (decim is 1 on the device route)
+  if (!chan_ranges::item_samples(c->cfg.max_batch, c->n, c->cfg.decim, &max_samples))
+    return srf_fail(nullptr, SS_ERR_INVALID, "max_batch * N * decim = %lld samples do not fit one channeliser call", (long long)c->cfg.max_batch * c->n * c->cfg.decim);
   srf_ctx* t = new (std::nothrow) srf_ctx();
   if (!t) return srf_fail(nullptr, SS_ERR_NOMEM, "out of memory");
   t->scan = c;
@@ -4193,7 +4205,7 @@ int srf_create(ss_feed* f, const srf_config* cfg, srf_ctx** out) {
   sc_default_config(&sc, c->cfg.sample_rate, cfg->bandwidth);
   sc.threshold = cfg->threshold;
   sc.channels = cfg->channels;
-  sc.max_samples = (int32_t)max_samples;
+  sc.max_samples = max_samples;
   sc.pack_scale = cfg->pack_scale;
   sc.device_id = c->cfg.device_id;
   int st = sc_create(&sc, &t->chan);
@@ -4208,7 +4220,7 @@ int srf_create(ss_feed* f, const srf_config* cfg, srf_ctx** out) {
     srf_free(t);
     return st;
   }
-  t->cap = sc_output_capacity(t->chan, (int32_t)max_samples);
+  t->cap = sc_output_capacity(t->chan, max_samples);
   const size_t plane = (size_t)2 * (size_t)t->cap * (size_t)cfg->channels;
   bool ok = hipSetDevice(c->cfg.device_id) == hipSuccess && hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) == hipSuccess;
   ok = ok && hipMalloc(&t->d_i8, plane) == hipSuccess && hipHostMalloc((void**)&t->h_i8, plane, hipHostMallocDefault) == hipSuccess;
@@ -4257,6 +4269,7 @@ int srf_record(srf_ctx* t, const sc_range* ranges, int32_t nranges, srf_result* 
   if (!out || nranges < 0 || (nranges > 0 && !ranges)) return srf_fail(t, SS_ERR_INVALID, "null argument");
   std::lock_guard<std::mutex> rec(t->rec_mtx);
   const void* d_in = nullptr;
+  const void* h_items = nullptr;  // an items feed: the held slot's pinned items, uploaded as far as the ranges read them
   int nsamples = 0;
   {
     std::lock_guard<std::mutex> lock(t->scan->mtx);
@@ -4265,7 +4278,8 @@ int srf_record(srf_ctx* t, const sc_range* ranges, int32_t nranges, srf_result* 
     if (f->held < 0) return srf_fail(t, SS_ERR_INVALID, "no batch is held: collect one first");
     const ss_feed_slot& s = f->slots[(size_t)f->held];
     d_in = s.d_in;  // the collect has waited for the batch's chain, which waited for the upload
-    nsamples = s.nframes * t->scan->n;
+    if (f->items) h_items = s.h_in;
+    nsamples = s.nframes * t->scan->n * (f->items ? t->scan->cfg.decim : 1);  // (srf_create: fits)
   }
   const int nch = t->cfg.channels;
   out->nsamples = nsamples;
@@ -4274,13 +4288,18 @@ int srf_record(srf_ctx* t, const sc_range* ranges, int32_t nranges, srf_result* 
   out->range_counts = t->h_rc;
   out->out_i8 = t->h_i8;
   out->out_cf32 = t->cfg.want_cf32 ? t->h_cf32 : nullptr;
+  out->h2d_bytes = 0;
   for (int ch = 0; ch < nch; ++ch) t->h_counts[ch] = 0;
   if (nranges > 0) {
-    // the held slot is not acquired and not submitted to while it is held, so its d_in stands still without the context's lock
-    int st = sc_process_ranges_device(t->chan, d_in, nsamples, ranges, nranges, t->d_i8, t->d_cf32, t->h_counts, t->h_rc, t->cap);
+    // the held slot is not acquired and not submitted to while it is held, so its d_in and its pinned items stand still without
+    // the context's lock
+    uint64_t uploaded = 0;
+    int st = h_items ? sc_process_ranges_upload(t->chan, h_items, nsamples, ranges, nranges, t->d_i8, t->d_cf32, t->h_counts, t->h_rc, t->cap, &uploaded)
+                     : sc_process_ranges_device(t->chan, d_in, nsamples, ranges, nranges, t->d_i8, t->d_cf32, t->h_counts, t->h_rc, t->cap);
     if (st != SS_OK) return srf_fail(t, st, "%s", sc_last_error(t->chan));
-    st = sc_sync(t->chan);
+    st = sc_sync(t->chan);  // (the uploads have read the pinned items by now: the slot may go)
     if (st != SS_OK) return srf_fail(t, st, "%s", sc_last_error(t->chan));
+    out->h2d_bytes = uploaded;
     hipError_t e = hipSetDevice(t->scan->cfg.device_id);
     for (int ch = 0; ch < nch && e == hipSuccess; ++ch) {
       const size_t n = (size_t)(t->h_counts[ch] < t->cap ? t->h_counts[ch] : t->cap), at = (size_t)2 * (size_t)t->cap * (size_t)ch;

@@ -70,6 +70,8 @@ def load_library(diag: bool | None = None) -> C.CDLL:
         lib.ss_selftest.restype = C.c_longlong
         lib.ss_feed_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         lib.ss_feed_create.restype = C.c_int
+        lib.ss_feed_create_items.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        lib.ss_feed_create_items.restype = C.c_int
         lib.ss_feed_destroy.argtypes = [C.c_void_p]
         lib.ss_feed_destroy.restype = None
         lib.ss_feed_acquire.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -87,7 +89,7 @@ def load_library(diag: bool | None = None) -> C.CDLL:
 EXPORTS = ("ss_default_config", "ss_device_count", "ss_create", "ss_destroy", "ss_last_error", "ss_process",
            "ss_process_device", "ss_flush", "ss_sync", "ss_stream", "ss_input_wait", "ss_get_stats", "ss_set_frequency_range", "ss_reset", "ss_reset_noise",
            "ss_read_window", "ss_read_noise", "ss_kernel_timing", "ss_kernel_timing_read", "ss_kernel_timing_read_slots", "ss_kernel_timing_read_frames", "ss_selftest", "ss_spectrogram_size", "ss_spectrogram_read",
-           "ss_spectrogram_payload", "ss_feed_create", "ss_feed_destroy", "ss_feed_acquire", "ss_feed_submit", "ss_feed_collect", "ss_feed_pending")
+           "ss_spectrogram_payload", "ss_feed_create", "ss_feed_create_items", "ss_feed_destroy", "ss_feed_acquire", "ss_feed_submit", "ss_feed_collect", "ss_feed_pending")
 
 
 def _ptr(t):
@@ -197,9 +199,11 @@ class SpectrumEngine(abi.Chain):
         self._check(self._lib.ss_kernel_timing_read_frames(self._h, ms, cnt, fr))
         return {name: (ms[k], cnt[k], fr[k]) for k, name in enumerate(self.KERNEL_SLOTS)}
 
-    def feed(self, depth: int = 3, cand_cap: int = 1 << 20, want_psd: bool = False) -> "Feed":
-        """Pipelined host feeding (ss_feed_*): pinned staging slots, H2D overlapped with the chain."""
-        return Feed(self, depth, cand_cap, want_psd)
+    def feed(self, depth: int = 3, cand_cap: int = 1 << 20, want_psd: bool = False, items: bool = False) -> "Feed":
+        """Pipelined host feeding (ss_feed_*): pinned staging slots, H2D overlapped with the chain. ``items=True``: a whole-item
+        feed (ss_feed_create_items) — the slots take the stream undecimated, items of N*decim samples, the scan still gets the
+        first N of each, and ``Feed.record`` works at any ``decim``."""
+        return Feed(self, depth, cand_cap, want_psd, items)
 
 
 class Feed:
@@ -207,14 +211,17 @@ class Feed:
     ``collect()`` results in submission order. Views returned by ``collect`` live in the feed's pinned memory and
     are valid until the slot is acquired again (copy what must outlive that)."""
 
-    def __init__(self, engine: SpectrumEngine, depth: int, cand_cap: int, want_psd: bool):
+    def __init__(self, engine: SpectrumEngine, depth: int, cand_cap: int, want_psd: bool, items: bool = False):
         self._e, self._lib = engine, engine._lib
         self.cand_cap = int(cand_cap)
+        self.items = bool(items)  # a whole-item feed: acquire() takes items of N*decim samples
         h = C.c_void_p()
-        engine._check(self._lib.ss_feed_create(engine._h, int(depth), int(cand_cap), int(bool(want_psd)), C.byref(h)))
+        create = self._lib.ss_feed_create_items if self.items else self._lib.ss_feed_create
+        engine._check(create(engine._h, int(depth), int(cand_cap), int(bool(want_psd)), C.byref(h)))
         self._h = h
         cfg = engine.cfg
-        self._shape = (cfg.max_batch, cfg.fft_size) if cfg.in_format == abi.SS_FMT_CF32 else (cfg.max_batch, cfg.fft_size, 2)
+        item = cfg.fft_size * (cfg.decim if self.items else 1)
+        self._shape = (cfg.max_batch, item) if cfg.in_format == abi.SS_FMT_CF32 else (cfg.max_batch, item, 2)
         self._dtype = {abi.SS_FMT_CF32: np.complex64, abi.SS_FMT_CS8: np.int8, abi.SS_FMT_CU8: np.uint8, abi.SS_FMT_CS16: np.int16}[cfg.in_format]
 
     def close(self):
@@ -230,8 +237,9 @@ class Feed:
         return TrackedFeed(self, group_size, self._e.cfg.start_level if start_level is None else start_level, max_watch)
 
     def record(self, bandwidth: int, channels: int = 4, **kw):
-        """A recorder bound to this feed (include/specscan_record_feed.h; the engine needs ``decim=1``): from now on a collected
-        batch stays held, its samples still on the device, until the returned object's ``record(ranges)`` has channelised sample
+        """A recorder bound to this feed (include/specscan_record_feed.h; the engine needs ``decim=1``, or the feed ``items=True``):
+        from now on a collected batch stays held — its samples still on the device, or on an items feed of a decimated engine its
+        whole items still in the slot's pinned memory — until the returned object's ``record(ranges)`` has channelised sample
         ranges of it or ``release()`` has let it go. ``threshold``, ``pack_scale``, ``want_cf32`` as recorder.RecordedFeed takes them."""
         from .recorder import RecordedFeed
         return RecordedFeed(self, bandwidth, channels, **kw)
@@ -255,7 +263,8 @@ class Feed:
 
     def acquire(self) -> np.ndarray:
         """[max_batch, N] complex64 (or [max_batch, N, 2] int8/uint8/int16) view of the next free pinned slot: frames
-        already decimated (the first N samples of each N*D item)."""
+        already decimated (the first N samples of each N*D item). On an items feed: [max_batch, N*D] (or [max_batch, N*D, 2]),
+        the whole items as the stream delivers them."""
         p = C.c_void_p()
         self._e._check(self._lib.ss_feed_acquire(self._h, C.byref(p)))
         nbytes = int(np.prod(self._shape)) * np.dtype(self._dtype).itemsize

@@ -11,7 +11,7 @@ import numpy as np
 from .abi import SpecscanError
 from .channelizer import SC_MAX_CHANNELS, SC_MAX_RANGES, ScRange, _ranges
 
-SRF_ABI_VERSION = 1
+SRF_ABI_VERSION = 2
 SRF_EXPORTS = ("srf_create", "srf_destroy", "srf_last_error", "srf_record", "srf_release")
 
 
@@ -22,7 +22,7 @@ class SrfConfig(C.Structure):  # srf_config
 
 class SrfResult(C.Structure):  # srf_result
     _fields_ = [("nsamples", C.c_int32), ("cap", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("range_counts", C.POINTER(C.c_int32)),
-                ("out_i8", C.POINTER(C.c_int8)), ("out_cf32", C.POINTER(C.c_float))]
+                ("out_i8", C.POINTER(C.c_int8)), ("out_cf32", C.POINTER(C.c_float)), ("h2d_bytes", C.c_uint64)]
 
 
 def bind_record_feed(lib: C.CDLL) -> C.CDLL:
@@ -40,9 +40,13 @@ def bind_record_feed(lib: C.CDLL) -> C.CDLL:
 
 
 class RecordedFeed:
-    """One srf_ctx bound to a Feed of an engine with decim 1 (``Feed.record``). From now on every collect of the feed (its own, or
-    a TrackedFeed's) leaves the batch held: ``record(ranges)`` channelises sample ranges of it from the upload that is still on
-    the device and lets it go, ``release()`` lets it go unrecorded. The feed and its engine must outlive the object."""
+    """One srf_ctx bound to a Feed (``Feed.record``): of an engine with decim 1, or an items feed (``engine.feed(items=True)``) of
+    any engine. From now on every collect of the feed (its own, or a TrackedFeed's) leaves the batch held: ``record(ranges)``
+    channelises sample ranges of it and lets it go, ``release()`` lets it go unrecorded. With decim 1 the samples are the upload
+    that is still on the device; on an items feed of a decimated engine they are the batch's whole items in the slot's pinned
+    memory, of which only the union of the ranges is uploaded (``last_h2d_bytes``). ``RangePlanner(channels, N * decim)`` is the
+    planner for an items feed: a frame of the tracker's lists stands for one item of the stream. The feed and its engine must
+    outlive the object."""
 
     def __init__(self, feed, bandwidth: int, channels: int = 4, threshold: int = 125, pack_scale: float = 127.0, want_cf32: bool = False):
         self._feed = feed
@@ -53,6 +57,7 @@ class RecordedFeed:
         if st != 0:
             raise SpecscanError(st, (self._lib.srf_last_error(None) or b"").decode())
         self._h = h
+        self.last_h2d_bytes = 0  # srf_result.h2d_bytes of the last record()
 
     def close(self):
         if getattr(self, "_h", None):
@@ -74,11 +79,14 @@ class RecordedFeed:
         self._check(self._lib.srf_release(self._h))
 
     def record(self, ranges):
-        """ranges: [(channel, shift_hz, begin, end), ...] in samples of the held batch (frame f is f * N .. (f + 1) * N). Returns
-        ({channel: (int8 [m, 2], complex64 [m] or None)} for every channel with a range, range_counts), numpy copies."""
+        """ranges: [(channel, shift_hz, begin, end), ...] in samples of the held batch's stream: frame f is f * N .. (f + 1) * N, or
+        on an items feed f * N * decim .. f * N * decim + N with the rest of its item behind it. Returns
+        ({channel: (int8 [m, 2], complex64 [m] or None)} for every channel with a range, range_counts), numpy copies;
+        ``last_h2d_bytes`` is what the call uploaded."""
         arr, n = _ranges(ranges)
         r = SrfResult()
         self._check(self._lib.srf_record(self._h, arr, n, C.byref(r)))
+        self.last_h2d_bytes = int(r.h2d_bytes)
         nch, cap = self.cfg.channels, r.cap
         counts = np.ctypeslib.as_array(r.counts, shape=(nch,)).copy()
         rc = np.ctypeslib.as_array(r.range_counts, shape=(max(n, 1),))[:n].copy()

@@ -187,7 +187,7 @@ def engine_overrides_for(info: RawFileInfo) -> dict:
 
 def replay_file(engine, path: str, kind: int | None = None, batch: int | None = None, depth: int = 3, cand_cap: int = 1 << 20,
                 want_psd: bool = False, frame_period_ms: float | None = None, stats: ReplayStats | None = None, read_threads: int = 4,
-                spectrogram=None, spectrogram_max_rows: int = 8):
+                spectrogram=None, spectrogram_max_rows: int = 8, items: bool = False):
     """Generator: streams the dump through ``engine`` (a SpectrumEngine whose in_format matches the file) and yields
     one result dict per batch, in order (copies: safe to keep). A reader thread fills pinned slots; up to ``depth - 1``
     batches are in flight behind the one being read.
@@ -199,7 +199,11 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
     delivers the spectrogram rows (``Feed.spectrogram``), and every row a batch closes is handed over as its
     DataController::pushSpectrogram payload behind its length as a little-endian uint32, in order — the file
     ``specscan_replay --spectrogram-out`` writes. The rows close on the frames' clock, so without ``frame_period_ms`` the
-    stream's own period, 1000 * fft_size * decim / sample_rate ms, is taken."""
+    stream's own period, 1000 * fft_size * decim / sample_rate ms, is taken.
+
+    items: read the dump's whole items of fft_size * decim samples into an items feed (``engine.feed(items=True)``), which keeps
+    them in its pinned slots and uploads the first fft_size of each: candidates and rows are the same, and a recorder bound
+    to such a feed has the whole stream to record from."""
     cfg = engine.cfg
     if kind is None:
         kind = parse_raw_file_name(path).kind
@@ -209,15 +213,15 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
     batch = int(batch or cfg.max_batch)
     if not 0 < batch <= cfg.max_batch:
         raise ValueError("batch must be in 1..max_batch")
-    reader = RawIqReader(path, kind, cfg.fft_size, cfg.decim)
-    feed = engine.feed(depth=depth, cand_cap=cand_cap, want_psd=want_psd)
+    reader = RawIqReader(path, kind, cfg.fft_size * cfg.decim, 1) if items else RawIqReader(path, kind, cfg.fft_size, cfg.decim)
+    feed = engine.feed(depth=depth, cand_cap=cand_cap, want_psd=want_psd, items=items)
     rows = None
     if spectrogram is not None:
         rows = feed.spectrogram(max_rows=spectrogram_max_rows)
         if frame_period_ms is None:
             frame_period_ms = 1000.0 * cfg.fft_size * cfg.decim / cfg.sample_rate
     st = stats if stats is not None else ReplayStats()
-    frame_bytes = cfg.fft_size * abi.SS_FMT_BYTES[want_fmt]
+    frame_bytes = cfg.fft_size * abi.SS_FMT_BYTES[want_fmt] * (cfg.decim if items else 1)  # what a frame takes out of the file
     submitted: queue.Queue = queue.Queue()
     free = threading.Semaphore(depth)  # a slot is free again once its batch has been collected
     err: list = []
