@@ -29,6 +29,11 @@
  * ss_reset and ss_set_frequency_range go with stf_reset, as they go with st_reset — and both need the feed drained first
  * (every submitted batch collected): a batch in flight was digested with the rows and marks the reset would wipe.
  *
+ * stf_create wants a scan context with SS_FLAG_KEEP_PLANES: every batch then writes its avg plane and no averaging tile is culled.
+ * specscan_track_sparse.h has stf_create_sparse for a context without the flag — the scan stays on its culled path, writes no avg
+ * plane, and only the tile columns the watch windows touch are evaluated once more behind the batch — and stf_sparse_stats. Every
+ * other name of this header serves both kinds of object, and the digest is the same bit for bit.
+ *
  * The device counts batches in 32 bits: a submit that would pass sequence number 2^32 - 1 without stf_reset fails with
  * SS_ERR_INVALID.
  *

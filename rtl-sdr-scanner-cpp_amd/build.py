@@ -13,8 +13,9 @@ LIB = os.path.join(CSRC, "libspecscan.so")
 LIB_DIAG = os.path.join(CSRC, "libspecscan_diag.so")
 SOURCES = ["specscan.hip", "channelizer.hip"]
 HEADERS = ["fft_kernels.h", "fft8192_kernel.h", "fft8192_v2.h", "scan_step.h", "fft256_kernels.h", "detect_kernels.h", "detect_fused.h", "reference_nan.h", "fft1024_kernels.h", "ring_place.h", "stage_slots.h",
-           "track_digest.h", "track_digest_blocked.h", "track_feed.h", "chan_ranges.h", "spectrogram_gate.h", "spectrogram_rows.h", os.path.join("..", "..", "include", "specscan_spectrogram_feed.h"), os.path.join("..", "..", "include", "specscan.h"), os.path.join("..", "..", "include", "specscan_channelizer.h"),
-           os.path.join("..", "..", "include", "specscan_track.h"), os.path.join("..", "..", "include", "specscan_track_feed.h"), os.path.join("..", "..", "include", "specscan_record_feed.h")]
+           "track_digest.h", "track_digest_blocked.h", "track_feed.h", "track_sparse.h", "chan_ranges.h", "spectrogram_gate.h", "spectrogram_rows.h", os.path.join("..", "..", "include", "specscan_spectrogram_feed.h"), os.path.join("..", "..", "include", "specscan.h"), os.path.join("..", "..", "include", "specscan_channelizer.h"),
+           os.path.join("..", "..", "include", "specscan_track.h"), os.path.join("..", "..", "include", "specscan_track_feed.h"), os.path.join("..", "..", "include", "specscan_track_sparse.h"),
+           os.path.join("..", "..", "include", "specscan_record_feed.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC", "-shared", "-Wall", "-Wno-unused-result"]
 
 
@@ -82,7 +83,8 @@ def build_replay_tool(force: bool = False, verbose: bool = False) -> str:
     src = os.path.join(HOST_DIR, "replay_main.cpp")
     tracker = os.path.join(HOST_DIR, "signal_tracker.cpp")
     deps = [src, tracker, os.path.join(HOST_DIR, "raw_file.h"), os.path.join(HOST_DIR, "signal_tracker.h"), os.path.join(HERE, "..", "include", "specscan.h"),
-            os.path.join(HERE, "..", "include", "specscan_track_feed.h"), os.path.join(HERE, "..", "include", "specscan_spectrogram_feed.h"), LIB]
+            os.path.join(HERE, "..", "include", "specscan_track_feed.h"), os.path.join(HERE, "..", "include", "specscan_track_sparse.h"),
+            os.path.join(HERE, "..", "include", "specscan_spectrogram_feed.h"), LIB]
     if force or not os.path.exists(REPLAY_TOOL) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(REPLAY_TOOL):
         build_lib()
         cmd = [shutil.which("g++") or "g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Wpedantic", "-Werror",

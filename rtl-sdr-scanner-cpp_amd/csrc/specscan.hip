@@ -25,6 +25,7 @@
 #include "../../include/specscan.h"
 #include "../../include/specscan_track.h"
 #include "../../include/specscan_track_feed.h"
+#include "../../include/specscan_track_sparse.h"
 #include "../../include/specscan_record_feed.h"
 #include "../../include/specscan_spectrogram_feed.h"
 #include "chan_ranges.h"
@@ -42,6 +43,7 @@
 #include "track_digest.h"
 #include "track_digest_blocked.h"
 #include "track_feed.h"
+#include "track_sparse.h"
 
 namespace {
 
@@ -49,6 +51,7 @@ thread_local char g_create_err[512] = "";
 
 // fused back end (grouping 21 x 21): frames per tile, and the ring rows kept between batches
 constexpr int kFusedTF = 16;
+static_assert(kFusedTF == ss::kWatchTF && ss::kWatchCol == ss::kFeedBlock, "k_watch_tiles (track_sparse.h) runs the tile this back end runs");
 // Deep pipelining (ss_ctx::deep): a call's last stage runs four launches after its first; the two queues synchronise once in
 // kDeepSyncPeriod launches on the launch three back (a wait costs ~10 us of queue time: rarely, and not within the first 32
 // launches of a run): everything launched more than 4 + kDeepSyncPeriod + 3 launches ago has finished.
@@ -500,6 +503,10 @@ struct ss_ctx {
   float* d_cand_avg = nullptr;
   int cand_cap_alloc = 0;
   const float* last_psd = nullptr;  // where the last batch's PSD plane lives (device)
+  // the fused detect stage launched last, as it was launched (launch_step, run_backend_fused): what a sparse tracked feed replays on
+  // the tile columns its watch windows touch (stf_enqueue, track_sparse.h)
+  ss::DetectArgs last_det{};
+  bool last_det_ok = false;
   int last_n = 0;
   // the tracking digest (st_digest, below): the capacity the last batch's candidate lists were given, and whether the centre
   // frequency has changed since that batch (retunes so far; how many there were when the batch ran)
@@ -1027,6 +1034,8 @@ void launch_step(ss_ctx* c, const FftRole* fft, const ss_ctx::Waiting::Riders& r
   const bool planned = det && c->use_fft8192 && det->segsum && !det->rel_out && !det->avg_out && !spec && plan_cols > 0;
   if (det) {
     a.det = *det;
+    c->last_det = *det;
+    c->last_det_ok = true;
     if (planned) {
       a.n_plan = n_det_tiles;
       a.plan_cols = plan_cols;
@@ -1559,6 +1568,8 @@ int run_backend_fused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, N
     c->nan_pending = ns;  // (flush_stages puts it between the two)
     return SS_OK;
   }
+  c->last_det = da;
+  c->last_det_ok = true;
   if (spec) hipLaunchKernelGGL((ss::k_detect_fused<G, GX, TF, TB, true>), dim3(tiles), dim3(TB), 0, c->stream, da);
   else hipLaunchKernelGGL((ss::k_detect_fused<G, GX, TF, TB, false>), dim3(tiles), dim3(TB), 0, c->stream, da);
   if (c->ref_nan) launch_nan_stage(c, ns);
@@ -3845,6 +3856,13 @@ struct stf_ctx {
   uint64_t next_seq = 1, collected = 0;  // the next batch's sequence number; the newest collected one
   uint64_t post_seq = 0;                 // p and K_p as last posted
   std::vector<int32_t> post_keys;
+  // stf_create_sparse on a context that keeps no planes (include/specscan_track_sparse.h, kernels: track_sparse.h)
+  bool sparse = false;
+  uint32_t* d_sp_mask = nullptr;               // [(n / 32) x max_batch] the replayed tiles' mask words: never read
+  int* d_sp_counts = nullptr;                  // [max_batch] ... and their counts
+  int32_t* d_col_flag = nullptr;               // [nblocks] the tile columns the batch's watch windows touch
+  unsigned long long* d_sp_evaluated = nullptr;  // tiles the replay ran, since stf_create_sparse / stf_reset
+  uint64_t sp_tiles_in_batches = 0;
   char err[512] = "";
 };
 
@@ -3860,7 +3878,8 @@ int stf_fail(stf_ctx* t, int status, const char* fmt, A... a) {
 void stf_free(stf_ctx* t) {
   if (!t) return;
   tails_free(t->rows);
-  for (void* p : {(void*)t->d_mark, (void*)t->d_keymark, (void*)t->d_counts}) (void)hipFree(p);
+  for (void* p : {(void*)t->d_mark, (void*)t->d_keymark, (void*)t->d_counts, (void*)t->d_sp_mask, (void*)t->d_sp_counts, (void*)t->d_col_flag, (void*)t->d_sp_evaluated})
+    (void)hipFree(p);
   for (auto& s : t->slots) {
     for (void* p : {(void*)s.d_coff, (void*)s.d_best, (void*)s.d_watch, (void*)s.d_pidx, (void*)s.d_keys, (void*)s.d_cavg, (void*)s.d_pavg, (void*)s.d_hdr}) (void)hipFree(p);
     for (void* p : {(void*)s.h_best, (void*)s.h_watch, (void*)s.h_pidx, (void*)s.h_keys, (void*)s.h_cavg, (void*)s.h_pavg, (void*)s.h_hdr}) (void)hipHostFree(p);
@@ -3874,7 +3893,9 @@ hipError_t stf_clear(stf_ctx* t) {
   hipError_t e = tails_zero(t->rows, c);
   if (e == hipSuccess) e = hipMemsetAsync(t->d_mark, 0, sizeof(uint32_t) * (size_t)c->n, c->stream);
   if (e == hipSuccess) e = hipMemsetAsync(t->d_keymark, 0, sizeof(uint32_t) * (size_t)c->n, c->stream);
+  if (e == hipSuccess && t->sparse) e = hipMemsetAsync(t->d_sp_evaluated, 0, sizeof(unsigned long long), c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  t->sp_tiles_in_batches = 0;
   t->next_seq = 1;
   t->collected = 0;
   t->post_seq = 0;
@@ -3883,6 +3904,66 @@ hipError_t stf_clear(stf_ctx* t) {
 }
 
 void stf_feed_gone(stf_ctx* t) { t->feed = nullptr; }
+
+// A sparse object, between the watch list and the peaks: avg in the tile columns the watch windows touch, by the batch's own detect
+// stage once more (track_sparse.h) — its arguments as they were launched (ss_ctx::last_det), with everything but avg switched off:
+//   maskbits, counts  scratch of the tracker's. The scan's mask buffers are all zero between uses (EmitArgs::clear_masks: culled tiles
+//                     write nothing and rely on it) and its count buffers are zeroed on a schedule of their own: words written there
+//                     now would be a later batch's candidates.
+//   avg_out           the batch's sparse plane (ss_ctx::last_avg = DetectArgs::avg_sparse): every cell of a marked column, hit or not
+//   rel_out, hist_out nothing: hist_by_fft = 1 — the ring has this batch's rows already (its own tiles, its FFT stage or the drain's
+//                     k_ring_fill wrote them: flush_stages has run)
+//   segsum, halo_segsum, live, tile_list, stats   nothing is culled, waited for or counted: ss_get_stats does not move
+//   spec_*            zero, and the SPEC = false tile: a SS_FLAG_SPECTROGRAM context does not accumulate the batch twice
+// The rows in front of the batch are read where the detect stage read them, hist_in or halo_psd as launched (the same bits either way,
+// detect_fused.h: DetectArgs::halo_psd). Both are intact here, and stay so until the replay has read them:
+//   * the ring window [hist_in, hist_in + 35 rows): a call's own rows never land on its own window (ring_place.h: the first thing
+//     ring_place_decide checks), so neither this batch's tiles nor its FFT stage nor the drain's k_ring_fill (hist_out) touched it. The
+//     next writers are a LATER call's rows, or that call's place_ring moving the window to the front (k_hist_shift, on this stream) or
+//     settling dB rows in place (k_rows_sub_thr, on this stream): all enqueued after this replay. Calls through the feed are not
+//     overlapped (run_batch: allow_overlap = false), so they carry no halo_psd; if one did, its halo buffer (d_halo[L mod 2 nq]) is
+//     next written 2 nq launches on, by a call enqueued later.
+//   * the dB plane (d_psd2 rotation, DetectArgs::psd = last_psd), the noise ceiling and the pass mask: what k_best_blocked and k_save_tail
+//     of the same digest read, on the same grounds (the comment above stf_slot).
+//   * d_avg2[b] comes round again after nbuf batches — as the sparse plane of a later batch's detect stage, behind this stream.
+// A later call's launches on the library's own queues wait for an event recorded on this stream first ("whatever the public stream
+// holds ... comes first"), in-order calls are on it: everything above is ordered behind the digest by that one rule.
+int stf_replay_watch_tiles(stf_ctx* t, stf_slot& s, int nframes) {
+  ss_ctx* c = t->scan;
+  const int n = c->n;
+  if (!c->last_det_ok || c->last_det.psd != c->last_psd || c->last_det.nframes != nframes || c->last_det.n != n || c->last_det.avg_sparse != c->last_avg)
+    return fail(c, SS_ERR_INVALID, "tracked feed (sparse): the detect stage launched last is not this batch's");
+  hipLaunchKernelGGL(ss::k_feed_watch_cols, dim3(1), dim3(256), 0, c->stream, (const int32_t*)s.d_watch, (const ss::FeedDigestHeader*)s.d_hdr, n, t->rows.group_size / 2,
+                     t->d_col_flag);
+  ss::WatchTilesArgs wa{};
+  wa.det = c->last_det;
+  wa.det.maskbits = t->d_sp_mask;
+  wa.det.counts = t->d_sp_counts;
+  wa.det.rel_out = nullptr;
+  wa.det.avg_out = const_cast<float*>(c->last_avg);
+  wa.det.hist_out = nullptr;
+  wa.det.hist_by_fft = 1;
+  wa.det.segsum = nullptr;
+  wa.det.halo_segsum = nullptr;
+  wa.det.live = nullptr;
+  wa.det.tile_list = nullptr;
+  wa.det.stats = nullptr;
+  wa.det.spec_partial = nullptr;
+  wa.det.spec_prev_partial = nullptr;
+  wa.det.spec_prev_sum = nullptr;
+  wa.det.spec_prev_tiles = 0;
+  wa.det.spec_m = wa.det.spec_n = 0;
+#ifdef SS_DIAG
+  wa.det.stamp_mid = nullptr;
+  wa.det.cull_stats = nullptr;
+#endif
+  wa.col_flag = t->d_col_flag;
+  wa.evaluated = t->d_sp_evaluated;
+  const int frame_tiles = (nframes + wa.det.shift + kFusedTF - 1) / kFusedTF, cols = t->nblocks;  // (256-bin blocks: the tile columns)
+  hipLaunchKernelGGL(ss::k_watch_tiles, dim3((unsigned)(frame_tiles * cols)), dim3(256), 0, c->stream, wa);
+  t->sp_tiles_in_batches += (uint64_t)frame_tiles * (uint64_t)cols;
+  return SS_OK;
+}
 
 // ss_feed_submit, under the context's lock, behind flush_stages and the result copies: the digest of the batch just enqueued.
 int stf_enqueue(ss_feed* f, int slot_no, int nframes) {
@@ -3921,6 +4002,10 @@ int stf_enqueue(ss_feed* f, int slot_no, int nframes) {
                      s.d_hdr);
   hipLaunchKernelGGL(ss::k_feed_scatter, dim3((unsigned)t->nblocks), dim3(ss::kFeedBlock), 0, c->stream, (const uint32_t*)t->d_mark, (const uint32_t*)t->d_keymark, n, p, seq,
                      (const int32_t*)t->d_counts, t->cfg.max_watch, s.d_watch);
+  if (t->sparse) {
+    const int st = stf_replay_watch_tiles(t, s, nframes);
+    if (st != SS_OK) return st;
+  }
   ss::FeedPeaksArgs pk{};
   pk.avg = c->last_avg;
   pk.watch = s.d_watch;
@@ -4016,18 +4101,21 @@ int feed_collect(ss_feed* f, ss_feed_result* out, stf_result* digest) {
   return SS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int stf_create(ss_feed* f, const stf_config* cfg, stf_ctx** out) {
+// stf_create and stf_create_sparse: allow_sparse = the context may lack SS_FLAG_KEEP_PLANES (the object is a sparse one if it does)
+int stf_create_any(ss_feed* f, const stf_config* cfg, stf_ctx** out, bool allow_sparse) {
   if (!f || !cfg || !out) return stf_fail(nullptr, SS_ERR_INVALID, "null argument");
   *out = nullptr;
   if (cfg->abi_version != STF_ABI_VERSION) return stf_fail(nullptr, SS_ERR_INVALID, "abi_version %u, library has %u", cfg->abi_version, STF_ABI_VERSION);
   if (cfg->group_size < 0 || cfg->max_watch <= 0) return stf_fail(nullptr, SS_ERR_INVALID, "group_size >= 0 and max_watch > 0 required");
   ss_ctx* c = f->c;
   std::lock_guard<std::mutex> lock(c->mtx);
-  if (!(c->cfg.flags & SS_FLAG_KEEP_PLANES)) return stf_fail(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_KEEP_PLANES (the digest reads the kept dB and avg planes)");
+  const bool sparse = allow_sparse && !(c->cfg.flags & SS_FLAG_KEEP_PLANES);
+  if (!allow_sparse && !(c->cfg.flags & SS_FLAG_KEEP_PLANES)) return stf_fail(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_KEEP_PLANES (the digest reads the kept dB and avg planes)");
+  if (sparse && !c->fused)
+    return stf_fail(nullptr, SS_ERR_INVALID, "sparse tracking needs the fused back end (grouping 21 x 21; this context has %d x %d): the unfused back end keeps no sparse avg plane",
+                    c->cfg.grouping_x, c->cfg.grouping_y);
+  if (sparse && c->ref_nan) return stf_fail(nullptr, SS_ERR_INVALID, "sparse tracking on a SS_FLAG_REFERENCE_NAN context: its NaN stage patches the planes behind the tiles");
+  if (sparse && c->n >= 65536) return stf_fail(nullptr, SS_ERR_INVALID, "sparse tracking at fft_size %d: 65536 points and up can leave no bin-ordered dB plane (32768 at most)", c->n);
   if (f->cand_cap <= 0) return stf_fail(nullptr, SS_ERR_INVALID, "the feed was created with cand_cap 0: there are no candidate lists to digest");
   if (f->tracker) return stf_fail(nullptr, SS_ERR_INVALID, "the feed already has a tracker");
   if (f->pending > 0 || f->acquired >= 0) return stf_fail(nullptr, SS_ERR_INVALID, "the feed has batches pending: collect them first");
@@ -4039,6 +4127,7 @@ int stf_create(ss_feed* f, const stf_config* cfg, stf_ctx** out) {
   t->feed = f;
   t->cfg = *cfg;
   t->rows = rows;
+  t->sparse = sparse;
   t->nblocks = (c->n + ss::kFeedBlock - 1) / ss::kFeedBlock;
   t->slots.resize((size_t)f->depth);
   const size_t n = (size_t)c->n, frames = (size_t)c->cfg.max_batch, cap = (size_t)f->cand_cap, mw = (size_t)cfg->max_watch;
@@ -4055,6 +4144,17 @@ int stf_create(ss_feed* f, const stf_config* cfg, stf_ctx** out) {
     ok = ok && hipHostMalloc(&s.h_watch, sizeof(int32_t) * mw) == hipSuccess && hipHostMalloc(&s.h_keys, sizeof(int32_t) * mw) == hipSuccess;
     ok = ok && hipHostMalloc(&s.h_pidx, sizeof(int32_t) * frames * mw) == hipSuccess && hipHostMalloc(&s.h_pavg, sizeof(float) * frames * mw) == hipSuccess;
   }
+  if (sparse) {
+    const size_t words = (n / 32) * frames, plane = sizeof(float) * n * frames;
+    ok = ok && hipMalloc(&t->d_sp_mask, sizeof(uint32_t) * words) == hipSuccess && hipMalloc(&t->d_sp_counts, sizeof(int) * frames) == hipSuccess;
+    ok = ok && hipMalloc(&t->d_col_flag, sizeof(int32_t) * (size_t)t->nblocks) == hipSuccess && hipMalloc(&t->d_sp_evaluated, sizeof(unsigned long long)) == hipSuccess;
+    ok = ok && hipMemsetAsync(t->d_sp_mask, 0, sizeof(uint32_t) * words, c->stream) == hipSuccess && hipMemsetAsync(t->d_sp_counts, 0, sizeof(int) * frames, c->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(t->d_col_flag, 0, sizeof(int32_t) * (size_t)t->nblocks, c->stream) == hipSuccess;
+    // every sparse plane to NaN, once (all bytes 0xff): a cell of a watch window the replay failed to write would be a NaN peak, not a
+    // plausible value some earlier batch left there. Nothing pending (checked above); the planes are max_batch x n floats each.
+    flush_stages(c);
+    for (int k = 0; k < c->nbuf; ++k) ok = ok && hipMemsetAsync(c->d_avg2[k], 0xff, plane, c->stream) == hipSuccess;
+  }
   ok = ok && stf_clear(t) == hipSuccess;
   if (!ok) {
     const hipError_t e = hipGetLastError();
@@ -4063,6 +4163,30 @@ int stf_create(ss_feed* f, const stf_config* cfg, stf_ctx** out) {
   }
   f->tracker = t;
   *out = t;
+  return SS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int stf_create(ss_feed* f, const stf_config* cfg, stf_ctx** out) { return stf_create_any(f, cfg, out, false); }
+
+int stf_create_sparse(ss_feed* f, const stf_config* cfg, stf_ctx** out) { return stf_create_any(f, cfg, out, true); }
+
+int stf_sparse_stats(stf_ctx* t, uint64_t* tiles_evaluated, uint64_t* tiles_in_batches) {
+  if (!t) return SS_ERR_INVALID;
+  if (!tiles_evaluated || !tiles_in_batches) return stf_fail(t, SS_ERR_INVALID, "null argument");
+  ss_ctx* c = t->scan;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (!t->sparse) return stf_fail(t, SS_ERR_INVALID, "not a sparse object: the scan context keeps its planes (stf_create, or stf_create_sparse with SS_FLAG_KEEP_PLANES), nothing is replayed");
+  if (!t->feed) return stf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
+  unsigned long long ev = 0;
+  if (hipSetDevice(c->cfg.device_id) != hipSuccess || hipMemcpyAsync(&ev, t->d_sp_evaluated, sizeof(ev), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return stf_fail(t, SS_ERR_HIP, "reading the replay's counter failed: %s", hipGetErrorString(hipGetLastError()));
+  *tiles_evaluated = ev;
+  *tiles_in_batches = t->sp_tiles_in_batches;
   return SS_OK;
 }
 

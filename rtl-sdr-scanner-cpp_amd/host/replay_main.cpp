@@ -5,7 +5,7 @@
 // earlier batches cross PCIe and run. Optionally writes the raw PSD rows as the reference's DEBUG_SAVE_FULL_POWER
 // dump would (`..._power.raw`, sdr_device.cpp:173-176).
 //
-//   specscan_replay <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track [--bandwidth HZ]]
+//   specscan_replay <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse [--bandwidth HZ]]
 //                   [--spectrogram-out FILE [--spectrogram-max-rows R]]
 // Prints one JSON line: frames, batches, candidates, seconds, MS/s (file + PCIe inclusive).
 //
@@ -13,6 +13,9 @@
 // the consumer thread owns a specscan::SignalTracker (host/signal_tracker.h): after each stf_collect it runs the batch's frames
 // through processFrameDigest (frame time 1000 * frame_index * N * D / fs ms, the stream's own clock) and posts its keys. The reader
 // thread is unchanged. The JSON line gains `transmissions` (entries of the per-frame lists, summed) and `tracked_frames`.
+// --track-sparse: the same tracker and the same JSON, but the context keeps no planes (no SS_FLAG_KEEP_PLANES): the tracked feed is a
+// sparse one (include/specscan_track_sparse.h) that re-evaluates the tile columns the watch windows touch behind every batch. The JSON
+// line gains `tiles_evaluated` and `tiles_in_batches` (stf_sparse_stats).
 // --spectrogram-out FILE: the feed delivers the spectrogram rows (include/specscan_spectrogram_feed.h; the context gets
 // SS_FLAG_SPECTROGRAM). Frame k carries the time nearbyint(k * period), period = 1000 * N * D / fs ms — the clock the reference's
 // per-frame send gate runs on — and every row a batch closes is written to FILE as its DataController::pushSpectrogram payload
@@ -20,6 +23,7 @@
 #include <specscan.h>
 #include <specscan_spectrogram_feed.h>
 #include <specscan_track_feed.h>
+#include <specscan_track_sparse.h>
 
 #include <chrono>
 #include <cmath>
@@ -41,7 +45,7 @@ struct Options {
   std::string path, power_dir, spectrogram_out;
   int spectrogram_max_rows = 8;
   int fft = 0, decim = 0, batch = 1024, depth = 3, learn_frames = -1;
-  bool track = false;
+  bool track = false, track_sparse = false;
   int bandwidth = 32000;  // Config::recordingBandwidth: the tracker's windows are ceil(bandwidth / (fs / N)) bins wide
 };
 
@@ -65,6 +69,8 @@ bool parse_args(int argc, char** argv, Options* o) {
       if (!next(&o->learn_frames)) return false;
     } else if (a == "--track") {
       o->track = true;
+    } else if (a == "--track-sparse") {
+      o->track = o->track_sparse = true;
     } else if (a == "--bandwidth") {
       if (!next(&o->bandwidth) || o->bandwidth <= 0) return false;
     } else if (a == "--spectrogram-out") {
@@ -89,7 +95,7 @@ bool parse_args(int argc, char** argv, Options* o) {
 int main(int argc, char** argv) {
   Options opt;
   if (!parse_args(argc, argv, &opt)) {
-    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R]]\n", argv[0]);
+    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R]]\n", argv[0]);
     return 2;
   }
   specscan::RawFileInfo info;
@@ -102,7 +108,7 @@ int main(int argc, char** argv) {
   if (opt.fft > 0) cfg.fft_size = opt.fft;
   if (opt.decim > 0) cfg.decim = opt.decim;
   if (opt.learn_frames >= 0) cfg.learn_frames = opt.learn_frames;
-  if (opt.track) cfg.flags |= SS_FLAG_KEEP_PLANES;  // the digest reads the kept dB and avg planes
+  if (opt.track && !opt.track_sparse) cfg.flags |= SS_FLAG_KEEP_PLANES;  // the digest reads the kept dB and avg planes
   const bool want_rows = !opt.spectrogram_out.empty();
   if (want_rows) cfg.flags |= SS_FLAG_SPECTROGRAM;
   cfg.max_batch = opt.batch;
@@ -134,8 +140,8 @@ int main(int argc, char** argv) {
   tc.group_size = (int)((((long long)opt.bandwidth * cfg.fft_size) + info.sample_rate - 1) / info.sample_rate);  // sdr_device.cpp:151
   if (opt.track) {
     stf_config tcfg{STF_ABI_VERSION, tc.group_size, cfg.start_level, 4096};
-    if (stf_create(feed, &tcfg, &tracked) != SS_OK) {
-      fprintf(stderr, "stf_create: %s\n", stf_last_error(nullptr));
+    if ((opt.track_sparse ? stf_create_sparse(feed, &tcfg, &tracked) : stf_create(feed, &tcfg, &tracked)) != SS_OK) {
+      fprintf(stderr, "%s: %s\n", opt.track_sparse ? "stf_create_sparse" : "stf_create", stf_last_error(nullptr));
       ss_feed_destroy(feed);
       ss_destroy(ctx);
       return 1;
@@ -281,6 +287,11 @@ int main(int argc, char** argv) {
     }
     producer.join();
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    uint64_t tiles_evaluated = 0, tiles_in_batches = 0;
+    if (!failed && opt.track_sparse && stf_sparse_stats(tracked, &tiles_evaluated, &tiles_in_batches) != SS_OK) {
+      failed = true;
+      error = stf_last_error(tracked);
+    }
     if (failed) {
       fprintf(stderr, "replay failed: %s\n", error.c_str());
       rc = 1;
@@ -290,6 +301,7 @@ int main(int argc, char** argv) {
              opt.path.c_str(), cfg.fft_size, cfg.decim, (long long)reader.items(), frames, batches, candidates, seconds,
              seconds > 0 ? (double)frames * cfg.fft_size / seconds / 1e6 : 0.0);
       if (tracked) printf(", \"transmissions\": %lld, \"tracked_frames\": %lld", transmissions, tracked_frames);
+      if (opt.track_sparse) printf(", \"tiles_evaluated\": %llu, \"tiles_in_batches\": %llu", (unsigned long long)tiles_evaluated, (unsigned long long)tiles_in_batches);
       if (rows) printf(", \"spectrogram_rows\": %lld", spectrogram_rows);
       printf("}\n");
     }

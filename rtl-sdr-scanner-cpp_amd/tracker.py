@@ -1,7 +1,8 @@
 """ctypes binding of host/libspecscan_host.so — the host-side signal tracker (host/signal_tracker.h), the part of
 the reference's Transmission block that turns per-frame candidates into the Scanner's (shift Hz, flush) list — and of the
 st_* entry points of libspecscan.so (include/specscan_track.h), the device-side digest that tracker can run on instead of
-the rel and avg planes — and of the stf_* entry points (include/specscan_track_feed.h), the same digest behind the pipelined feed."""
+the rel and avg planes — and of the stf_* entry points (include/specscan_track_feed.h), the same digest behind the pipelined feed, with
+its form for engines that keep no planes (include/specscan_track_sparse.h)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -244,12 +245,23 @@ def bind_track_feed(lib: C.CDLL):
     return result
 
 
+STF_SPARSE_EXPORTS = ("stf_create_sparse", "stf_sparse_stats")  # include/specscan_track_sparse.h
+
+
+def bind_track_sparse(lib: C.CDLL) -> None:
+    lib.stf_create_sparse.argtypes = [C.c_void_p, C.POINTER(StfConfig), C.POINTER(C.c_void_p)]
+    lib.stf_create_sparse.restype = C.c_int
+    lib.stf_sparse_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.stf_sparse_stats.restype = C.c_int
+
+
 class TrackedFeed:
     """One stf_ctx bound to a Feed of an engine created with SS_FLAG_KEEP_PLANES (Feed.track): every batch submitted through the
     feed is digested in the stream behind its chain. ``collect`` replaces the feed's own; ``post_keys(seq, tracker.keys)`` after
-    every collect keeps the watch lists short; ``reset`` goes with the engine's ``reset`` (feed drained first)."""
+    every collect keeps the watch lists short; ``reset`` goes with the engine's ``reset`` (feed drained first).
+    ``sparse=True``: stf_create_sparse — the engine may lack SS_FLAG_KEEP_PLANES (fused back end, up to 32768 points)."""
 
-    def __init__(self, feed, group_size: int, start_level: float = 8.0, max_watch: int = 1024):
+    def __init__(self, feed, group_size: int, start_level: float = 8.0, max_watch: int = 1024, sparse: bool = False):
         from .abi import SpecscanError
         self._err = SpecscanError
         self._feed = feed  # (the feed and its engine must outlive the object; a feed closed first leaves it only close())
@@ -257,7 +269,9 @@ class TrackedFeed:
         self._result = bind_track_feed(self._lib)
         cfg = StfConfig(STF_ABI_VERSION, int(group_size), float(start_level), int(max_watch))
         h = C.c_void_p()
-        st = self._lib.stf_create(feed._h, C.byref(cfg), C.byref(h))
+        if sparse:
+            bind_track_sparse(self._lib)
+        st = (self._lib.stf_create_sparse if sparse else self._lib.stf_create)(feed._h, C.byref(cfg), C.byref(h))
         if st != 0:
             raise SpecscanError(st, (self._lib.stf_last_error(None) or b"").decode())
         self._h = h
@@ -280,6 +294,14 @@ class TrackedFeed:
 
     def reset(self):
         self._check(self._lib.stf_reset(self._h))
+
+    def sparse_stats(self) -> dict:
+        """{"tiles_evaluated", "tiles_in_batches"} since the object was made or reset: the tiles the replay behind the batches ran, out
+        of the tiles those batches have. SpecscanError on an object whose engine keeps its planes (nothing is replayed there)."""
+        bind_track_sparse(self._lib)
+        ev, tot = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.stf_sparse_stats(self._h, C.byref(ev), C.byref(tot)))
+        return {"tiles_evaluated": int(ev.value), "tiles_in_batches": int(tot.value)}
 
     def post_keys(self, seq: int, keys):
         """The tracker's keys after it has processed batch ``seq`` (SignalTracker.keys): batches submitted from now on watch them."""

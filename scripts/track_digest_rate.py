@@ -5,18 +5,25 @@
                sst_process_frame_digest per frame                                           — what enableDeviceTracker does
   (c) tracked feed: ss_feed_acquire / ss_feed_submit with an stf_ctx on the feed (depth 3), stf_collect of the
                batch submitted two turns earlier, sst_process_frame_digest per frame, stf_post_keys — what specscan_replay --track does
+  (d) tracked feed, sparse: route (c) on an engine WITHOUT SS_FLAG_KEEP_PLANES, stf_create_sparse (include/specscan_track_sparse.h)
+               — what specscan_replay --track-sparse does
+  (u) untracked feed: route (c)'s turns with no tracker at all (ss_feed_collect, no per-frame loop): the scan alone, the floor of c and d
 
 at 8192 points in 1024-frame batches and at 2^20 points in 16-frame batches. Wall clock around the whole batch (the call, the
 digest, the tracker's frames), median of --reps repetitions after a warm-up; both routes go through the C ABI with buffers allocated
 once, and the per-frame loop is the same Python loop in all. Route (c)'s turn is: fill a pinned slot, submit it, and — from the third
 turn on — collect, track and post the oldest batch, so its time per turn is its time per batch with two batches in flight (what it
 leaves in flight when its turn ends is a millisecond or two of device work that finishes while its own tracker loop still runs).
-Prints one JSON line per shape. With --route b (or c) only that route runs: the form to put behind
+Routes on a feed also report what their scan culled (ss_get_stats: tiles_culled / tiles_tested) and, route (d), what its replay ran
+(stf_sparse_stats: tiles_evaluated / tiles_in_batches); `d_minus_c_ms_median` is the median of the turn-by-turn differences of the two
+interleaved routes. Prints one JSON line per shape. With --route b (or c) only that route runs: the form to put behind
 `rocprofv3 --kernel-trace --stats --` for the device times of the digest's kernels.
 
-    python scripts/track_digest_rate.py [--reps 7] [--route abc|ab|a|b|c] [--shapes 8192,1048576] [--group G]
+    python scripts/track_digest_rate.py [--reps 7] [--warm 3] [--route abc|ab|a|b|c|d|ucd|...] [--shapes 8192,1048576] [--group G]
 
---group G replaces the shapes' group_size (128 and 547).
+--group G replaces the shapes' group_size (128 and 547). --level L: start_level of the engines and of the trackers (default: the
+reference's 8 dB; the script's streams learn their ceiling from 7 frames, which leaves the noise tiles' culling bounds above 8 dB —
+nothing is culled there on any route —, at 15 dB the noise tiles are).
 """
 from __future__ import annotations
 
@@ -42,10 +49,11 @@ def at(a, offset_elems, typ):
 
 
 class Route:
-    def __init__(self, n, fs, batch, g, digest: bool):
+    def __init__(self, n, fs, batch, g, digest: bool, level=8.0):
         self.n, self.batch, self.digest = n, batch, digest
-        self.eng = pkg.SpectrumEngine(fs, 145_000_000, fft_size=n, decim=1, max_batch=batch, learn_ms=280, flags=abi.SS_FLAG_KEEP_PLANES if digest else 0)
-        self.trk = tracker.SignalTracker(n, fs, group_size=g, min_time_ms=200, timeout_ms=400)
+        self.eng = pkg.SpectrumEngine(fs, 145_000_000, fft_size=n, decim=1, max_batch=batch, learn_ms=280, start_level=level,
+                                      flags=abi.SS_FLAG_KEEP_PLANES if digest else 0)
+        self.trk = tracker.SignalTracker(n, fs, group_size=g, start_level=level, min_time_ms=200, timeout_ms=400)
         self.cap = batch * 1024
         self.psd = np.empty((batch, n), np.float32)
         self.rel = None if digest else np.empty((batch, n), np.float32)
@@ -95,15 +103,16 @@ class Route:
 
 
 class FeedRoute:
-    """Route (c): the tracked feed, two batches in flight."""
+    """Routes (c), (d), (u): the feed, two batches in flight — tracked on kept planes, tracked sparse, or not tracked."""
 
-    def __init__(self, n, fs, batch, g):
-        self.n, self.batch = n, batch
-        self.eng = pkg.SpectrumEngine(fs, 145_000_000, fft_size=n, decim=1, max_batch=batch, learn_ms=280, flags=abi.SS_FLAG_KEEP_PLANES)
-        self.trk = tracker.SignalTracker(n, fs, group_size=g, min_time_ms=200, timeout_ms=400)
+    def __init__(self, n, fs, batch, g, sparse=False, tracked=True, level=8.0):
+        self.n, self.batch, self.sparse = n, batch, sparse
+        self.eng = pkg.SpectrumEngine(fs, 145_000_000, fft_size=n, decim=1, max_batch=batch, learn_ms=280, start_level=level,
+                                      flags=abi.SS_FLAG_KEEP_PLANES if tracked and not sparse else 0)
+        self.trk = tracker.SignalTracker(n, fs, group_size=g, start_level=level, min_time_ms=200, timeout_ms=400)
         self.feed = self.eng.feed(depth=3, cand_cap=batch * 1024)
-        self.stf = self.feed.track(g, max_watch=4096)
-        self.res = self.stf._result()
+        self.stf = self.feed.track(g, max_watch=4096, sparse=sparse) if tracked else None
+        self.res = self.stf._result() if tracked else abi.SsFeedResult()
         self.tx = np.empty(2 * n, np.int32)
         self.sig = np.empty(n, np.int32)
         self.nsig = C.c_int()
@@ -113,6 +122,11 @@ class FeedRoute:
 
     def collect(self):
         lib, hl, n = self.eng._lib, self.trk._lib, self.n
+        if self.stf is None:
+            st = lib.ss_feed_collect(self.feed._h, C.byref(self.res))
+            assert st == 0, (st, lib.ss_last_error(self.eng._h))
+            self.times.pop(0)
+            return 0
         st = lib.stf_collect(self.stf._h, C.byref(self.res))
         assert st == 0, (st, lib.stf_last_error(self.stf._h))
         r, t = self.res, self.times.pop(0)
@@ -147,15 +161,32 @@ class FeedRoute:
         return seen
 
 
-LABELS = {"a": "planes", "b": "digest", "c": "feed"}
+    def tile_stats(self):
+        self.eng.sync()
+        s = self.eng.stats()
+        out = {"tiles_total": s["tiles_total"], "tiles_tested": s["tiles_tested"], "tiles_culled": s["tiles_culled"],
+               "culled_over_tested": round(s["tiles_culled"] / s["tiles_tested"], 4) if s["tiles_tested"] else None}
+        if self.sparse:
+            r = self.stf.sparse_stats()
+            out.update(r, evaluated_over_in_batches=round(r["tiles_evaluated"] / max(1, r["tiles_in_batches"]), 4))
+        return out
 
 
-def shape(n, batch, g, reps, routes, warm=3, distinct=4):
+LABELS = {"a": "planes", "b": "digest", "c": "feed", "d": "feed_sparse", "u": "feed_untracked"}
+
+
+def make_route(name, n, fs, batch, g, level):
+    if name in "cdu":
+        return FeedRoute(n, fs, batch, g, sparse=name == "d", tracked=name != "u", level=level)
+    return Route(n, fs, batch, g, digest=name == "b", level=level)
+
+
+def shape(n, batch, g, reps, routes, warm=3, distinct=4, level=8.0):
     fs = 2_048_000 if n == 8192 else n * 250
     band = pkg.synth.SyntheticBand(n, seed=0, on_frame=batch // 8 + 30, off_frame=5 * max(batch, 64) // 8 + 30, period=max(batch, 64) + 60)
     batches = [band.frames_cf32(batch) for _ in range(distinct)]
-    out = {"fft_size": n, "batch": batch, "group_size": g, "reps": reps}
-    made = {name: FeedRoute(n, fs, batch, g) if name == "c" else Route(n, fs, batch, g, digest=name == "b") for name in routes}
+    out = {"fft_size": n, "batch": batch, "group_size": g, "start_level": level, "reps": reps}
+    made = {name: make_route(name, n, fs, batch, g, level) for name in routes}
     times = {name: [] for name in routes}
     seen = {name: 0 for name in routes}
     for k in range(warm + reps):  # the routes alternate batch by batch: whatever else the host does meets both
@@ -173,10 +204,19 @@ def shape(n, batch, g, reps, routes, warm=3, distinct=4):
         if name == "b":
             out["digest_d2h_bytes_last"] = route.d2h
             out["planes_d2h_bytes"] = 8 * n * batch
-    if "c" in made:  # (its transmissions lag two batches behind the other routes')
-        out["feed_d2h_bytes_last"] = made["c"].d2h
-        made["c"].drain()
-        out["feed_transmissions_warm_up_included"] = made["c"].total
+    for name in "cdu":  # (their transmissions lag two batches behind the other routes')
+        if name in made:
+            label = LABELS[name]
+            out[f"{label}_d2h_bytes_last"] = made[name].d2h
+            made[name].drain()
+            out[f"{label}_transmissions_warm_up_included"] = made[name].total
+            out[f"{label}_tiles"] = made[name].tile_stats()
+    for x, y in (("d", "c"), ("c", "u"), ("d", "u")):  # paired: the routes alternate turn by turn
+        if x in made and y in made:
+            out[f"{x}_minus_{y}_ms_median"] = round(1e3 * statistics.median(p - q for p, q in zip(times[x], times[y])), 3)
+    if "c" in made and "d" in made:
+        out["same_transmission_count_c_d"] = made["c"].total == made["d"].total
+        out["feed_sparse_over_feed"] = round(out["feed_sparse_ms_median"] / out["feed_ms_median"], 4)
     if "b" in made and "c" in made:
         out["feed_over_digest"] = round(out["feed_ms_median"] / out["digest_ms_median"], 4)
     if "a" in made and "b" in made:
@@ -188,13 +228,17 @@ def shape(n, batch, g, reps, routes, warm=3, distinct=4):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--route", default="ab", choices=("abc", "ab", "a", "b", "c"))
+    ap.add_argument("--warm", type=int, default=3)
+    ap.add_argument("--route", default="ab", help="any of a, b, c, d, u, in the order they are to alternate")
     ap.add_argument("--shapes", default="8192,1048576")
     ap.add_argument("--group", type=int, default=None)
+    ap.add_argument("--level", type=float, default=8.0)
     args = ap.parse_args()
     for n in (int(s) for s in args.shapes.split(",")):
         g = args.group if args.group is not None else 128 if n == 8192 else 547
-        shape(n, 1024 if n == 8192 else 16, g, args.reps, list(args.route))
+        if not args.route or set(args.route) - set("abcdu") or ("d" in args.route and n > 32768):
+            ap.error("--route: letters of abcdu (d: up to 32768 points)")
+        shape(n, 1024 if n == 8192 else 16, g, args.reps, list(dict.fromkeys(args.route)), warm=args.warm, level=args.level)
 
 
 if __name__ == "__main__":
