@@ -12,10 +12,9 @@ LIB = os.path.join(CSRC, "libspecscan.so")
 # Used by the A/B tests and the measurement scripts only; the product library never reads the environment.
 LIB_DIAG = os.path.join(CSRC, "libspecscan_diag.so")
 SOURCES = ["specscan.hip", "channelizer.hip"]
-HEADERS = ["fft_kernels.h", "fft8192_kernel.h", "fft8192_v2.h", "scan_step.h", "fft256_kernels.h", "detect_kernels.h", "detect_fused.h", "reference_nan.h", "fft1024_kernels.h", "ring_place.h", "stage_slots.h",
-           "track_digest.h", "track_digest_blocked.h", "track_feed.h", "track_sparse.h", "chan_ranges.h", "spectrogram_gate.h", "spectrogram_rows.h", os.path.join("..", "..", "include", "specscan_spectrogram_feed.h"), os.path.join("..", "..", "include", "specscan.h"), os.path.join("..", "..", "include", "specscan_channelizer.h"),
-           os.path.join("..", "..", "include", "specscan_track.h"), os.path.join("..", "..", "include", "specscan_track_feed.h"), os.path.join("..", "..", "include", "specscan_track_sparse.h"),
-           os.path.join("..", "..", "include", "specscan_record_feed.h")]
+INCLUDE = os.path.join(HERE, "..", "include")
+# every header a library can depend on: what csrc holds (plain file names) and the public headers (relative to csrc, like SOURCES)
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + sorted(os.path.join("..", "..", "include", f) for f in os.listdir(INCLUDE) if f.endswith(".h"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC", "-shared", "-Wall", "-Wno-unused-result"]
 
 

@@ -4,6 +4,15 @@
 //
 // One ss_ctx = one scan chain of the reference (the blocks SdrDevice::setupChains wires after the
 // Blocker, sources/radio/sdr_device.cpp:161-168) pinned to one HIP device and one stream.
+//
+// This file is the scan engine (ss_*) up to ss_read_noise. The APIs built on it are host code in headers of their own, included
+// at the end and part of this translation unit (the kernel headers define non-template __global__ functions: one inclusion):
+//   host_feed.h              the pipelined feed, ss_feed_* (its slot ring: feed_ring.h)
+//   host_track.h             the tracking digest, st_*
+//   host_track_feed.h        the tracked feed and its sparse form, stf_*
+//   host_record_feed.h       the feed's recorder, srf_*
+//   host_spectrogram_feed.h  the feed's spectrogram rows, sgf_*
+// Their buffers are owned by type (device_buffers.h).
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -563,6 +572,19 @@ int fail_to(char* dst, int status, const char* fmt, ...) {
 template <class... A>
 int fail(ss_ctx* c, int status, const char* fmt, A... a) {
   return fail_to(c ? c->err : g_create_err, status, fmt, a...);
+}
+
+// The objects of the other APIs (host_*.h; T has a member err[512]): each API has a create-time text of its own, so that
+// stf_last_error(NULL) never shows another API's message. Without an object: obj_fail<T>(nullptr, ...).
+template <class T>
+char* create_err() {
+  thread_local char text[512] = "";
+  return text;
+}
+
+template <class T, class... A>
+int obj_fail(T* t, int status, const char* fmt, A... a) {
+  return fail_to(t ? t->err : create_err<T>(), status, fmt, a...);
 }
 
 #define SS_HIP(ctx, call)                                                                              \
@@ -3268,1401 +3290,11 @@ int ss_read_noise(ss_ctx* c, float* thr) {
 
 }  // extern "C"
 
-// ------------------------------------------------------------------------------------------------
-// Pipelined host feeding (include/specscan.h): pinned staging slots, H2D on a copy stream, the chain on
-// the context's stream, exact-size candidate read-back on a third stream at collect time.
-// ------------------------------------------------------------------------------------------------
-struct ss_feed_slot {
-  void* h_in = nullptr;  // pinned
-  void* d_in = nullptr;
-  int32_t* h_off = nullptr;  // pinned
-  int32_t* h_idx = nullptr;
-  float* h_avg = nullptr;
-  float* h_psd = nullptr;
-  int32_t* d_off = nullptr;
-  int32_t* d_idx = nullptr;
-  float* d_avg = nullptr;
-  hipEvent_t ev_h2d = nullptr, ev_done = nullptr;
-  int nframes = 0;
-  int64_t tag = 0;
-  int state = 0;  // 0 free, 1 acquired (being filled), 2 submitted, 3 collected and held for the recorder (srf_*)
-};
-
-struct ss_feed {
-  ss_ctx* c = nullptr;
-  int depth = 0, cand_cap = 0;
-  bool want_psd = false;
-  bool items = false;  // ss_feed_create_items on a decimated context: h_in holds whole items of n * decim samples, d_in their first n
-  std::vector<ss_feed_slot> slots;
-  int next_acquire = 0, next_collect = 0, pending = 0, acquired = -1;
-  hipStream_t copy_stream = nullptr, d2h_stream = nullptr;
-  stf_ctx* tracker = nullptr;  // stf_create: every batch is digested behind its chain (include/specscan_track_feed.h)
-  srf_ctx* recorder = nullptr;  // srf_create: a collected slot stays held until its samples are recorded or let go (include/specscan_record_feed.h)
-  int held = -1;                // the held slot
-  sgf_ctx* spectrogram = nullptr;  // sgf_create: every batch leaves the spectrogram rows it closes (include/specscan_spectrogram_feed.h)
-  int last_collected = -1;         // the slot of the batch collected last: what sgf_rows reads
-};
-
-// What a batch's clock decides for the spectrogram rows, worked out on copies before anything is enqueued (sgf_plan_batch) and
-// taken over once the batch's chain is in the stream (sgf_enqueue).
-struct sgf_plan {
-  int32_t center = 0;
-  int64_t last_send = 0;  // the centre's gate behind the batch
-  int32_t have_last = 0;
-  int32_t ncuts = 0;
-  int32_t cut[SGF_MAX_ROWS];   // the closing frames
-  int64_t time[SGF_MAX_ROWS];  // and their t_ms
-};
-
-namespace {
-// (the tracked feed, further down)
-int stf_enqueue(ss_feed* f, int slot, int nframes);
-void stf_feed_gone(stf_ctx* t);
-void srf_feed_gone(srf_ctx* t);
-void sgf_feed_gone(sgf_ctx* t);
-int sgf_plan_batch(ss_feed* f, int nframes, const int64_t* t_ms, sgf_plan* plan);
-int sgf_enqueue(ss_feed* f, int slot, int nframes, const sgf_plan& plan);
-int feed_collect(ss_feed* f, ss_feed_result* out, stf_result* digest);
-
-void feed_free(ss_feed* f) {
-  if (!f) return;
-  for (auto& s : f->slots) {
-    if (s.h_in) (void)hipHostFree(s.h_in);
-    if (s.h_off) (void)hipHostFree(s.h_off);
-    if (s.h_idx) (void)hipHostFree(s.h_idx);
-    if (s.h_avg) (void)hipHostFree(s.h_avg);
-    if (s.h_psd) (void)hipHostFree(s.h_psd);
-    (void)hipFree(s.d_in);
-    (void)hipFree(s.d_off);
-    (void)hipFree(s.d_idx);
-    (void)hipFree(s.d_avg);
-    if (s.ev_h2d) (void)hipEventDestroy(s.ev_h2d);
-    if (s.ev_done) (void)hipEventDestroy(s.ev_done);
-  }
-  if (f->copy_stream) (void)hipStreamDestroy(f->copy_stream);
-  if (f->d2h_stream) (void)hipStreamDestroy(f->d2h_stream);
-  delete f;
-}
-
-int feed_create(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd, bool items, ss_feed** out) {
-  if (!c || !out) return SS_ERR_INVALID;
-  std::lock_guard<std::mutex> lock(c->mtx);
-  if (depth < 2 || depth > 8 || cand_cap < 0) return fail(c, SS_ERR_INVALID, "feed depth %d (2..8) / cand_cap %d", depth, cand_cap);
-  SS_HIP(c, hipSetDevice(c->cfg.device_id));
-  ss_feed* f = new ss_feed;
-  f->c = c;
-  f->depth = depth;
-  f->cand_cap = cand_cap;
-  f->want_psd = want_psd != 0;
-  f->items = items && c->cfg.decim != 1;  // with decim == 1 the items are the frames: an ordinary feed
-  f->slots.resize((size_t)depth);
-  const size_t in_bytes = in_bytes_per_sample(c->cfg.in_format) * (size_t)c->n * (size_t)c->cfg.max_batch;
-  const size_t host_bytes = f->items ? in_bytes * (size_t)c->cfg.decim : in_bytes;
-  const size_t plane = sizeof(float) * (size_t)c->n * (size_t)c->cfg.max_batch;
-  const size_t ncand = (size_t)(cand_cap > 0 ? cand_cap : 1);
-#define FEED_HIP(call)                                                              \
-  do {                                                                              \
-    hipError_t e_ = (call);                                                         \
-    if (e_ != hipSuccess) {                                                         \
-      feed_free(f);                                                                 \
-      return fail(c, SS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));    \
-    }                                                                               \
-  } while (0)
-  FEED_HIP(hipStreamCreateWithFlags(&f->copy_stream, hipStreamNonBlocking));
-  FEED_HIP(hipStreamCreateWithFlags(&f->d2h_stream, hipStreamNonBlocking));
-  for (auto& s : f->slots) {
-    FEED_HIP(hipHostMalloc(&s.h_in, host_bytes, hipHostMallocDefault));
-    FEED_HIP(hipMalloc(&s.d_in, in_bytes));
-    FEED_HIP(hipHostMalloc((void**)&s.h_off, sizeof(int32_t) * ((size_t)c->cfg.max_batch + 1), hipHostMallocDefault));
-    FEED_HIP(hipHostMalloc((void**)&s.h_idx, sizeof(int32_t) * ncand, hipHostMallocDefault));
-    FEED_HIP(hipHostMalloc((void**)&s.h_avg, sizeof(float) * ncand, hipHostMallocDefault));
-    if (f->want_psd) FEED_HIP(hipHostMalloc((void**)&s.h_psd, plane, hipHostMallocDefault));
-    FEED_HIP(hipMalloc(&s.d_off, sizeof(int32_t) * ((size_t)c->cfg.max_batch + 1)));
-    FEED_HIP(hipMalloc(&s.d_idx, sizeof(int32_t) * ncand));
-    FEED_HIP(hipMalloc(&s.d_avg, sizeof(float) * ncand));
-    FEED_HIP(hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming));
-    FEED_HIP(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
-  }
-#undef FEED_HIP
-  *out = f;
-  return SS_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int ss_feed_create(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd, ss_feed** out) { return feed_create(c, depth, cand_cap, want_psd, false, out); }
-
-int ss_feed_create_items(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd, ss_feed** out) { return feed_create(c, depth, cand_cap, want_psd, true, out); }
-
-void ss_feed_destroy(ss_feed* f) {
-  if (!f) return;
-  {
-    std::lock_guard<std::mutex> lock(f->c->mtx);
-    (void)hipSetDevice(f->c->cfg.device_id);
-    (void)hipStreamSynchronize(f->copy_stream);
-    (void)hipStreamSynchronize(f->c->stream);
-    (void)hipStreamSynchronize(f->d2h_stream);
-    if (f->tracker) stf_feed_gone(f->tracker);
-    if (f->recorder) srf_feed_gone(f->recorder);
-    if (f->spectrogram) sgf_feed_gone(f->spectrogram);
-  }
-  feed_free(f);
-}
-
-int ss_feed_pending(const ss_feed* f) {
-  if (!f) return 0;
-  std::lock_guard<std::mutex> lock(f->c->mtx);
-  return f->pending;
-}
-
-int ss_feed_acquire(ss_feed* f, void** frames) {
-  if (!f || !frames) return SS_ERR_INVALID;
-  ss_ctx* c = f->c;
-  std::lock_guard<std::mutex> lock(c->mtx);
-  if (f->acquired >= 0) {  // acquiring twice without a submit hands out the same buffer
-    *frames = f->slots[(size_t)f->acquired].h_in;
-    return SS_OK;
-  }
-  ss_feed_slot& s = f->slots[(size_t)f->next_acquire];
-  if (s.state != 0) return fail(c, SS_ERR_INVALID, "no free feed slot: collect a batch first");
-  s.state = 1;
-  f->acquired = f->next_acquire;
-  f->next_acquire = (f->next_acquire + 1) % f->depth;
-  *frames = s.h_in;
-  return SS_OK;
-}
-
-int ss_feed_submit(ss_feed* f, int32_t nframes, const int64_t* t_ms, int64_t user_tag) {
-  if (!f) return SS_ERR_INVALID;
-  ss_ctx* c = f->c;
-  std::lock_guard<std::mutex> lock(c->mtx);
-  if (f->acquired < 0) return fail(c, SS_ERR_INVALID, "ss_feed_submit without ss_feed_acquire");
-  if (nframes <= 0) return fail(c, SS_ERR_INVALID, "nframes %d", nframes);
-  if (nframes > c->cfg.max_batch) return fail(c, SS_ERR_BATCH, "nframes %d > max_batch %d", nframes, c->cfg.max_batch);
-  sgf_plan rows_plan;
-  if (f->spectrogram) {  // refusals of the spectrogram rows come before anything is enqueued: the slot stays acquired
-    const int planned = sgf_plan_batch(f, nframes, t_ms, &rows_plan);
-    if (planned != SS_OK) return planned;
-  }
-  SS_HIP(c, hipSetDevice(c->cfg.device_id));
-  ss_feed_slot& s = f->slots[(size_t)f->acquired];
-  const int n = c->n;
-  const size_t row_bytes = in_bytes_per_sample(c->cfg.in_format) * (size_t)n;
-  if (f->items)  // the first n samples of every item: d_in stays compact, and everything behind the copy is an ordinary feed's
-    SS_HIP(c, hipMemcpy2DAsync(s.d_in, row_bytes, s.h_in, row_bytes * (size_t)c->cfg.decim, row_bytes, (size_t)nframes, hipMemcpyHostToDevice, f->copy_stream));
-  else
-    SS_HIP(c, hipMemcpyAsync(s.d_in, s.h_in, row_bytes * (size_t)nframes, hipMemcpyHostToDevice, f->copy_stream));
-  SS_HIP(c, hipEventRecord(s.ev_h2d, f->copy_stream));
-  SS_HIP(c, hipStreamWaitEvent(c->stream, s.ev_h2d, 0));
-  NoiseState* z = nullptr;
-  int st = get_noise(c, &z);
-  if (st != SS_OK) return st;
-  const int n_learn = plan_learning(c, z, nframes, t_ms);
-  const bool want_cands = f->cand_cap > 0;
-  st = run_batch(c, s.d_in, (long long)n, nframes, n_learn, z, nullptr, nullptr, nullptr, s.d_off, want_cands ? s.d_idx : nullptr,
-                 want_cands ? s.d_avg : nullptr, f->cand_cap);
-  if (st != SS_OK) return st;
-  flush_stages(c);  // the slot's results are copied out right behind the batch
-  SS_HIP(c, hipMemcpyAsync(s.h_off, s.d_off, sizeof(int32_t) * ((size_t)nframes + 1), hipMemcpyDeviceToHost, c->stream));
-  if (f->want_psd) SS_HIP(c, hipMemcpyAsync(s.h_psd, c->last_psd, sizeof(float) * (size_t)n * (size_t)nframes, hipMemcpyDeviceToHost, c->stream));
-  if (f->tracker) {  // the digest: behind the chain and the result copies, in front of ev_done; nothing in it waits on the host
-    st = stf_enqueue(f, f->acquired, nframes);
-    if (st != SS_OK) return st;
-  }
-  if (f->spectrogram) {  // the rows this batch closes: one kernel on the dB plane, then exactly their bytes to the slot's pinned memory
-    st = sgf_enqueue(f, f->acquired, nframes, rows_plan);
-    if (st != SS_OK) return st;
-  }
-  SS_HIP(c, hipEventRecord(s.ev_done, c->stream));
-  s.nframes = nframes;
-  s.tag = user_tag;
-  s.state = 2;
-  f->acquired = -1;
-  ++f->pending;
-  return SS_OK;
-}
-
-int ss_feed_collect(ss_feed* f, ss_feed_result* out) {
-  if (!f || !out) return SS_ERR_INVALID;
-  return feed_collect(f, out, nullptr);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The tracking digest (include/specscan_track.h, kernels: track_digest.h, track_digest_blocked.h): what the host-side signal tracker reads of the last
-// batch's rel and avg planes, computed next to them.
-namespace {
-
-// What st_ctx and stf_ctx share: the rel rows getBestIndex looks at, and the ones among them that lie before a batch.
-struct digest_rows {
-  int group_size = 0;
-  float start_level = 0.0f;
-  int nrows = 1;      // ceil(grouping_y / 2): the rel rows getBestIndex looks at
-  int tail_rows = 0;  // nrows - 1: how many of them can lie before a batch
-  float* d_tail[2] = {};  // [tail_rows][n] each; [tail_cur] holds the rows before the next batch, the other one is written by the digest
-  int tail_cur = 0;
-};
-
-// create time: the row count, and whether a tile of the candidates' kernel (track_digest_blocked.h) fits LDS; the message goes to err
-int digest_rows_plan(digest_rows& r, const ss_ctx* scan, int group_size, float start_level, char* err) {
-  r.group_size = group_size;
-  r.start_level = start_level;
-  r.nrows = (scan->cfg.grouping_y + 1) / 2;
-  r.tail_rows = r.nrows - 1;
-  const size_t lds = ss::blocked_lds_bytes(r.nrows, group_size / 2);
-  if (lds > 65536) return fail_to(err, SS_ERR_INVALID, "group_size %d with %d rows needs %zu bytes of LDS per tile (64 KiB at most)", group_size, r.nrows, lds);
-  return SS_OK;
-}
-
-size_t tail_bytes(const digest_rows& r, const ss_ctx* scan) { return sizeof(float) * (size_t)std::max(1, r.tail_rows) * (size_t)scan->n; }
-
-hipError_t tails_alloc(digest_rows& r, const ss_ctx* scan) {
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc(&r.d_tail[k], tail_bytes(r, scan));
-  return e;
-}
-
-// both tails to zero on the context's stream (the caller waits for it)
-hipError_t tails_zero(const digest_rows& r, const ss_ctx* scan) {
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMemsetAsync(r.d_tail[k], 0, tail_bytes(r, scan), scan->stream);
-  return e;
-}
-
-void tails_free(digest_rows& r) {
-  for (float* p : r.d_tail) (void)hipFree(p);
-}
-
-// the rel rows of the last batch and in front of it
-ss::RelRows rel_rows(const ss_ctx* c, const digest_rows& r) {
-  ss::RelRows rows{};
-  rows.n = c->n;
-  rows.n_learn = c->last_n_learn;
-  rows.tail_rows = r.tail_rows;
-  rows.tail = r.d_tail[r.tail_cur];
-  if (c->fused) {
-    rows.psd = c->last_psd;
-    rows.thr = c->last_thr;
-  } else {
-    rows.rel = c->d_rel + (size_t)(c->cfg.grouping_y - 1) * c->n;
-  }
-  return rows;
-}
-
-// the candidates' kernel over the last batch: lists on the device in, cand_best and cand_avg out
-void launch_cand_best(const ss_ctx* c, const digest_rows& r, const ss::RelRows& rows, int nframes, const int32_t* cand_off, const int32_t* cand_idx, int32_t* cand_best,
-                      float* cand_avg) {
-  ss::CandBestArgs a{};
-  a.rows = rows;
-  a.avg = c->last_avg;
-  a.cand_off = cand_off;
-  a.cand_idx = cand_idx;
-  a.cand_best = cand_best;
-  a.cand_avg = cand_avg;
-  a.nframes = nframes;
-  a.tiles = (c->n + ss::kTrackTile - 1) / ss::kTrackTile;
-  a.half = r.group_size / 2;
-  a.nrows = r.nrows;
-  a.width = ss::kTrackTile + 2 * a.half;
-  a.start_level = r.start_level;
-  hipLaunchKernelGGL(ss::k_best_blocked, dim3((unsigned)((size_t)nframes * a.tiles)), dim3(ss::kTrackTile), ss::blocked_lds_bytes(r.nrows, a.half), c->stream, a);
-}
-
-// the batch's last rows into the other tail; flip_tail makes it the current one
-void launch_save_tail(const ss_ctx* c, const digest_rows& r, const ss::RelRows& rows, int nframes) {
-  if (r.tail_rows == 0) return;
-  const size_t total = (size_t)r.tail_rows * (size_t)c->n;
-  hipLaunchKernelGGL(ss::k_save_tail, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream, rows, nframes, r.d_tail[r.tail_cur ^ 1]);
-}
-
-void flip_tail(digest_rows& r) {
-  if (r.tail_rows > 0) r.tail_cur ^= 1;
-}
-
-}  // namespace
-
-struct st_ctx {
-  ss_ctx* scan = nullptr;
-  st_config cfg{};
-  digest_rows rows;
-  unsigned long long seen_batch = 0;  // ss_ctx::batch_no of the last batch digested (or at st_create / st_reset)
-  int32_t *d_off = nullptr, *d_idx = nullptr, *d_best = nullptr, *d_watch = nullptr, *d_pidx = nullptr;
-  float *d_cavg = nullptr, *d_pavg = nullptr;
-  int32_t *h_off = nullptr, *h_idx = nullptr, *h_best = nullptr, *h_watch = nullptr, *h_pidx = nullptr;  // pinned
-  float *h_cavg = nullptr, *h_pavg = nullptr;
-  size_t peak_cap = 0;  // elements of d_pidx / d_pavg / h_pidx / h_pavg (grown to nframes x nwatch as needed)
-  size_t cand_alloc = 0;  // elements of d_idx / d_best / d_cavg and their host twins (grown as needed, cfg.cand_cap at most)
-  std::vector<int32_t> merged;  // the watch list being formed
-  std::vector<uint8_t> mark;    // [n], all zero between digests
-  char err[512] = "";
-};
-
-namespace {
-
-thread_local char g_st_create_err[512] = "";
-
-template <class... A>
-int st_fail(st_ctx* t, int status, const char* fmt, A... a) {
-  return fail_to(t ? t->err : g_st_create_err, status, fmt, a...);
-}
-
-#define ST_HIP(ctx, call)                                                                                 \
-  do {                                                                                                    \
-    hipError_t e_ = (call);                                                                               \
-    if (e_ != hipSuccess) return st_fail(ctx, SS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-  } while (0)
-
-void st_free(st_ctx* t) {
-  if (!t) return;
-  tails_free(t->rows);
-  for (void* p : {(void*)t->d_off, (void*)t->d_idx, (void*)t->d_best, (void*)t->d_watch, (void*)t->d_pidx, (void*)t->d_cavg, (void*)t->d_pavg}) (void)hipFree(p);
-  for (void* p : {(void*)t->h_off, (void*)t->h_idx, (void*)t->h_best, (void*)t->h_watch, (void*)t->h_pidx, (void*)t->h_cavg, (void*)t->h_pavg}) (void)hipHostFree(p);
-  delete t;
-}
-
-// (cfg.cand_cap is a limit, not an allocation: an adapter that cannot know its traffic states fft_size x max_batch and pays for what comes)
-int st_grow_cands(st_ctx* t, size_t need) {
-  if (need <= t->cand_alloc) return SS_OK;
-  const size_t cap = std::min((size_t)t->cfg.cand_cap, std::max({need, t->cand_alloc * 2, (size_t)4096}));
-  for (void* p : {(void*)t->d_idx, (void*)t->d_best, (void*)t->d_cavg}) (void)hipFree(p);
-  for (void* p : {(void*)t->h_idx, (void*)t->h_best, (void*)t->h_cavg}) (void)hipHostFree(p);
-  t->d_idx = t->d_best = t->h_idx = t->h_best = nullptr;
-  t->d_cavg = t->h_cavg = nullptr;
-  t->cand_alloc = 0;
-  ST_HIP(t, hipMalloc(&t->d_idx, sizeof(int32_t) * cap));
-  ST_HIP(t, hipMalloc(&t->d_best, sizeof(int32_t) * cap));
-  ST_HIP(t, hipMalloc(&t->d_cavg, sizeof(float) * cap));
-  ST_HIP(t, hipHostMalloc(&t->h_idx, sizeof(int32_t) * cap));
-  ST_HIP(t, hipHostMalloc(&t->h_best, sizeof(int32_t) * cap));
-  ST_HIP(t, hipHostMalloc(&t->h_cavg, sizeof(float) * cap));
-  t->cand_alloc = cap;
-  return SS_OK;
-}
-
-int st_grow_peaks(st_ctx* t, size_t need) {
-  if (need <= t->peak_cap) return SS_OK;
-  const size_t cap = std::max(need, t->peak_cap * 2);
-  (void)hipFree(t->d_pidx);
-  (void)hipFree(t->d_pavg);
-  (void)hipHostFree(t->h_pidx);
-  (void)hipHostFree(t->h_pavg);
-  t->d_pidx = t->h_pidx = nullptr;
-  t->d_pavg = t->h_pavg = nullptr;
-  t->peak_cap = 0;
-  ST_HIP(t, hipMalloc(&t->d_pidx, sizeof(int32_t) * cap));
-  ST_HIP(t, hipMalloc(&t->d_pavg, sizeof(float) * cap));
-  ST_HIP(t, hipHostMalloc(&t->h_pidx, sizeof(int32_t) * cap));
-  ST_HIP(t, hipHostMalloc(&t->h_pavg, sizeof(float) * cap));
-  t->peak_cap = cap;
-  return SS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int st_create(ss_ctx* scan, const st_config* cfg, st_ctx** out) {
-  if (!scan || !cfg || !out) return st_fail(nullptr, SS_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (cfg->abi_version != ST_ABI_VERSION) return st_fail(nullptr, SS_ERR_INVALID, "abi_version %u, library has %u", cfg->abi_version, ST_ABI_VERSION);
-  if (cfg->group_size < 0 || cfg->max_watch <= 0 || cfg->cand_cap <= 0) return st_fail(nullptr, SS_ERR_INVALID, "group_size >= 0, max_watch > 0 and cand_cap > 0 required");
-  std::lock_guard<std::mutex> lock(scan->mtx);
-  if (!(scan->cfg.flags & SS_FLAG_KEEP_PLANES)) return st_fail(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_KEEP_PLANES (the digest reads the kept dB and avg planes)");
-  digest_rows rows;
-  if (const int st = digest_rows_plan(rows, scan, cfg->group_size, cfg->start_level, g_st_create_err); st != SS_OK) return st;
-  st_ctx* t = new (std::nothrow) st_ctx();
-  if (!t) return st_fail(nullptr, SS_ERR_NOMEM, "out of memory");
-  t->scan = scan;
-  t->cfg = *cfg;
-  t->rows = rows;
-  t->seen_batch = scan->batch_no;
-  const size_t frames = (size_t)scan->cfg.max_batch;
-  bool ok = hipSetDevice(scan->cfg.device_id) == hipSuccess && tails_alloc(t->rows, scan) == hipSuccess && tails_zero(t->rows, scan) == hipSuccess;
-  ok = ok && hipMalloc(&t->d_off, sizeof(int32_t) * (frames + 1)) == hipSuccess && hipHostMalloc(&t->h_off, sizeof(int32_t) * (frames + 1)) == hipSuccess;
-  ok = ok && hipMalloc(&t->d_watch, sizeof(int32_t) * (size_t)cfg->max_watch) == hipSuccess && hipHostMalloc(&t->h_watch, sizeof(int32_t) * (size_t)cfg->max_watch) == hipSuccess;
-  ok = ok && hipStreamSynchronize(scan->stream) == hipSuccess;
-  if (!ok) {
-    const hipError_t e = hipGetLastError();
-    st_free(t);
-    return st_fail(nullptr, SS_ERR_NOMEM, "allocating the digest's buffers failed: %s", hipGetErrorString(e));
-  }
-  *out = t;
-  return SS_OK;
-}
-
-void st_destroy(st_ctx* t) {
-  if (!t) return;
-  {
-    std::lock_guard<std::mutex> lock(t->scan->mtx);
-    (void)hipSetDevice(t->scan->cfg.device_id);
-    (void)hipStreamSynchronize(t->scan->stream);
-  }
-  st_free(t);
-}
-
-const char* st_last_error(const st_ctx* t) { return t ? t->err : g_st_create_err; }
-
-int st_reset(st_ctx* t) {
-  if (!t) return SS_ERR_INVALID;
-  ss_ctx* c = t->scan;
-  std::lock_guard<std::mutex> lock(c->mtx);
-  ST_HIP(t, hipSetDevice(c->cfg.device_id));
-  ST_HIP(t, hipMemsetAsync(t->rows.d_tail[t->rows.tail_cur], 0, tail_bytes(t->rows, c), c->stream));
-  ST_HIP(t, hipStreamSynchronize(c->stream));
-  t->seen_batch = c->batch_no;
-  return SS_OK;
-}
-
-int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const int32_t* keys, int32_t nkeys, st_result* out) {
-  if (!t) return SS_ERR_INVALID;
-  if (!cand_off || !out || nkeys < 0 || (nkeys > 0 && !keys)) return st_fail(t, SS_ERR_INVALID, "null argument");
-  ss_ctx* c = t->scan;
-  std::lock_guard<std::mutex> lock(c->mtx);
-  const int n = c->n, nframes = c->last_n;
-  if (nframes <= 0) return st_fail(t, SS_ERR_INVALID, "no batch processed since ss_create / ss_reset / ss_reset_noise");
-  if (c->batch_no == t->seen_batch) return st_fail(t, SS_ERR_INVALID, "the last batch has been digested already (or none has run since st_create / st_reset)");
-  if (c->batch_no != t->seen_batch + 1)
-    return st_fail(t, SS_ERR_INVALID, "%llu batches went by without st_digest: the kept rel rows are stale until st_reset", c->batch_no - t->seen_batch - 1);
-  if (c->last_retunes != c->retunes) return st_fail(t, SS_ERR_INVALID, "ss_set_frequency_range since the last batch: its noise ceiling is not the current one");
-  if (!c->last_avg || (c->fused && (!c->last_psd || !c->last_thr))) return st_fail(t, SS_ERR_INVALID, "the last batch left no dB plane, avg plane or noise ceiling to digest");
-  // the lists: offsets clipped to what the batch's call could write (SS_ERR_CAND_OVERFLOW leaves truncated lists), bins checked
-  const int64_t cap = c->last_cand_cap > 0 ? c->last_cand_cap : 0;
-  int64_t prev = 0;
-  for (int f = 0; f <= nframes; ++f) {
-    int64_t o = cand_off[f];
-    if (o < prev || (f == 0 && o != 0)) return st_fail(t, SS_ERR_INVALID, "cand_off is not a list of offsets (frame %d)", f);
-    prev = o;
-    if (o > cap) o = cap;
-    t->h_off[f] = (int32_t)o;
-  }
-  const int ncand = t->h_off[nframes];
-  if (ncand > t->cfg.cand_cap) return st_fail(t, SS_ERR_INVALID, "%d candidates > cand_cap %d", ncand, t->cfg.cand_cap);
-  if (ncand > 0 && !cand_idx) return st_fail(t, SS_ERR_INVALID, "null argument");
-  ST_HIP(t, hipSetDevice(c->cfg.device_id));
-  if (const int st = st_grow_cands(t, (size_t)ncand); st != SS_OK) return st;
-  for (int j = 0; j < ncand; ++j) {
-    const int32_t b = cand_idx[j];
-    if (b < 0 || b >= n) return st_fail(t, SS_ERR_INVALID, "candidate %d: bin %d outside [0, %d)", j, b, n);
-    t->h_idx[j] = b;
-  }
-  if (nkeys > t->cfg.max_watch) return st_fail(t, SS_ERR_INVALID, "%d keys > max_watch %d", nkeys, t->cfg.max_watch);
-  for (int k = 0; k < nkeys; ++k)
-    if (keys[k] < 0 || keys[k] >= n) return st_fail(t, SS_ERR_INVALID, "key %d: bin %d outside [0, %d)", k, keys[k], n);
-  flush_stages(c);
-  const ss::RelRows rows = rel_rows(c, t->rows);
-  uint64_t d2h = 0;
-  if (ncand > 0) {
-    ST_HIP(t, hipMemcpyAsync(t->d_off, t->h_off, sizeof(int32_t) * ((size_t)nframes + 1), hipMemcpyHostToDevice, c->stream));
-    ST_HIP(t, hipMemcpyAsync(t->d_idx, t->h_idx, sizeof(int32_t) * (size_t)ncand, hipMemcpyHostToDevice, c->stream));
-    launch_cand_best(c, t->rows, rows, nframes, t->d_off, t->d_idx, t->d_best, t->d_cavg);
-    ST_HIP(t, hipGetLastError());
-    ST_HIP(t, hipMemcpyAsync(t->h_best, t->d_best, sizeof(int32_t) * (size_t)ncand, hipMemcpyDeviceToHost, c->stream));
-    ST_HIP(t, hipMemcpyAsync(t->h_cavg, t->d_cavg, sizeof(float) * (size_t)ncand, hipMemcpyDeviceToHost, c->stream));
-    ST_HIP(t, stream_wait(c->stream));
-    d2h += 8ull * (uint64_t)ncand;
-  }
-  // the watch list: every key the tracker can hold while it walks the batch
-  // (one flag per bin and a walk over the bins: a batch brings hundreds of thousands of candidates and a handful of distinct keys)
-  std::vector<int32_t>& w = t->merged;
-  w.clear();
-  t->mark.resize((size_t)n, 0);
-  for (int k = 0; k < nkeys; ++k) t->mark[(size_t)keys[k]] = 1;
-  bool sane = true;
-  for (int j = 0; j < ncand; ++j) {
-    const uint32_t b = (uint32_t)t->h_best[j];
-    if (b < (uint32_t)n) t->mark[b] = 1;
-    else sane = false;
-  }
-  for (int b = 0; b < n; ++b)
-    if (t->mark[(size_t)b]) {
-      w.push_back(b);
-      t->mark[(size_t)b] = 0;
-    }
-  if (!sane) return st_fail(t, SS_ERR_HIP, "the candidates' kernel returned a bin outside [0, %d)", n);
-  const int nwatch = (int)w.size();
-  if (nwatch > t->cfg.max_watch) return st_fail(t, SS_ERR_INVALID, "%d watch keys > max_watch %d", nwatch, t->cfg.max_watch);
-  if (nwatch > 0) {
-    const int st = st_grow_peaks(t, (size_t)nframes * (size_t)nwatch);
-    if (st != SS_OK) return st;
-    memcpy(t->h_watch, w.data(), sizeof(int32_t) * (size_t)nwatch);
-    ST_HIP(t, hipMemcpyAsync(t->d_watch, t->h_watch, sizeof(int32_t) * (size_t)nwatch, hipMemcpyHostToDevice, c->stream));
-    ss::WindowPeaksArgs p{};
-    p.avg = c->last_avg;
-    p.watch = t->d_watch;
-    p.peak_idx = t->d_pidx;
-    p.peak_avg = t->d_pavg;
-    p.n = n;
-    p.nframes = nframes;
-    p.nwatch = nwatch;
-    p.half = t->rows.group_size / 2;
-    const size_t items = (size_t)nframes * (size_t)nwatch;
-    hipLaunchKernelGGL(ss::k_window_peaks, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, c->stream, p);
-    ST_HIP(t, hipGetLastError());
-    ST_HIP(t, hipMemcpyAsync(t->h_pidx, t->d_pidx, sizeof(int32_t) * items, hipMemcpyDeviceToHost, c->stream));
-    ST_HIP(t, hipMemcpyAsync(t->h_pavg, t->d_pavg, sizeof(float) * items, hipMemcpyDeviceToHost, c->stream));
-    d2h += 8ull * (uint64_t)items;
-  }
-  launch_save_tail(c, t->rows, rows, nframes);
-  ST_HIP(t, hipGetLastError());
-  ST_HIP(t, stream_wait(c->stream));
-  flip_tail(t->rows);
-  t->seen_batch = c->batch_no;
-  out->nframes = nframes;
-  out->ncand = ncand;
-  out->nwatch = nwatch;
-  out->cand_best = t->h_best;
-  out->cand_avg = t->h_cavg;
-  out->watch = t->h_watch;
-  out->peak_idx = t->h_pidx;
-  out->peak_avg = t->h_pavg;
-  out->d2h_bytes = d2h;
-  return SS_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The tracking digest behind the pipelined feed (include/specscan_track_feed.h, kernels: track_feed.h + track_digest.h): every batch
-// submitted through a tracked feed is digested on the context's stream right behind its chain; the watch list is formed on the
-// device from sequence-number marks, so no step waits for the host.
-//
-// Ordering against the next batch's chain, which may run on the library's own queues and rotates the PSD / avg / mask / offset
-// buffers (and raises the noise ceiling in place while it learns): the digest is on the context's stream, and whatever that stream
-// holds comes before a batch — an in-order call is on that stream itself, and an overlapped call's first launch waits for an event
-// recorded behind it (run_call_deep: "whatever the public stream holds ... comes first"; the want_psd copy of ss_feed_submit
-// rests on the same lines). ss_feed_submit has drained the deferred stages (flush_stages joins the queues into the stream) before
-// the digest is enqueued, so the digest in turn sees the whole batch.
-struct stf_slot {
-  int32_t *d_coff = nullptr, *d_best = nullptr, *d_watch = nullptr, *d_pidx = nullptr, *d_keys = nullptr;
-  float *d_cavg = nullptr, *d_pavg = nullptr;
-  ss::FeedDigestHeader* d_hdr = nullptr;
-  int32_t *h_best = nullptr, *h_watch = nullptr, *h_pidx = nullptr, *h_keys = nullptr;  // pinned
-  float *h_cavg = nullptr, *h_pavg = nullptr;
-  ss::FeedDigestHeader* h_hdr = nullptr;
-  uint64_t seq = 0, keys_seq = 0;
-};
-
-struct stf_ctx {
-  ss_ctx* scan = nullptr;
-  ss_feed* feed = nullptr;  // null once the feed has been destroyed: only stf_destroy / stf_last_error from then on
-  stf_config cfg{};
-  digest_rows rows;
-  uint32_t *d_mark = nullptr, *d_keymark = nullptr;  // [n] each: sequence number of the newest batch that had the bin as cand_best / as a posted key
-  int32_t* d_counts = nullptr;                       // [ceil(n / 256)] block counts, then their prefix sums
-  int nblocks = 0;
-  std::vector<stf_slot> slots;
-  uint64_t next_seq = 1, collected = 0;  // the next batch's sequence number; the newest collected one
-  uint64_t post_seq = 0;                 // p and K_p as last posted
-  std::vector<int32_t> post_keys;
-  // stf_create_sparse on a context that keeps no planes (include/specscan_track_sparse.h, kernels: track_sparse.h)
-  bool sparse = false;
-  uint32_t* d_sp_mask = nullptr;               // [(n / 32) x max_batch] the replayed tiles' mask words: never read
-  int* d_sp_counts = nullptr;                  // [max_batch] ... and their counts
-  int32_t* d_col_flag = nullptr;               // [nblocks] the tile columns the batch's watch windows touch
-  unsigned long long* d_sp_evaluated = nullptr;  // tiles the replay ran, since stf_create_sparse / stf_reset
-  uint64_t sp_tiles_in_batches = 0;
-  char err[512] = "";
-};
-
-namespace {
-
-thread_local char g_stf_create_err[512] = "";
-
-template <class... A>
-int stf_fail(stf_ctx* t, int status, const char* fmt, A... a) {
-  return fail_to(t ? t->err : g_stf_create_err, status, fmt, a...);
-}
-
-void stf_free(stf_ctx* t) {
-  if (!t) return;
-  tails_free(t->rows);
-  for (void* p : {(void*)t->d_mark, (void*)t->d_keymark, (void*)t->d_counts, (void*)t->d_sp_mask, (void*)t->d_sp_counts, (void*)t->d_col_flag, (void*)t->d_sp_evaluated})
-    (void)hipFree(p);
-  for (auto& s : t->slots) {
-    for (void* p : {(void*)s.d_coff, (void*)s.d_best, (void*)s.d_watch, (void*)s.d_pidx, (void*)s.d_keys, (void*)s.d_cavg, (void*)s.d_pavg, (void*)s.d_hdr}) (void)hipFree(p);
-    for (void* p : {(void*)s.h_best, (void*)s.h_watch, (void*)s.h_pidx, (void*)s.h_keys, (void*)s.h_cavg, (void*)s.h_pavg, (void*)s.h_hdr}) (void)hipHostFree(p);
-  }
-  delete t;
-}
-
-// (under the context's lock) rows, marks and post back to zero, on the context's stream
-hipError_t stf_clear(stf_ctx* t) {
-  ss_ctx* c = t->scan;
-  hipError_t e = tails_zero(t->rows, c);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_mark, 0, sizeof(uint32_t) * (size_t)c->n, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_keymark, 0, sizeof(uint32_t) * (size_t)c->n, c->stream);
-  if (e == hipSuccess && t->sparse) e = hipMemsetAsync(t->d_sp_evaluated, 0, sizeof(unsigned long long), c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  t->sp_tiles_in_batches = 0;
-  t->next_seq = 1;
-  t->collected = 0;
-  t->post_seq = 0;
-  t->post_keys.clear();
-  return e;
-}
-
-void stf_feed_gone(stf_ctx* t) { t->feed = nullptr; }
-
-// A sparse object, between the watch list and the peaks: avg in the tile columns the watch windows touch, by the batch's own detect
-// stage once more (track_sparse.h) — its arguments as they were launched (ss_ctx::last_det), with everything but avg switched off:
-//   maskbits, counts  scratch of the tracker's. The scan's mask buffers are all zero between uses (EmitArgs::clear_masks: culled tiles
-//                     write nothing and rely on it) and its count buffers are zeroed on a schedule of their own: words written there
-//                     now would be a later batch's candidates.
-//   avg_out           the batch's sparse plane (ss_ctx::last_avg = DetectArgs::avg_sparse): every cell of a marked column, hit or not
-//   rel_out, hist_out nothing: hist_by_fft = 1 — the ring has this batch's rows already (its own tiles, its FFT stage or the drain's
-//                     k_ring_fill wrote them: flush_stages has run)
-//   segsum, halo_segsum, live, tile_list, stats   nothing is culled, waited for or counted: ss_get_stats does not move
-//   spec_*            zero, and the SPEC = false tile: a SS_FLAG_SPECTROGRAM context does not accumulate the batch twice
-// The rows in front of the batch are read where the detect stage read them, hist_in or halo_psd as launched (the same bits either way,
-// detect_fused.h: DetectArgs::halo_psd). Both are intact here, and stay so until the replay has read them:
-//   * the ring window [hist_in, hist_in + 35 rows): a call's own rows never land on its own window (ring_place.h: the first thing
-//     ring_place_decide checks), so neither this batch's tiles nor its FFT stage nor the drain's k_ring_fill (hist_out) touched it. The
-//     next writers are a LATER call's rows, or that call's place_ring moving the window to the front (k_hist_shift, on this stream) or
-//     settling dB rows in place (k_rows_sub_thr, on this stream): all enqueued after this replay. Calls through the feed are not
-//     overlapped (run_batch: allow_overlap = false), so they carry no halo_psd; if one did, its halo buffer (d_halo[L mod 2 nq]) is
-//     next written 2 nq launches on, by a call enqueued later.
-//   * the dB plane (d_psd2 rotation, DetectArgs::psd = last_psd), the noise ceiling and the pass mask: what k_best_blocked and k_save_tail
-//     of the same digest read, on the same grounds (the comment above stf_slot).
-//   * d_avg2[b] comes round again after nbuf batches — as the sparse plane of a later batch's detect stage, behind this stream.
-// A later call's launches on the library's own queues wait for an event recorded on this stream first ("whatever the public stream
-// holds ... comes first"), in-order calls are on it: everything above is ordered behind the digest by that one rule.
-int stf_replay_watch_tiles(stf_ctx* t, stf_slot& s, int nframes) {
-  ss_ctx* c = t->scan;
-  const int n = c->n;
-  if (!c->last_det_ok || c->last_det.psd != c->last_psd || c->last_det.nframes != nframes || c->last_det.n != n || c->last_det.avg_sparse != c->last_avg)
-    return fail(c, SS_ERR_INVALID, "tracked feed (sparse): the detect stage launched last is not this batch's");
-  hipLaunchKernelGGL(ss::k_feed_watch_cols, dim3(1), dim3(256), 0, c->stream, (const int32_t*)s.d_watch, (const ss::FeedDigestHeader*)s.d_hdr, n, t->rows.group_size / 2,
-                     t->d_col_flag);
-  ss::WatchTilesArgs wa{};
-  wa.det = c->last_det;
-  wa.det.maskbits = t->d_sp_mask;
-  wa.det.counts = t->d_sp_counts;
-  wa.det.rel_out = nullptr;
-  wa.det.avg_out = const_cast<float*>(c->last_avg);
-  wa.det.hist_out = nullptr;
-  wa.det.hist_by_fft = 1;
-  wa.det.segsum = nullptr;
-  wa.det.halo_segsum = nullptr;
-  wa.det.live = nullptr;
-  wa.det.tile_list = nullptr;
-  wa.det.stats = nullptr;
-  wa.det.spec_partial = nullptr;
-  wa.det.spec_prev_partial = nullptr;
-  wa.det.spec_prev_sum = nullptr;
-  wa.det.spec_prev_tiles = 0;
-  wa.det.spec_m = wa.det.spec_n = 0;
-#ifdef SS_DIAG
-  wa.det.stamp_mid = nullptr;
-  wa.det.cull_stats = nullptr;
-#endif
-  wa.col_flag = t->d_col_flag;
-  wa.evaluated = t->d_sp_evaluated;
-  const int frame_tiles = (nframes + wa.det.shift + kFusedTF - 1) / kFusedTF, cols = t->nblocks;  // (256-bin blocks: the tile columns)
-  hipLaunchKernelGGL(ss::k_watch_tiles, dim3((unsigned)(frame_tiles * cols)), dim3(256), 0, c->stream, wa);
-  t->sp_tiles_in_batches += (uint64_t)frame_tiles * (uint64_t)cols;
-  return SS_OK;
-}
-
-// ss_feed_submit, under the context's lock, behind flush_stages and the result copies: the digest of the batch just enqueued.
-int stf_enqueue(ss_feed* f, int slot_no, int nframes) {
-  stf_ctx* t = f->tracker;
-  ss_ctx* c = f->c;
-  ss_feed_slot& fs = f->slots[(size_t)slot_no];
-  stf_slot& s = t->slots[(size_t)slot_no];
-  const int n = c->n;
-  if (t->next_seq > 0xffffffffull) return fail(c, SS_ERR_INVALID, "tracked feed: 2^32 - 1 batches since stf_create / stf_reset (the device counts in 32 bits): stf_reset");
-  if (!c->last_avg || (c->fused && (!c->last_psd || !c->last_thr)) || (!c->fused && !c->d_rel))
-    return fail(c, SS_ERR_INVALID, "tracked feed: the batch left no dB plane, avg plane or noise ceiling to digest");
-  const uint32_t seq = (uint32_t)t->next_seq, p = (uint32_t)t->post_seq;
-  const int nkeys = (int)t->post_keys.size();
-  if (nkeys > 0) {
-    memcpy(s.h_keys, t->post_keys.data(), sizeof(int32_t) * (size_t)nkeys);
-    SS_HIP(c, hipMemcpyAsync(s.d_keys, s.h_keys, sizeof(int32_t) * (size_t)nkeys, hipMemcpyHostToDevice, c->stream));
-  }
-  ss::FeedPrepareArgs pa{};
-  pa.off = fs.d_off;
-  pa.coff = s.d_coff;
-  pa.keys = s.d_keys;
-  pa.keymark = t->d_keymark;
-  pa.hdr = s.d_hdr;
-  pa.nframes = nframes;
-  pa.cand_cap = f->cand_cap;
-  pa.nkeys = nkeys;
-  pa.seq = seq;
-  hipLaunchKernelGGL(ss::k_feed_prepare, dim3((unsigned)grid_for((size_t)std::max(nframes + 1, nkeys), 256)), dim3(256), 0, c->stream, pa);
-  const ss::RelRows rows = rel_rows(c, t->rows);
-  launch_cand_best(c, t->rows, rows, nframes, s.d_coff, fs.d_idx, s.d_best, s.d_cavg);
-  hipLaunchKernelGGL(ss::k_feed_stamp, dim3((unsigned)std::min(grid_for((size_t)f->cand_cap, 256), 1024)), dim3(256), 0, c->stream, (const int32_t*)s.d_coff, nframes,
-                     (const int32_t*)s.d_best, t->d_mark, n, seq, s.d_hdr);
-  hipLaunchKernelGGL(ss::k_feed_count, dim3((unsigned)t->nblocks), dim3(ss::kFeedBlock), 0, c->stream, (const uint32_t*)t->d_mark, (const uint32_t*)t->d_keymark, n, p, seq,
-                     t->d_counts);
-  hipLaunchKernelGGL(ss::k_feed_scan, dim3(1), dim3(64), 0, c->stream, t->d_counts, t->nblocks, (const int32_t*)fs.d_off, (const int32_t*)s.d_coff, nframes, t->cfg.max_watch,
-                     s.d_hdr);
-  hipLaunchKernelGGL(ss::k_feed_scatter, dim3((unsigned)t->nblocks), dim3(ss::kFeedBlock), 0, c->stream, (const uint32_t*)t->d_mark, (const uint32_t*)t->d_keymark, n, p, seq,
-                     (const int32_t*)t->d_counts, t->cfg.max_watch, s.d_watch);
-  if (t->sparse) {
-    const int st = stf_replay_watch_tiles(t, s, nframes);
-    if (st != SS_OK) return st;
-  }
-  ss::FeedPeaksArgs pk{};
-  pk.avg = c->last_avg;
-  pk.watch = s.d_watch;
-  pk.hdr = s.d_hdr;
-  pk.peak_idx = s.d_pidx;
-  pk.peak_avg = s.d_pavg;
-  pk.n = n;
-  pk.nframes = nframes;
-  pk.half = t->rows.group_size / 2;
-  // (the list's length is known to the device only: enough workgroups to fill the machine, each walks its share)
-  const size_t most = ((size_t)nframes * (size_t)t->cfg.max_watch + 3) / 4;
-  hipLaunchKernelGGL(ss::k_feed_peaks, dim3((unsigned)std::min<size_t>(most, 2048)), dim3(256), 0, c->stream, pk);
-  launch_save_tail(c, t->rows, rows, nframes);
-  flip_tail(t->rows);  // (stream order: the next batch's digest reads what this one wrote)
-  SS_HIP(c, hipGetLastError());
-  SS_HIP(c, hipMemcpyAsync(s.h_hdr, s.d_hdr, sizeof(ss::FeedDigestHeader), hipMemcpyDeviceToHost, c->stream));
-  s.seq = t->next_seq++;
-  s.keys_seq = t->post_seq;
-  return SS_OK;
-}
-
-// ss_feed_collect and stf_collect: the oldest pending batch, and — digest != nullptr — its digest, read back in exact sizes on the
-// feed's read-back stream next to the candidate lists.
-int feed_collect(ss_feed* f, ss_feed_result* out, stf_result* digest) {
-  ss_ctx* c = f->c;
-  ss_feed_slot* s = nullptr;
-  int slot_no = 0;
-  {
-    std::lock_guard<std::mutex> lock(c->mtx);
-    if (f->tracker && !digest) return fail(c, SS_ERR_INVALID, "ss_feed_collect on a tracked feed: collect through stf_collect");
-    if (f->held >= 0) return fail(c, SS_ERR_INVALID, "the batch collected last is held for the recorder: srf_record or srf_release first");
-    if (f->pending == 0) return fail(c, SS_ERR_INVALID, "ss_feed_collect: nothing pending");
-    slot_no = f->next_collect;
-    s = &f->slots[(size_t)slot_no];
-  }
-  // wait outside the lock: a producer thread may acquire / submit the next slots meanwhile
-  hipError_t e = hipEventSynchronize(s->ev_done);
-  std::lock_guard<std::mutex> lock(c->mtx);
-  if (e != hipSuccess) return fail(c, SS_ERR_HIP, "hipEventSynchronize failed: %s", hipGetErrorString(e));
-  SS_HIP(c, hipSetDevice(c->cfg.device_id));
-  const int total = s->h_off[s->nframes];
-  const int ncopy = total < f->cand_cap ? total : f->cand_cap;
-  bool copies = false;
-  if (ncopy > 0) {
-    SS_HIP(c, hipMemcpyAsync(s->h_idx, s->d_idx, sizeof(int32_t) * (size_t)ncopy, hipMemcpyDeviceToHost, f->d2h_stream));
-    SS_HIP(c, hipMemcpyAsync(s->h_avg, s->d_avg, sizeof(float) * (size_t)ncopy, hipMemcpyDeviceToHost, f->d2h_stream));
-    copies = true;
-  }
-  if (digest) {
-    stf_ctx* t = f->tracker;
-    stf_slot& d = t->slots[(size_t)slot_no];
-    const ss::FeedDigestHeader h = *d.h_hdr;
-    if (h.ncand != ncopy || h.nwatch < 0 || (h.flags & ss::kFeedBadBest))
-      return fail(c, SS_ERR_HIP, "tracked feed: the digest's header does not fit the batch (ncand %d / %d, nwatch %d, flags %d)", h.ncand, ncopy, h.nwatch, h.flags);
-    const bool over = (h.flags & ss::kFeedOverflow) != 0 || h.nwatch > t->cfg.max_watch;
-    const size_t nw = over ? 0 : (size_t)h.nwatch, items = nw * (size_t)s->nframes;
-    if (ncopy > 0) {
-      SS_HIP(c, hipMemcpyAsync(d.h_best, d.d_best, sizeof(int32_t) * (size_t)ncopy, hipMemcpyDeviceToHost, f->d2h_stream));
-      SS_HIP(c, hipMemcpyAsync(d.h_cavg, d.d_cavg, sizeof(float) * (size_t)ncopy, hipMemcpyDeviceToHost, f->d2h_stream));
-    }
-    if (nw > 0) {
-      SS_HIP(c, hipMemcpyAsync(d.h_watch, d.d_watch, sizeof(int32_t) * nw, hipMemcpyDeviceToHost, f->d2h_stream));
-      SS_HIP(c, hipMemcpyAsync(d.h_pidx, d.d_pidx, sizeof(int32_t) * items, hipMemcpyDeviceToHost, f->d2h_stream));
-      SS_HIP(c, hipMemcpyAsync(d.h_pavg, d.d_pavg, sizeof(float) * items, hipMemcpyDeviceToHost, f->d2h_stream));
-      copies = true;
-    }
-    digest->seq = d.seq;
-    digest->keys_seq = d.keys_seq;
-    digest->status = over ? SS_ERR_INVALID : SS_OK;
-    digest->ncand = ncopy;
-    digest->nwatch = h.nwatch;
-    digest->cand_best = d.h_best;
-    digest->cand_avg = d.h_cavg;
-    digest->watch = d.h_watch;
-    digest->peak_idx = d.h_pidx;
-    digest->peak_avg = d.h_pavg;
-    digest->d2h_bytes = sizeof(ss::FeedDigestHeader) + 8ull * (uint64_t)ncopy + 4ull * nw + 8ull * items;
-    t->collected = d.seq;
-  }
-  if (copies) SS_HIP(c, hipStreamSynchronize(f->d2h_stream));
-  out->nframes = s->nframes;
-  out->status = (f->cand_cap > 0 && total > f->cand_cap) ? SS_ERR_CAND_OVERFLOW : SS_OK;
-  out->user_tag = s->tag;
-  out->cand_off = s->h_off;
-  out->cand_idx = s->h_idx;
-  out->cand_avg = s->h_avg;
-  out->psd_db = f->want_psd ? s->h_psd : nullptr;
-  s->state = f->recorder ? 3 : 0;  // held: its d_in is what srf_record reads
-  if (f->recorder) f->held = slot_no;
-  f->last_collected = slot_no;
-  f->next_collect = (f->next_collect + 1) % f->depth;
-  --f->pending;
-  return SS_OK;
-}
-
-// stf_create and stf_create_sparse: allow_sparse = the context may lack SS_FLAG_KEEP_PLANES (the object is a sparse one if it does)
-int stf_create_any(ss_feed* f, const stf_config* cfg, stf_ctx** out, bool allow_sparse) {
-  if (!f || !cfg || !out) return stf_fail(nullptr, SS_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (cfg->abi_version != STF_ABI_VERSION) return stf_fail(nullptr, SS_ERR_INVALID, "abi_version %u, library has %u", cfg->abi_version, STF_ABI_VERSION);
-  if (cfg->group_size < 0 || cfg->max_watch <= 0) return stf_fail(nullptr, SS_ERR_INVALID, "group_size >= 0 and max_watch > 0 required");
-  ss_ctx* c = f->c;
-  std::lock_guard<std::mutex> lock(c->mtx);
-  const bool sparse = allow_sparse && !(c->cfg.flags & SS_FLAG_KEEP_PLANES);
-  if (!allow_sparse && !(c->cfg.flags & SS_FLAG_KEEP_PLANES)) return stf_fail(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_KEEP_PLANES (the digest reads the kept dB and avg planes)");
-  if (sparse && !c->fused)
-    return stf_fail(nullptr, SS_ERR_INVALID, "sparse tracking needs the fused back end (grouping 21 x 21; this context has %d x %d): the unfused back end keeps no sparse avg plane",
-                    c->cfg.grouping_x, c->cfg.grouping_y);
-  if (sparse && c->ref_nan) return stf_fail(nullptr, SS_ERR_INVALID, "sparse tracking on a SS_FLAG_REFERENCE_NAN context: its NaN stage patches the planes behind the tiles");
-  if (sparse && c->n >= 65536) return stf_fail(nullptr, SS_ERR_INVALID, "sparse tracking at fft_size %d: 65536 points and up can leave no bin-ordered dB plane (32768 at most)", c->n);
-  if (f->cand_cap <= 0) return stf_fail(nullptr, SS_ERR_INVALID, "the feed was created with cand_cap 0: there are no candidate lists to digest");
-  if (f->tracker) return stf_fail(nullptr, SS_ERR_INVALID, "the feed already has a tracker");
-  if (f->pending > 0 || f->acquired >= 0) return stf_fail(nullptr, SS_ERR_INVALID, "the feed has batches pending: collect them first");
-  digest_rows rows;
-  if (const int st = digest_rows_plan(rows, c, cfg->group_size, cfg->start_level, g_stf_create_err); st != SS_OK) return st;
-  stf_ctx* t = new (std::nothrow) stf_ctx();
-  if (!t) return stf_fail(nullptr, SS_ERR_NOMEM, "out of memory");
-  t->scan = c;
-  t->feed = f;
-  t->cfg = *cfg;
-  t->rows = rows;
-  t->sparse = sparse;
-  t->nblocks = (c->n + ss::kFeedBlock - 1) / ss::kFeedBlock;
-  t->slots.resize((size_t)f->depth);
-  const size_t n = (size_t)c->n, frames = (size_t)c->cfg.max_batch, cap = (size_t)f->cand_cap, mw = (size_t)cfg->max_watch;
-  bool ok = hipSetDevice(c->cfg.device_id) == hipSuccess && tails_alloc(t->rows, c) == hipSuccess;
-  ok = ok && hipMalloc(&t->d_mark, sizeof(uint32_t) * n) == hipSuccess && hipMalloc(&t->d_keymark, sizeof(uint32_t) * n) == hipSuccess;
-  ok = ok && hipMalloc(&t->d_counts, sizeof(int32_t) * (size_t)t->nblocks) == hipSuccess;
-  for (auto& s : t->slots) {
-    ok = ok && hipMalloc(&s.d_coff, sizeof(int32_t) * (frames + 1)) == hipSuccess && hipMalloc(&s.d_hdr, sizeof(ss::FeedDigestHeader)) == hipSuccess;
-    ok = ok && hipMalloc(&s.d_best, sizeof(int32_t) * cap) == hipSuccess && hipMalloc(&s.d_cavg, sizeof(float) * cap) == hipSuccess;
-    ok = ok && hipMalloc(&s.d_watch, sizeof(int32_t) * mw) == hipSuccess && hipMalloc(&s.d_keys, sizeof(int32_t) * mw) == hipSuccess;
-    ok = ok && hipMalloc(&s.d_pidx, sizeof(int32_t) * frames * mw) == hipSuccess && hipMalloc(&s.d_pavg, sizeof(float) * frames * mw) == hipSuccess;
-    ok = ok && hipHostMalloc(&s.h_hdr, sizeof(ss::FeedDigestHeader)) == hipSuccess;
-    ok = ok && hipHostMalloc(&s.h_best, sizeof(int32_t) * cap) == hipSuccess && hipHostMalloc(&s.h_cavg, sizeof(float) * cap) == hipSuccess;
-    ok = ok && hipHostMalloc(&s.h_watch, sizeof(int32_t) * mw) == hipSuccess && hipHostMalloc(&s.h_keys, sizeof(int32_t) * mw) == hipSuccess;
-    ok = ok && hipHostMalloc(&s.h_pidx, sizeof(int32_t) * frames * mw) == hipSuccess && hipHostMalloc(&s.h_pavg, sizeof(float) * frames * mw) == hipSuccess;
-  }
-  if (sparse) {
-    const size_t words = (n / 32) * frames, plane = sizeof(float) * n * frames;
-    ok = ok && hipMalloc(&t->d_sp_mask, sizeof(uint32_t) * words) == hipSuccess && hipMalloc(&t->d_sp_counts, sizeof(int) * frames) == hipSuccess;
-    ok = ok && hipMalloc(&t->d_col_flag, sizeof(int32_t) * (size_t)t->nblocks) == hipSuccess && hipMalloc(&t->d_sp_evaluated, sizeof(unsigned long long)) == hipSuccess;
-    ok = ok && hipMemsetAsync(t->d_sp_mask, 0, sizeof(uint32_t) * words, c->stream) == hipSuccess && hipMemsetAsync(t->d_sp_counts, 0, sizeof(int) * frames, c->stream) == hipSuccess;
-    ok = ok && hipMemsetAsync(t->d_col_flag, 0, sizeof(int32_t) * (size_t)t->nblocks, c->stream) == hipSuccess;
-    // every sparse plane to NaN, once (all bytes 0xff): a cell of a watch window the replay failed to write would be a NaN peak, not a
-    // plausible value some earlier batch left there. Nothing pending (checked above); the planes are max_batch x n floats each.
-    flush_stages(c);
-    for (int k = 0; k < c->nbuf; ++k) ok = ok && hipMemsetAsync(c->d_avg2[k], 0xff, plane, c->stream) == hipSuccess;
-  }
-  ok = ok && stf_clear(t) == hipSuccess;
-  if (!ok) {
-    const hipError_t e = hipGetLastError();
-    stf_free(t);
-    return stf_fail(nullptr, SS_ERR_NOMEM, "allocating the tracked feed's buffers failed: %s", hipGetErrorString(e));
-  }
-  f->tracker = t;
-  *out = t;
-  return SS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int stf_create(ss_feed* f, const stf_config* cfg, stf_ctx** out) { return stf_create_any(f, cfg, out, false); }
-
-int stf_create_sparse(ss_feed* f, const stf_config* cfg, stf_ctx** out) { return stf_create_any(f, cfg, out, true); }
-
-int stf_sparse_stats(stf_ctx* t, uint64_t* tiles_evaluated, uint64_t* tiles_in_batches) {
-  if (!t) return SS_ERR_INVALID;
-  if (!tiles_evaluated || !tiles_in_batches) return stf_fail(t, SS_ERR_INVALID, "null argument");
-  ss_ctx* c = t->scan;
-  std::lock_guard<std::mutex> lock(c->mtx);
-  if (!t->sparse) return stf_fail(t, SS_ERR_INVALID, "not a sparse object: the scan context keeps its planes (stf_create, or stf_create_sparse with SS_FLAG_KEEP_PLANES), nothing is replayed");
-  if (!t->feed) return stf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
-  unsigned long long ev = 0;
-  if (hipSetDevice(c->cfg.device_id) != hipSuccess || hipMemcpyAsync(&ev, t->d_sp_evaluated, sizeof(ev), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return stf_fail(t, SS_ERR_HIP, "reading the replay's counter failed: %s", hipGetErrorString(hipGetLastError()));
-  *tiles_evaluated = ev;
-  *tiles_in_batches = t->sp_tiles_in_batches;
-  return SS_OK;
-}
-
-void stf_destroy(stf_ctx* t) {
-  if (!t) return;
-  {
-    std::lock_guard<std::mutex> lock(t->scan->mtx);
-    (void)hipSetDevice(t->scan->cfg.device_id);
-    if (t->feed) {  // (a destroyed feed has waited for its streams already)
-      (void)hipStreamSynchronize(t->scan->stream);
-      (void)hipStreamSynchronize(t->feed->d2h_stream);
-      t->feed->tracker = nullptr;
-    }
-  }
-  stf_free(t);
-}
-
-const char* stf_last_error(const stf_ctx* t) { return t ? t->err : g_stf_create_err; }
-
-int stf_post_keys(stf_ctx* t, uint64_t seq, const int32_t* keys, int32_t nkeys) {
-  if (!t) return SS_ERR_INVALID;
-  if (nkeys < 0 || (nkeys > 0 && !keys)) return stf_fail(t, SS_ERR_INVALID, "null argument");
-  std::lock_guard<std::mutex> lock(t->scan->mtx);
-  if (!t->feed) return stf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
-  if (seq > t->collected) return stf_fail(t, SS_ERR_INVALID, "keys after batch %llu, but the newest collected batch is %llu: not collected yet", (unsigned long long)seq, (unsigned long long)t->collected);
-  if (seq < t->post_seq) return stf_fail(t, SS_ERR_INVALID, "keys after batch %llu are older than the last post (%llu)", (unsigned long long)seq, (unsigned long long)t->post_seq);
-  if (nkeys > t->cfg.max_watch) return stf_fail(t, SS_ERR_INVALID, "%d keys > max_watch %d", nkeys, t->cfg.max_watch);
-  for (int k = 0; k < nkeys; ++k)
-    if (keys[k] < 0 || keys[k] >= t->scan->n) return stf_fail(t, SS_ERR_INVALID, "key %d: bin %d outside [0, %d)", k, keys[k], t->scan->n);
-  t->post_seq = seq;
-  t->post_keys.assign(keys, keys + nkeys);
-  return SS_OK;
-}
-
-int stf_collect(stf_ctx* t, stf_result* out) {
-  if (!t) return SS_ERR_INVALID;
-  if (!out) return stf_fail(t, SS_ERR_INVALID, "null argument");
-  ss_feed* f = nullptr;
-  {
-    std::lock_guard<std::mutex> lock(t->scan->mtx);
-    f = t->feed;
-    if (!f) return stf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
-  }
-  const int st = feed_collect(f, &out->batch, out);
-  if (st != SS_OK) {
-    std::lock_guard<std::mutex> lock(t->scan->mtx);
-    return stf_fail(t, st, "%s", t->scan->err);
-  }
-  return SS_OK;
-}
-
-int stf_reset(stf_ctx* t) {
-  if (!t) return SS_ERR_INVALID;
-  ss_ctx* c = t->scan;
-  std::lock_guard<std::mutex> lock(c->mtx);
-  if (!t->feed) return stf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
-  if (t->feed->pending > 0 || t->feed->acquired >= 0) return stf_fail(t, SS_ERR_INVALID, "stf_reset with batches pending: collect them first");
-  if (hipSetDevice(c->cfg.device_id) != hipSuccess || stf_clear(t) != hipSuccess) return stf_fail(t, SS_ERR_HIP, "clearing the kept rows and marks failed: %s", hipGetErrorString(hipGetLastError()));
-  t->rows.tail_cur = 0;
-  return SS_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The recorder bound to the feed (include/specscan_record_feed.h): a channeliser of its own, run on the held slot's upload.
-// The slot bookkeeping (ss_feed::held, ss_feed_slot::state 3) is the scan context's, under its mutex; the channeliser, its planes
-// and the pinned results are the recorder's, under rec_mtx, which is held for a whole srf_record so that the scan context's
-// mutex is not: a producer thread acquires and submits the other slots meanwhile. Lock order: rec_mtx, then the context's.
-struct srf_ctx {
-  ss_ctx* scan = nullptr;
-  ss_feed* feed = nullptr;  // null once the feed has been destroyed: only srf_destroy / srf_last_error from then on
-  srf_config cfg{};
-  char err[512] = "";
-  std::mutex rec_mtx;
-  sc_ctx* chan = nullptr;
-  hipStream_t stream = nullptr;  // the copies of the outputs, behind sc_sync
-  int cap = 0;
-  int8_t* d_i8 = nullptr;
-  float* d_cf32 = nullptr;
-  int8_t* h_i8 = nullptr;  // pinned
-  float* h_cf32 = nullptr;
-  int32_t* h_counts = nullptr;
-  int32_t* h_rc = nullptr;
-};
-
-namespace {
-
-thread_local char g_srf_create_err[512] = "";
-
-template <class... A>
-int srf_fail(srf_ctx* t, int status, const char* fmt, A... a) {
-  return fail_to(t ? t->err : g_srf_create_err, status, fmt, a...);
-}
-
-void srf_free(srf_ctx* t) {
-  if (!t) return;
-  if (t->chan) sc_destroy(t->chan);
-  (void)hipFree(t->d_i8);
-  (void)hipFree(t->d_cf32);
-  if (t->h_i8) (void)hipHostFree(t->h_i8);
-  if (t->h_cf32) (void)hipHostFree(t->h_cf32);
-  if (t->h_counts) (void)hipHostFree(t->h_counts);
-  if (t->h_rc) (void)hipHostFree(t->h_rc);
-  if (t->stream) (void)hipStreamDestroy(t->stream);
-  delete t;
-}
-
-void srf_feed_gone(srf_ctx* t) { t->feed = nullptr; }
-
-// the held slot goes back to the producer (the context's mutex is held)
-void srf_let_go(ss_feed* f) {
-  f->slots[(size_t)f->held].state = 0;
-  f->held = -1;
-}
-
-}  // namespace
-
-extern "C" {
-
-int srf_create(ss_feed* f, const srf_config* cfg, srf_ctx** out) {
-  if (!f || !cfg || !out) return srf_fail(nullptr, SS_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (cfg->abi_version != SRF_ABI_VERSION) return srf_fail(nullptr, SS_ERR_INVALID, "abi_version %u, library has %u", cfg->abi_version, SRF_ABI_VERSION);
-  ss_ctx* c = f->c;
-  std::lock_guard<std::mutex> lock(c->mtx);
-  if (c->cfg.decim != 1 && !f->items)
-    return srf_fail(nullptr, SS_ERR_INVALID, "the scan context has decim %d: an ordinary feed takes only the frames the scan reads, there is no stream to record from (ss_feed_create_items keeps the whole items)", c->cfg.decim);
-  if (f->recorder) return srf_fail(nullptr, SS_ERR_INVALID, "the feed already has a recorder");
-  if (f->pending > 0 || f->acquired >= 0) return srf_fail(nullptr, SS_ERR_INVALID, "the feed has batches pending: collect them first");
-  int32_t max_samples = 0;  // of the recorded stream: whole items (decim is 1 on the device route)
-  if (!chan_ranges::item_samples(c->cfg.max_batch, c->n, c->cfg.decim, &max_samples))
-    return srf_fail(nullptr, SS_ERR_INVALID, "max_batch * N * decim = %lld samples do not fit one channeliser call", (long long)c->cfg.max_batch * c->n * c->cfg.decim);
-  srf_ctx* t = new (std::nothrow) srf_ctx();
-  if (!t) return srf_fail(nullptr, SS_ERR_NOMEM, "out of memory");
-  t->scan = c;
-  t->feed = f;
-  t->cfg = *cfg;
-  sc_config sc;
-  sc_default_config(&sc, c->cfg.sample_rate, cfg->bandwidth);
-  sc.threshold = cfg->threshold;
-  sc.channels = cfg->channels;
-  sc.max_samples = max_samples;
-  sc.pack_scale = cfg->pack_scale;
-  sc.device_id = c->cfg.device_id;
-  int st = sc_create(&sc, &t->chan);
-  if (st != SS_OK) {
-    srf_fail(nullptr, st, "sc_create: %s", sc_last_error(nullptr));
-    srf_free(t);
-    return st;
-  }
-  st = sc_set_input_format(t->chan, c->cfg.in_format, c->cfg.int_scale);
-  if (st != SS_OK) {
-    srf_fail(nullptr, st, "sc_set_input_format: %s", sc_last_error(t->chan));
-    srf_free(t);
-    return st;
-  }
-  t->cap = sc_output_capacity(t->chan, max_samples);
-  const size_t plane = (size_t)2 * (size_t)t->cap * (size_t)cfg->channels;
-  bool ok = hipSetDevice(c->cfg.device_id) == hipSuccess && hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipMalloc(&t->d_i8, plane) == hipSuccess && hipHostMalloc((void**)&t->h_i8, plane, hipHostMallocDefault) == hipSuccess;
-  if (cfg->want_cf32) ok = ok && hipMalloc(&t->d_cf32, sizeof(float) * plane) == hipSuccess && hipHostMalloc((void**)&t->h_cf32, sizeof(float) * plane, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&t->h_counts, sizeof(int32_t) * SC_MAX_CHANNELS, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&t->h_rc, sizeof(int32_t) * SC_MAX_RANGES, hipHostMallocDefault) == hipSuccess;
-  if (!ok) {
-    const hipError_t e = hipGetLastError();
-    srf_free(t);
-    return srf_fail(nullptr, SS_ERR_NOMEM, "allocating the recorder's buffers failed: %s", hipGetErrorString(e));
-  }
-  f->recorder = t;
-  *out = t;
-  return SS_OK;
-}
-
-void srf_destroy(srf_ctx* t) {
-  if (!t) return;
-  {
-    std::lock_guard<std::mutex> rec(t->rec_mtx);
-    std::lock_guard<std::mutex> lock(t->scan->mtx);
-    if (t->feed) {
-      if (t->feed->held >= 0) srf_let_go(t->feed);  // (without a recorder nothing is held)
-      t->feed->recorder = nullptr;
-    }
-    (void)hipSetDevice(t->scan->cfg.device_id);
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-  }
-  srf_free(t);
-}
-
-const char* srf_last_error(const srf_ctx* t) { return t ? t->err : g_srf_create_err; }
-
-int srf_release(srf_ctx* t) {
-  if (!t) return SS_ERR_INVALID;
-  std::lock_guard<std::mutex> rec(t->rec_mtx);
-  std::lock_guard<std::mutex> lock(t->scan->mtx);
-  if (!t->feed) return srf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
-  if (t->feed->held < 0) return srf_fail(t, SS_ERR_INVALID, "no batch is held: collect one first");
-  srf_let_go(t->feed);
-  return SS_OK;
-}
-
-int srf_record(srf_ctx* t, const sc_range* ranges, int32_t nranges, srf_result* out) {
-  if (!t) return SS_ERR_INVALID;
-  if (!out || nranges < 0 || (nranges > 0 && !ranges)) return srf_fail(t, SS_ERR_INVALID, "null argument");
-  std::lock_guard<std::mutex> rec(t->rec_mtx);
-  const void* d_in = nullptr;
-  const void* h_items = nullptr;  // an items feed: the held slot's pinned items, uploaded as far as the ranges read them
-  int nsamples = 0;
-  {
-    std::lock_guard<std::mutex> lock(t->scan->mtx);
-    ss_feed* f = t->feed;
-    if (!f) return srf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
-    if (f->held < 0) return srf_fail(t, SS_ERR_INVALID, "no batch is held: collect one first");
-    const ss_feed_slot& s = f->slots[(size_t)f->held];
-    d_in = s.d_in;  // the collect has waited for the batch's chain, which waited for the upload
-    if (f->items) h_items = s.h_in;
-    nsamples = s.nframes * t->scan->n * (f->items ? t->scan->cfg.decim : 1);  // (srf_create: fits)
-  }
-  const int nch = t->cfg.channels;
-  out->nsamples = nsamples;
-  out->cap = t->cap;
-  out->counts = t->h_counts;
-  out->range_counts = t->h_rc;
-  out->out_i8 = t->h_i8;
-  out->out_cf32 = t->cfg.want_cf32 ? t->h_cf32 : nullptr;
-  out->h2d_bytes = 0;
-  for (int ch = 0; ch < nch; ++ch) t->h_counts[ch] = 0;
-  if (nranges > 0) {
-    // the held slot is not acquired and not submitted to while it is held, so its d_in and its pinned items stand still without
-    // the context's lock
-    uint64_t uploaded = 0;
-    int st = h_items ? sc_process_ranges_upload(t->chan, h_items, nsamples, ranges, nranges, t->d_i8, t->d_cf32, t->h_counts, t->h_rc, t->cap, &uploaded)
-                     : sc_process_ranges_device(t->chan, d_in, nsamples, ranges, nranges, t->d_i8, t->d_cf32, t->h_counts, t->h_rc, t->cap);
-    if (st != SS_OK) return srf_fail(t, st, "%s", sc_last_error(t->chan));
-    st = sc_sync(t->chan);  // (the uploads have read the pinned items by now: the slot may go)
-    if (st != SS_OK) return srf_fail(t, st, "%s", sc_last_error(t->chan));
-    out->h2d_bytes = uploaded;
-    hipError_t e = hipSetDevice(t->scan->cfg.device_id);
-    for (int ch = 0; ch < nch && e == hipSuccess; ++ch) {
-      const size_t n = (size_t)(t->h_counts[ch] < t->cap ? t->h_counts[ch] : t->cap), at = (size_t)2 * (size_t)t->cap * (size_t)ch;
-      if (n == 0) continue;
-      e = hipMemcpyAsync(t->h_i8 + at, t->d_i8 + at, 2 * n, hipMemcpyDeviceToHost, t->stream);
-      if (e == hipSuccess && t->cfg.want_cf32) e = hipMemcpyAsync(t->h_cf32 + at, t->d_cf32 + at, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, t->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
-    if (e != hipSuccess) return srf_fail(t, SS_ERR_HIP, "copying the recorded samples failed: %s", hipGetErrorString(e));
-  }
-  std::lock_guard<std::mutex> lock(t->scan->mtx);
-  if (t->feed && t->feed->held >= 0) srf_let_go(t->feed);
-  return SS_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The spectrogram rows of the feed (include/specscan_spectrogram_feed.h): the reference's per-frame send gate on the host
-// (spectrogram_gate.h) and its arithmetic, in its order, in one kernel behind every batch (spectrogram_rows.h). Everything here is
-// the scan context's, under its mutex. The kernel is on the context's stream behind flush_stages, like the tracked feed's digest
-// (see there for why the next batch's chain cannot overtake it): it reads c->last_psd before the next batch rotates the planes.
-struct sgf_container {  // Spectrogram::Container (spectrogram.h:10-16), one per centre frequency: the sum on the device, the rest here
-  int32_t center = 0;
-  float* d_sum = nullptr;
-  int64_t last_send = 0;
-  int32_t have_last = 0;  // the container's first frame stamps last_send
-  int32_t count = 0;      // m_counter
-};
-
-struct sgf_slot {
-  int8_t* d_rows = nullptr;
-  float* d_mean = nullptr;
-  int8_t* h_rows = nullptr;  // pinned
-  float* h_mean = nullptr;
-  int64_t* h_time = nullptr;
-  int32_t *h_frame = nullptr, *h_count = nullptr;
-  int32_t nrows = 0, frequency = 0, open_count = 0;
-};
-
-struct sgf_ctx {
-  ss_ctx* scan = nullptr;
-  ss_feed* feed = nullptr;  // null once the feed has been destroyed: only sgf_destroy / sgf_last_error from then on
-  sgf_config cfg{};
-  int size = 0, log2_m = 0;
-  std::vector<sgf_container> containers;
-  std::vector<sgf_slot> slots;
-  char err[512] = "";
-};
-
-namespace {
-
-thread_local char g_sgf_create_err[512] = "";
-
-template <class... A>
-int sgf_fail(sgf_ctx* t, int status, const char* fmt, A... a) {
-  return fail_to(t ? t->err : g_sgf_create_err, status, fmt, a...);
-}
-
-void sgf_free(sgf_ctx* t) {
-  if (!t) return;
-  for (auto& g : t->containers) (void)hipFree(g.d_sum);
-  for (auto& s : t->slots) {
-    (void)hipFree(s.d_rows);
-    (void)hipFree(s.d_mean);
-    for (void* p : {(void*)s.h_rows, (void*)s.h_mean, (void*)s.h_time, (void*)s.h_frame, (void*)s.h_count})
-      if (p) (void)hipHostFree(p);
-  }
-  delete t;
-}
-
-void sgf_feed_gone(sgf_ctx* t) { t->feed = nullptr; }
-
-sgf_container* sgf_container_for(sgf_ctx* t, int32_t center) {
-  for (auto& g : t->containers)
-    if (g.center == center) return &g;
-  return nullptr;
-}
-
-// ss_feed_submit, under the context's lock, in front of the upload: the gate of the centre in force over the batch's clock, on
-// copies. A refusal leaves every state as it was.
-int sgf_plan_batch(ss_feed* f, int nframes, const int64_t* t_ms, sgf_plan* plan) {
-  sgf_ctx* t = f->spectrogram;
-  ss_ctx* c = f->c;
-  if (!t_ms) return fail(c, SS_ERR_INVALID, "ss_feed_submit without t_ms: the feed's spectrogram rows close on the frames' clock");
-  plan->center = (c->range_lo + c->range_hi) / 2;
-  if (const sgf_container* g = sgf_container_for(t, plan->center)) {
-    plan->last_send = g->last_send;
-    plan->have_last = g->have_last;
-  }
-  const int rows = ss::spectrogram_gate_plan(&plan->last_send, &plan->have_last, t_ms, nframes, plan->cut, t->cfg.max_rows);
-  if (rows > t->cfg.max_rows) return fail(c, SS_ERR_INVALID, "the batch's clock closes %d spectrogram rows, max_rows is %d: submit fewer frames at a time", rows, t->cfg.max_rows);
-  plan->ncuts = rows;
-  for (int k = 0; k < rows; ++k) plan->time[k] = t_ms[plan->cut[k]];
-  return SS_OK;
-}
-
-// ss_feed_submit, behind flush_stages and the result copies, in front of ev_done: the batch's rows, and the plan taken over.
-int sgf_enqueue(ss_feed* f, int slot_no, int nframes, const sgf_plan& plan) {
-  sgf_ctx* t = f->spectrogram;
-  ss_ctx* c = f->c;
-  sgf_slot& s = t->slots[(size_t)slot_no];
-  if (!c->last_psd || ((uintptr_t)c->last_psd & 15u)) return fail(c, SS_ERR_INVALID, "spectrogram rows: the batch left no (16-byte aligned) dB plane");
-  sgf_container* g = sgf_container_for(t, plan.center);
-  if (!g) {  // first use of a centre: a zeroed sum row (Container's constructor)
-    sgf_container fresh;
-    fresh.center = plan.center;
-    SS_HIP(c, hipMalloc(&fresh.d_sum, sizeof(float) * (size_t)t->size));
-    const hipError_t e = hipMemsetAsync(fresh.d_sum, 0, sizeof(float) * (size_t)t->size, c->stream);
-    if (e != hipSuccess) {
-      (void)hipFree(fresh.d_sum);
-      return fail(c, SS_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
-    }
-    t->containers.push_back(fresh);
-    g = &t->containers.back();
-  }
-  ss::SpecRowsArgs a{};
-  a.psd = c->last_psd;
-  a.sum = g->d_sum;
-  a.rows = s.d_rows;
-  a.mean = t->cfg.want_mean ? s.d_mean : nullptr;
-  a.n = c->n;
-  a.nframes = nframes;
-  a.size = t->size;
-  a.log2_m = t->log2_m;
-  a.count0 = g->count;
-  a.ncuts = plan.ncuts;
-  for (int k = 0; k < plan.ncuts; ++k) a.cut[k] = plan.cut[k];
-  const dim3 grid((unsigned)(c->n >> std::max(t->log2_m, 6)));
-  if (t->log2_m <= 2) hipLaunchKernelGGL(ss::k_spec_rows<false>, grid, dim3(256), 0, c->stream, a);
-  else hipLaunchKernelGGL(ss::k_spec_rows<true>, grid, dim3(256), 0, c->stream, a);
-  SS_HIP(c, hipGetLastError());
-  if (plan.ncuts > 0) {
-    const size_t cells = (size_t)plan.ncuts * (size_t)t->size;
-    SS_HIP(c, hipMemcpyAsync(s.h_rows, s.d_rows, cells, hipMemcpyDeviceToHost, c->stream));
-    if (t->cfg.want_mean) SS_HIP(c, hipMemcpyAsync(s.h_mean, s.d_mean, sizeof(float) * cells, hipMemcpyDeviceToHost, c->stream));
-  }
-  int32_t count = g->count, prev = -1;
-  for (int k = 0; k < plan.ncuts; ++k) {  // m_counter at each send: the closing frame is part of its row
-    s.h_time[k] = plan.time[k];
-    s.h_frame[k] = plan.cut[k];
-    s.h_count[k] = count + (plan.cut[k] - prev);
-    count = 0;
-    prev = plan.cut[k];
-  }
-  g->count = count + (nframes - 1 - prev);
-  g->last_send = plan.last_send;
-  g->have_last = plan.have_last;
-  s.nrows = plan.ncuts;
-  s.frequency = plan.center;
-  s.open_count = g->count;
-  return SS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t sgf_gate_plan(int64_t* last_send, int32_t* have_last, const int64_t* t_ms, int32_t nframes, int32_t* cut_frame, int32_t cap) {
-  if (!last_send || !have_last || nframes < 0 || (nframes > 0 && !t_ms) || cap < 0 || (cap > 0 && !cut_frame)) return SS_ERR_INVALID;
-  return ss::spectrogram_gate_plan(last_send, have_last, t_ms, nframes, cut_frame, cap);
-}
-
-int sgf_create(ss_feed* f, const sgf_config* cfg, sgf_ctx** out) {
-  if (!f || !cfg || !out) return sgf_fail(nullptr, SS_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (cfg->abi_version != SGF_ABI_VERSION) return sgf_fail(nullptr, SS_ERR_INVALID, "abi_version %u, library has %u", cfg->abi_version, SGF_ABI_VERSION);
-  if (cfg->max_rows < 1 || cfg->max_rows > SGF_MAX_ROWS) return sgf_fail(nullptr, SS_ERR_INVALID, "max_rows %d outside 1..%d", cfg->max_rows, SGF_MAX_ROWS);
-  ss_ctx* c = f->c;
-  std::lock_guard<std::mutex> lock(c->mtx);
-  if (c->spec_n <= 0) return sgf_fail(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_SPECTROGRAM (it fixes the row size and keeps every batch's dB plane)");
-  if (f->spectrogram) return sgf_fail(nullptr, SS_ERR_INVALID, "the feed already has a spectrogram object");
-  if (f->pending > 0 || f->acquired >= 0) return sgf_fail(nullptr, SS_ERR_INVALID, "the feed has batches pending: collect them first");
-  int log2_m = 0;
-  while (log2_m < 30 && ((long long)c->spec_n << log2_m) < c->n) ++log2_m;
-  if (((long long)c->spec_n << log2_m) != c->n || c->spec_m != (1 << log2_m) || c->n % 64 != 0)
-    return sgf_fail(nullptr, SS_ERR_INVALID, "%d points into %d spectrogram bins: the rows need a power-of-two ratio and a multiple of 64 points", c->n, c->spec_n);
-  sgf_ctx* t = new (std::nothrow) sgf_ctx();
-  if (!t) return sgf_fail(nullptr, SS_ERR_NOMEM, "out of memory");
-  t->scan = c;
-  t->feed = f;
-  t->cfg = *cfg;
-  t->size = c->spec_n;
-  t->log2_m = log2_m;
-  t->slots.resize((size_t)f->depth);
-  const size_t cells = (size_t)cfg->max_rows * (size_t)t->size, rows = (size_t)cfg->max_rows;
-  bool ok = hipSetDevice(c->cfg.device_id) == hipSuccess;
-  for (auto& s : t->slots) {
-    ok = ok && hipMalloc(&s.d_rows, cells) == hipSuccess && hipHostMalloc((void**)&s.h_rows, cells, hipHostMallocDefault) == hipSuccess;
-    if (cfg->want_mean) ok = ok && hipMalloc(&s.d_mean, sizeof(float) * cells) == hipSuccess && hipHostMalloc((void**)&s.h_mean, sizeof(float) * cells, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&s.h_time, sizeof(int64_t) * rows, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&s.h_frame, sizeof(int32_t) * rows, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&s.h_count, sizeof(int32_t) * rows, hipHostMallocDefault) == hipSuccess;
-  }
-  if (!ok) {
-    const hipError_t e = hipGetLastError();
-    sgf_free(t);
-    return sgf_fail(nullptr, SS_ERR_NOMEM, "allocating the spectrogram rows' buffers failed: %s", hipGetErrorString(e));
-  }
-  f->spectrogram = t;
-  f->last_collected = -1;
-  *out = t;
-  return SS_OK;
-}
-
-void sgf_destroy(sgf_ctx* t) {
-  if (!t) return;
-  {
-    std::lock_guard<std::mutex> lock(t->scan->mtx);
-    (void)hipSetDevice(t->scan->cfg.device_id);
-    if (t->feed) {  // (a destroyed feed has waited for its streams already)
-      (void)hipStreamSynchronize(t->scan->stream);
-      t->feed->spectrogram = nullptr;
-    }
-  }
-  sgf_free(t);
-}
-
-const char* sgf_last_error(const sgf_ctx* t) { return t ? t->err : g_sgf_create_err; }
-
-int sgf_rows(sgf_ctx* t, sgf_result* out) {
-  if (!t) return SS_ERR_INVALID;
-  if (!out) return sgf_fail(t, SS_ERR_INVALID, "null argument");
-  std::lock_guard<std::mutex> lock(t->scan->mtx);
-  const ss_feed* f = t->feed;
-  if (!f) return sgf_fail(t, SS_ERR_INVALID, "the feed has been destroyed");
-  if (f->last_collected < 0) return sgf_fail(t, SS_ERR_INVALID, "no batch has been collected since sgf_create");
-  const sgf_slot& s = t->slots[(size_t)f->last_collected];
-  out->nrows = s.nrows;
-  out->size = t->size;
-  out->frequency = s.frequency;
-  out->sample_rate = t->scan->cfg.sample_rate;
-  out->open_count = s.open_count;
-  out->time_ms = s.h_time;
-  out->frame = s.h_frame;
-  out->count = s.h_count;
-  out->rows = s.h_rows;
-  out->mean = t->cfg.want_mean ? s.h_mean : nullptr;
-  return SS_OK;
-}
-
-}  // extern "C"
+// The APIs built on the scan engine: host code only, in this order (see the top of the file).
+#include "device_buffers.h"
+#include "feed_ring.h"
+#include "host_feed.h"
+#include "host_track.h"
+#include "host_track_feed.h"
+#include "host_record_feed.h"
+#include "host_spectrogram_feed.h"

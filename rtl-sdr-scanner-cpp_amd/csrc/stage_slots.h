@@ -1,6 +1,7 @@
 // stage_slots.h — the stages of earlier calls that wait on the host until a later launch carries them: the bookkeeping of specscan.hip's
 // in-order step pipeline as fixed slots named for what each stage waits for (no HIP in here, payloads are template parameters:
-// tests/host/stage_slots_check.cpp runs it on the CPU against the schedules below).
+// tests/host/stage_slots_check.cpp runs it on the CPU against the schedules below). The slots of the pipelined feed are another
+// matter: feed_ring.h, under host_feed.h.
 //
 // A call's stages run in the order rows -> plan -> detect -> emit, each on a later launch than the one before; the launches of the
 // calls that follow carry them (scan_step.h), or flush_stages drains them. Buffers a waiting stage reads while a later call already

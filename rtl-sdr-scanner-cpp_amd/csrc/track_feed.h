@@ -1,6 +1,6 @@
 // track_feed.h — the tracking digest behind the pipelined feed (include/specscan_track_feed.h): the steps of st_digest that ran on the
 // host — clipping the offsets, forming the watch list — as kernels, so that a batch is digested in the stream right behind its chain,
-// with no host wait in between. The candidates' kernel (k_best_blocked of track_digest_blocked.h; launch_cand_best in specscan.hip)
+// with no host wait in between. The candidates' kernel (k_best_blocked of track_digest_blocked.h; launch_cand_best in host_track.h)
 // and k_save_tail of track_digest.h run unchanged between them.
 //
 //   k_feed_prepare   coff[f] = min(off[f], cand_cap); keymark[key] = seq for the posted keys; the header's flags to zero

@@ -10,7 +10,7 @@
 //                       themselves and run detect_tile<21, 21, 16, 256, false>
 //
 // Same body, same inputs: every value is the one a context with SS_FLAG_KEEP_PLANES writes, bit for bit. What the replay must NOT do
-// is the host's business (specscan.hip, stf_enqueue): mask bits and counts go to scratch of the tracker's own, no ring row, rel row,
+// is the host's business (host_track_feed.h, stf_replay_watch_tiles): mask bits and counts go to scratch of the tracker's own, no ring row, rel row,
 // statistic or spectrogram sum is written.
 #pragma once
 #include <cstdint>
