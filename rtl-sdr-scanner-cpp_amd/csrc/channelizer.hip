@@ -33,6 +33,7 @@
 #include "../../include/specscan.h"
 #include "../../include/specscan_channelizer.h"
 #include "chan_ranges.h"
+#include "device_buffers.h"
 
 namespace {
 
@@ -148,9 +149,9 @@ std::vector<float> design_resampler_taps(int interp, int decim) {
 struct Stage {
   int interp = 1, decim = 1, ntaps = 0, nt = 0;  // nt = taps per polyphase arm = block history
   std::vector<float> taps;
-  float* d_arm_dec = nullptr;  // fast first stage: h[D t + b] at [t][b], b padded to 64 per pass, zeros beyond D and ntaps
-  float* d_arm = nullptr;  // [interp][nt]: arm[i][j] = taps[i + j * interp], zero padded (rational_resampler_impl::install_taps)
-  float2* d_buf = nullptr;  // stages > 0: per slot [hist (nt-1) | new samples], stride buf_stride
+  ss::device_buffer<float> d_arm_dec;  // fast first stage: h[D t + b] at [t][b], b padded to 64 per pass, zeros beyond D and ntaps
+  ss::device_buffer<float> d_arm;  // [interp][nt]: arm[i][j] = taps[i + j * interp], zero padded (rational_resampler_impl::install_taps)
+  ss::device_buffer<float2> d_buf;  // stages > 0: per slot [hist (nt-1) | new samples], stride buf_stride
   long long buf_stride = 0;
   int max_in = 0, max_out = 0;
   int tile = 64;        // outputs per workgroup
@@ -173,23 +174,23 @@ struct Slot {
 
 }  // namespace
 
-struct sc_ctx {
+struct SS_HIDDEN sc_ctx {
   sc_config cfg{};
   std::mutex mtx;
   char err[512] = "";
   int32_t in_format = SS_FMT_CF32;  // sc_set_input_format
   float in_scale = 1.0f;            // resolved int_scale (unused by CF32)
-  hipStream_t stream = nullptr;
+  ss::hip_stream stream;
   std::vector<Stage> stages;
   Slot slots[SC_MAX_CHANNELS];
-  float2* d_hist0 = nullptr;  // first stage: per slot the newest nt-1 ROTATED samples
+  ss::device_buffer<float2> d_hist0;  // first stage: per slot the newest nt-1 ROTATED samples
   long long hist0_stride = 0;
-  float2* d_ptab = nullptr;  // k_chan_dec: per slot exp(2*pi*i*k*df), rebuilt by sc_start
+  ss::device_buffer<float2> d_ptab;  // k_chan_dec: per slot exp(2*pi*i*k*df), rebuilt by sc_start
   long long ptab_stride = 0;
   // host-entry staging
-  float2* d_in = nullptr;
-  int8_t* d_out_i8 = nullptr;
-  float* d_out_cf32 = nullptr;
+  ss::device_buffer<float2> d_in;
+  ss::device_buffer<int8_t> d_out_i8;
+  ss::device_buffer<float> d_out_cf32;
   int out_cap_alloc = 0;
 };
 
@@ -587,22 +588,6 @@ __global__ __launch_bounds__(256) void k_chan_keep(ChanArgs a) {
 
 using chan_ranges::stage_outputs;  // outputs of one resampler for n_in new samples given its (ctr, skip), and the state after them
 
-void free_sc(sc_ctx* c) {
-  if (!c) return;
-  for (auto& st : c->stages) {
-    (void)hipFree(st.d_arm);
-    (void)hipFree(st.d_arm_dec);
-    (void)hipFree(st.d_buf);
-  }
-  (void)hipFree(c->d_hist0);
-  (void)hipFree(c->d_ptab);
-  (void)hipFree(c->d_in);
-  (void)hipFree(c->d_out_i8);
-  (void)hipFree(c->d_out_cf32);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-}
-
 // The first stage (the only one that reads the raw stream) and its history update, for one input format.
 template <int FMT>
 void launch_first_stage(const sc_ctx* c, const Stage& st, const ChanArgs& a, int max_out) {
@@ -796,15 +781,12 @@ int run_ranges(sc_ctx* c, const void* d_iq, int nsamples, const sc_range* ranges
 
 // the host entry points' staging buffers: the stream, and planes of cap outputs per channel
 int host_staging(sc_ctx* c, int cap) {
-  if (!c->d_in) SC_HIP(c, hipMalloc(&c->d_in, sizeof(float2) * (size_t)c->cfg.max_samples));  // CF32-sized: a format switch never reallocates
+  if (!c->d_in) SC_HIP(c, c->d_in.alloc((size_t)c->cfg.max_samples));  // CF32-sized: a format switch never reallocates
   if (cap > c->out_cap_alloc) {
-    (void)hipFree(c->d_out_i8);
-    (void)hipFree(c->d_out_cf32);
-    c->d_out_i8 = nullptr;
-    c->d_out_cf32 = nullptr;
+    ss::reset_all(c->d_out_i8, c->d_out_cf32);
     c->out_cap_alloc = 0;
-    SC_HIP(c, hipMalloc(&c->d_out_i8, (size_t)2 * (size_t)cap * (size_t)c->cfg.channels));
-    SC_HIP(c, hipMalloc(&c->d_out_cf32, sizeof(float2) * (size_t)cap * (size_t)c->cfg.channels));
+    SC_HIP(c, c->d_out_i8.alloc((size_t)2 * (size_t)cap * (size_t)c->cfg.channels));
+    SC_HIP(c, c->d_out_cf32.alloc((size_t)2 * (size_t)cap * (size_t)c->cfg.channels));
     c->out_cap_alloc = cap;
   }
   return SS_OK;
@@ -855,17 +837,8 @@ int sc_create(const sc_config* cfg, sc_ctx** out) {
   if (factors.size() > SC_MAX_STAGES) return sc_fail(nullptr, SS_ERR_INVALID, "%zu resampler stages > %d", factors.size(), SC_MAX_STAGES);
   sc_ctx* c = new sc_ctx;
   c->cfg = *cfg;
-#define SC_CREATE_HIP(call)                                                           \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      sc_fail(nullptr, SS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));    \
-      free_sc(c);                                                                     \
-      return SS_ERR_HIP;                                                              \
-    }                                                                                 \
-  } while (0)
-  SC_CREATE_HIP(hipSetDevice(cfg->device_id));
-  SC_CREATE_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  ss::hip_steps made;
+  made.then([&] { return hipSetDevice(cfg->device_id); }, "hipSetDevice").stream(c->stream);
   long long max_in = cfg->max_samples;
   for (const auto& f : factors) {
     Stage st;
@@ -919,45 +892,41 @@ int sc_create(const sc_config* cfg, sc_ctx** out) {
     }
     if ((long long)st.lds_floats2 * (long long)sizeof(float2) > 64 * 1024 || (long long)(st.nt - 1) * (long long)sizeof(float2) > 64 * 1024) {
       sc_fail(nullptr, SS_ERR_INVALID, "resampler %d/%d needs %d taps per arm: does not fit the LDS tile", st.interp, st.decim, st.nt);
-      free_sc(c);
+      delete c;
       return SS_ERR_INVALID;
     }
     std::vector<float> arm((size_t)st.interp * (size_t)st.nt, 0.0f);
     for (int k = 0; k < st.ntaps; ++k) arm[(size_t)(k % st.interp) * st.nt + k / st.interp] = st.taps[(size_t)k];
-    SC_CREATE_HIP(hipMalloc(&st.d_arm, sizeof(float) * arm.size()));
-    SC_CREATE_HIP(hipMemcpy(st.d_arm, arm.data(), sizeof(float) * arm.size(), hipMemcpyHostToDevice));
+    made.upload(st.d_arm, arm);
     if (st.fast) {
       const int pitch = 64 * st.passes;
       std::vector<float> dec((size_t)kDecA * (size_t)pitch, 0.0f);
       for (int t = 0; t < kDecA; ++t)
         for (int b = 0; b < st.decim; ++b)
           if (st.decim * t + b < st.ntaps) dec[(size_t)t * pitch + b] = st.taps[(size_t)(st.decim * t + b)];
-      SC_CREATE_HIP(hipMalloc(&st.d_arm_dec, sizeof(float) * dec.size()));
-      SC_CREATE_HIP(hipMemcpy(st.d_arm_dec, dec.data(), sizeof(float) * dec.size(), hipMemcpyHostToDevice));
+      made.upload(st.d_arm_dec, dec);
     }
     if (!c->stages.empty()) {
       st.buf_stride = (long long)(st.nt - 1) + st.max_in;
-      SC_CREATE_HIP(hipMalloc(&st.d_buf, sizeof(float2) * (size_t)st.buf_stride * (size_t)cfg->channels));
-      SC_CREATE_HIP(hipMemsetAsync(st.d_buf, 0, sizeof(float2) * (size_t)st.buf_stride * (size_t)cfg->channels, c->stream));  // zero history
+      made.alloc(st.d_buf, (size_t)st.buf_stride * (size_t)cfg->channels).zero_async(st.d_buf, (size_t)st.buf_stride * (size_t)cfg->channels, c->stream);  // zero history
     }
     max_in = st.max_out;
-    c->stages.push_back(st);
+    c->stages.push_back(std::move(st));
   }
   c->hist0_stride = c->stages[0].nt > 1 ? c->stages[0].nt - 1 : 1;
-  SC_CREATE_HIP(hipMalloc(&c->d_hist0, sizeof(float2) * (size_t)c->hist0_stride * (size_t)cfg->channels));
-  SC_CREATE_HIP(hipMemsetAsync(c->d_hist0, 0, sizeof(float2) * (size_t)c->hist0_stride * (size_t)cfg->channels, c->stream));
-  if (c->ptab_stride > 0) {
-    SC_CREATE_HIP(hipMalloc(&c->d_ptab, sizeof(float2) * (size_t)c->ptab_stride * (size_t)cfg->channels));
-    SC_CREATE_HIP(hipMemsetAsync(c->d_ptab, 0, sizeof(float2) * (size_t)c->ptab_stride * (size_t)cfg->channels, c->stream));
-  }
+  made.alloc(c->d_hist0, (size_t)c->hist0_stride * (size_t)cfg->channels).zero_async(c->d_hist0, (size_t)c->hist0_stride * (size_t)cfg->channels, c->stream);
+  if (c->ptab_stride > 0) made.alloc(c->d_ptab, (size_t)c->ptab_stride * (size_t)cfg->channels).zero_async(c->d_ptab, (size_t)c->ptab_stride * (size_t)cfg->channels, c->stream);
   for (const void* f : {reinterpret_cast<const void*>(k_chan_stage<true, SS_FMT_CF32>), reinterpret_cast<const void*>(k_chan_stage<true, SS_FMT_CS8>),
                         reinterpret_cast<const void*>(k_chan_stage<true, SS_FMT_CU8>), reinterpret_cast<const void*>(k_chan_stage<true, SS_FMT_CS16>),
                         reinterpret_cast<const void*>(k_chan_stage<false, SS_FMT_CF32>), reinterpret_cast<const void*>(k_chan_keep<true, SS_FMT_CF32>),
                         reinterpret_cast<const void*>(k_chan_keep<true, SS_FMT_CS8>), reinterpret_cast<const void*>(k_chan_keep<true, SS_FMT_CU8>),
                         reinterpret_cast<const void*>(k_chan_keep<true, SS_FMT_CS16>), reinterpret_cast<const void*>(k_chan_keep<false, SS_FMT_CF32>)})
-    SC_CREATE_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-  SC_CREATE_HIP(hipStreamSynchronize(c->stream));
-#undef SC_CREATE_HIP
+    made.then([&] { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); }, "hipFuncSetAttribute");
+  made.then([&] { return hipStreamSynchronize(c->stream); }, "hipStreamSynchronize");
+  if (!made.ok()) {
+    delete c;
+    return sc_fail(nullptr, SS_ERR_HIP, "%s failed: %s", made.what(), hipGetErrorString(made.error()));
+  }
   *out = c;
   return SS_OK;
 }
@@ -966,7 +935,7 @@ void sc_destroy(sc_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->cfg.device_id);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  free_sc(c);
+  delete c;
 }
 
 int sc_stage_count(const sc_ctx* c) { return c ? (int)c->stages.size() : 0; }
@@ -1101,7 +1070,7 @@ int sc_process_ranges_upload(sc_ctx* c, const void* iq, int32_t nsamples, const 
   for (int ch = 0; ch < c->cfg.channels; ++ch)
     if (c->slots[ch].active) return sc_fail(c, SS_ERR_INVALID, "channel %d is recording (sc_start): ranges and start/stop are not mixed", ch);
   SC_HIP(c, hipSetDevice(c->cfg.device_id));
-  if (!c->d_in) SC_HIP(c, hipMalloc(&c->d_in, sizeof(float2) * (size_t)c->cfg.max_samples));  // as host_staging
+  if (!c->d_in) SC_HIP(c, c->d_in.alloc((size_t)c->cfg.max_samples));  // as host_staging
   // Interval [b, e) of the stream goes to d_in + b: the ranges address d_in as they address the stream. What lies between the
   // intervals is whatever an earlier call left there; no range reads it (every raw load is clamped into its range).
   chan_ranges::Interval iv[SC_MAX_RANGES];
@@ -1110,7 +1079,7 @@ int sc_process_ranges_upload(sc_ctx* c, const void* iq, int32_t nsamples, const 
   uint64_t bytes = 0;
   for (int i = 0; i < niv; ++i) {
     const size_t at = bps * (size_t)iv[i].begin, len = bps * (size_t)(iv[i].end - iv[i].begin);
-    SC_HIP(c, hipMemcpyAsync(reinterpret_cast<char*>(c->d_in) + at, static_cast<const char*>(iq) + at, len, hipMemcpyHostToDevice, c->stream));
+    SC_HIP(c, hipMemcpyAsync(reinterpret_cast<char*>(c->d_in.get()) + at, static_cast<const char*>(iq) + at, len, hipMemcpyHostToDevice, c->stream));
     bytes += len;
   }
   if (uploaded_bytes) *uploaded_bytes = bytes;

@@ -41,7 +41,7 @@ struct ss_feed_slot {
   ss::pinned_buffer<float> h_avg, h_psd;
   ss::device_buffer<int32_t> d_off, d_idx;
   ss::device_buffer<float> d_avg;
-  hipEvent_t ev_h2d = nullptr, ev_done = nullptr;
+  ss::hip_event ev_h2d, ev_done;
   int nframes = 0;
   int64_t tag = 0;
 };
@@ -54,20 +54,12 @@ struct SS_HIDDEN ss_feed {
   bool items = false;  // ss_feed_create_items on a decimated context: h_in holds whole items of n * decim samples, d_in their first n
   ss::feed_ring ring;
   std::vector<ss_feed_slot> slots;
-  hipStream_t copy_stream = nullptr, d2h_stream = nullptr;
+  ss::hip_stream copy_stream, d2h_stream;
   feed_rider* tracker = nullptr;      // stf_create: every batch is digested behind its chain (include/specscan_track_feed.h)
   feed_rider* recorder = nullptr;     // srf_create: a collected slot stays held until its samples are recorded or let go (include/specscan_record_feed.h)
   feed_rider* spectrogram = nullptr;  // sgf_create: every batch leaves the spectrogram rows it closes (include/specscan_spectrogram_feed.h); sgf_rows reads ring.last_collected()
 
   explicit ss_feed(int depth) : ring(depth), slots((size_t)depth) {}
-  ~ss_feed() {
-    for (auto& s : slots) {
-      if (s.ev_h2d) (void)hipEventDestroy(s.ev_h2d);
-      if (s.ev_done) (void)hipEventDestroy(s.ev_done);
-    }
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    if (d2h_stream) (void)hipStreamDestroy(d2h_stream);
-  }
 };
 
 namespace {
@@ -118,14 +110,12 @@ int feed_create(ss_ctx* c, int32_t depth, int32_t cand_cap, int32_t want_psd, bo
   const size_t host_bytes = f->items ? in_bytes * (size_t)c->cfg.decim : in_bytes;
   const size_t ncand = (size_t)(cand_cap > 0 ? cand_cap : 1);
   ss::hip_steps made;
-  made.then([&] { return hipStreamCreateWithFlags(&f->copy_stream, hipStreamNonBlocking); }, "hipStreamCreateWithFlags");
-  made.then([&] { return hipStreamCreateWithFlags(&f->d2h_stream, hipStreamNonBlocking); }, "hipStreamCreateWithFlags");
+  made.stream(f->copy_stream).stream(f->d2h_stream);
   for (auto& s : f->slots) {
     made.alloc(s.h_in, host_bytes).alloc(s.d_in, in_bytes).alloc(s.h_off, frames + 1).alloc(s.h_idx, ncand).alloc(s.h_avg, ncand);
     if (f->want_psd) made.alloc(s.h_psd, (size_t)c->n * frames);
     made.alloc(s.d_off, frames + 1).alloc(s.d_idx, ncand).alloc(s.d_avg, ncand);
-    made.then([&] { return hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming); }, "hipEventCreateWithFlags");
-    made.then([&] { return hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming); }, "hipEventCreateWithFlags");
+    made.event(s.ev_h2d).event(s.ev_done);
   }
   if (!made.ok()) {
     delete f;

@@ -9,7 +9,7 @@ struct SS_HIDDEN srf_ctx : feed_rider {
   srf_config cfg{};
   std::mutex rec_mtx;
   sc_ctx* chan = nullptr;
-  hipStream_t stream = nullptr;  // the copies of the outputs, behind sc_sync
+  ss::hip_stream stream;  // the copies of the outputs, behind sc_sync
   int cap = 0;
   ss::device_buffer<int8_t> d_i8;
   ss::device_buffer<float> d_cf32;
@@ -19,7 +19,6 @@ struct SS_HIDDEN srf_ctx : feed_rider {
 
   ~srf_ctx() {
     if (chan) sc_destroy(chan);
-    if (stream) (void)hipStreamDestroy(stream);
   }
 };
 
@@ -62,7 +61,7 @@ int srf_create(ss_feed* f, const srf_config* cfg, srf_ctx** out) {
   t->cap = sc_output_capacity(t->chan, max_samples);
   const size_t plane = (size_t)2 * (size_t)t->cap * (size_t)cfg->channels;
   ss::hip_steps made;
-  made.then([&] { return hipSetDevice(c->cfg.device_id); }).then([&] { return hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking); });
+  made.then([&] { return hipSetDevice(c->cfg.device_id); }).stream(t->stream);
   made.alloc(t->d_i8, plane).alloc(t->h_i8, plane);
   if (cfg->want_cf32) made.alloc(t->d_cf32, plane).alloc(t->h_cf32, plane);
   made.alloc(t->h_counts, SC_MAX_CHANNELS).alloc(t->h_rc, SC_MAX_RANGES);

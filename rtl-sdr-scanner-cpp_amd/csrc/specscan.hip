@@ -12,7 +12,8 @@
 //   host_track_feed.h        the tracked feed and its sparse form, stf_*
 //   host_record_feed.h       the feed's recorder, srf_*
 //   host_spectrogram_feed.h  the feed's spectrogram rows, sgf_*
-// Their buffers are owned by type (device_buffers.h).
+// Every device buffer, stream and event is owned by type (device_buffers.h): an object of the C APIs frees by `delete`. Which form of
+// the pipeline a configuration gets is decided in scan_form.h, and the context's sized buffers are allocated in ctx_buffers.h.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -38,13 +39,16 @@
 #include "../../include/specscan_record_feed.h"
 #include "../../include/specscan_spectrogram_feed.h"
 #include "chan_ranges.h"
+#include "ctx_buffers.h"
 #include "detect_fused.h"
 #include "detect_kernels.h"
+#include "device_buffers.h"
 #include "fft1024_kernels.h"
 #include "fft256_kernels.h"
 #include "reference_nan.h"
 #include "fft_kernels.h"
 #include "ring_place.h"
+#include "scan_form.h"
 #include "scan_step.h"
 #include "spectrogram_gate.h"
 #include "spectrogram_rows.h"
@@ -58,29 +62,22 @@ namespace {
 
 thread_local char g_create_err[512] = "";
 
-// fused back end (grouping 21 x 21): frames per tile, and the ring rows kept between batches
-constexpr int kFusedTF = 16;
 static_assert(kFusedTF == ss::kWatchTF && ss::kWatchCol == ss::kFeedBlock, "k_watch_tiles (track_sparse.h) runs the tile this back end runs");
-// Deep pipelining (ss_ctx::deep): a call's last stage runs four launches after its first; the two queues synchronise once in
-// kDeepSyncPeriod launches on the launch three back (a wait costs ~10 us of queue time: rarely, and not within the first 32
-// launches of a run): everything launched more than 4 + kDeepSyncPeriod + 3 launches ago has finished.
-constexpr int kDeepSpecSlots = 64;  // calls whose spectrogram partial sums may wait to be added to their container
-constexpr int kDeepFoldBatch = 8;   // ... added in batches of this many calls
-constexpr int kDeepSyncPeriod = 64;
-constexpr int kDeepSyncPhase = 32;
-constexpr int kMaxQueues = 4;  // launch queues of the deep pipelining (ss_ctx::nq)
-constexpr int kDeepHorizon = 2 * kMaxQueues + kDeepSyncPeriod + 2 * kMaxQueues + 1;
-constexpr int kHistRows = ss::DetectTile<21, 21, kFusedTF, 256>::H;  // 35
+// what scan_form.h and ctx_buffers.h, which include no kernel header, say of the kernels' constants
+static_assert(kHistRows == ss::DetectTile<21, 21, kFusedTF, 256>::H && kFormLiveLists == ss::kLiveLists && kFormLiveCap == ss::kLiveCap && kFormLiveInts == ss::kLiveInts &&
+                  kFormStatWords == ss::kStatShards * ss::kStatShardStride && kFormHaloSegPitch == ss::kHaloSegPitch && kFormNanStateInts * sizeof(int) == sizeof(ss::NanState),
+              "scan_form.h");
+static_assert(ss::kLiveHeader + ss::kLiveLists * ss::kLiveCap <= ss::kLiveCounts, "the lists end before the count copies");
 
 struct SpecState {  // Spectrogram::Container, sources/radio/blocks/spectrogram.h:10-16, one per centre frequency
   int32_t center = 0;
-  float* d_sum = nullptr;
+  ss::device_buffer<float> d_sum;
   int count = 0;
 };
 
 struct NoiseState {  // NoiseLearner::Noise, sources/radio/blocks/noise_learner.h:11-20, one per centre frequency
   int32_t center = 0;
-  float* d_thr = nullptr;
+  ss::device_buffer<float> d_thr;
   int samples = 0;
   bool ready = false;
   int64_t start_ms = 0;
@@ -98,177 +95,37 @@ struct NanStage {
 
 }  // namespace
 
-struct ss_ctx {
+// The form (ScanForm, scan_form.h: n, fused, step_path, deep, nq, the rotating sets' counts, det_lag2, merge, dif8, cull, cull_long, ...) and
+// the buffers, streams and events sized from it (CtxBuffers, ctx_buffers.h) are its bases: c->deep, c->d_hist read as members.
+struct SS_HIDDEN ss_ctx : ScanForm, CtxBuffers {
+  ~ss_ctx();
   ss_config cfg{};
-  int n = 0, logn = 0;
   float db_off = 0.0f;  // 10*log10(fs), the constant term of PSD::work (psd.cpp:19)
   int32_t range_lo = 0, range_hi = 0;
   std::vector<int32_t> ignored;
-  hipStream_t stream = nullptr;  // every kernel and copy of this chain is ordered on this stream
   unsigned long long batch_no = 0;
-  // constants
-  float* d_win = nullptr;
-  float2* d_tw = nullptr;
-  float2* d_tw8k = nullptr;   // 8192 points: tw2[256] ++ tw3a[1024] ++ tw3b[2048] (first-generation tables, SS_DIAG A/B runs)
-  float2* d_tw8v2 = nullptr;  // 8192 points: tw2[256] ++ lane[384] ++ wave[96] (fft8192_v2.h)
-  bool use_fft8192 = false;
-  // Implementation choices. The shipped library fixes them here; a build with -DSS_DIAG (libspecscan_diag.so, used by
-  // the A/B tests and the measurement scripts only) lets the environment override them once, at ss_create.
-  struct Diag {
-    bool backend_unfused = false;  // per-stage back-end kernels also for the 21 x 21 grouping
-    bool fft_generic = false;      // radix-4 LDS kernels instead of the register-pass ones
-    int fft_rows_r = -1;           // 0 never / 1 always use k_fft_rows256xR_psd for N2 = 512..4096 (-1: up to 2048)
-    int fft_sub = -1;              // 0 never / 1 always split N2 > 256 rows into radix-A step + 256-point rows (-1: from 2048)
-    bool fft_twopass = true;       // 2^20 points as 1024 x 1024 in two passes (SS_FFT_TWOPASS=0: 256 x 4096 in three, as until round 3)
-    bool ring_only = true;         // 2^20 points, detect mode, calls shorter than the ring: no dB plane is written (SS_RING_ONLY=0: written as ever)
-    bool fft_xcd_map = true;       // XCD-aware tile order in k_fft_rows256xR_psd
-    bool spec_standalone = false;  // spectrogram by its own two kernels instead of inside the detect tiles
-    bool pipeline = true;          // 8192 points: defer detect / emit of a call into the next calls' launches (scan_step.h)
-    int fft_tw = 2;                // 8192 points: where the twiddles come from (fft8192_v2.h: 0 global, 1 pass-2 table in LDS, 2 LDS + SGPRs)
-    bool fft_swz = true;           // 8192 points: 16-byte swizzled first exchange
-    int prio_fft = 0, prio_other = 0;  // s_setprio of k_scan_step's roles
-    std::string stamp_path;        // SS_DIAG only: dump per-workgroup start / end stamps of the 40th full k_scan_step launch here
-    long long* d_stamps = nullptr;
-    int stamp_launches = 0;
-    unsigned* d_cull_stats = nullptr;  // SS_DIAG only (SS_CULL_STATS=1): tiles seen / on the culling path / culled, printed by ss_destroy
-    // SS_DIAG only, deep pipelining: the input canary. The launch of call L + 1 reads the last frames of call L's input once
-    // more (the halo, run_call_deep); include/specscan.h tells callers to leave every input alone until ss_sync. A checksum of
-    // those frames is taken right behind launch L (the public stream waits for it: whatever the caller enqueues there after the
-    // call comes later) and again right before launch L + 1; ss_sync compares the two and fails loudly when a caller has
-    // refilled the buffer in between — a case the address check of run_call_deep cannot see (the same bytes under another pointer).
-    // Opt-in (SS_CANARY=1): the wait puts the public stream behind every launch, which is not what one wants to time.
-    bool canary = false;
-    unsigned long long* d_canary = nullptr;  // [64][2]
-    hipEvent_t ev_canary = nullptr;
-    std::vector<int> canary_pairs;           // slots whose two sums have both been enqueued
-    unsigned canary_seq = 0;
-    int canary_prev_slot = -1;               // the slot that holds the first sum of the previous call's frames (-1: none taken)
-    bool emit_wide = true;         // long rows (n >= 16384): several waves per frame in the emit stage
-    bool no_order_table = false;   // SS_DIAG: never use a dispatch-order table
-    int hint_mode = 0;             // SS_DIAG timing ablations of the list hand-over (scan_step.h); 3: plan workgroups never publish (tests/test_gpu_wait_bound.py)
-    int wait_limit = 0;            // SS_DIAG (SS_WAIT_LIMIT): StepArgs::wait_limit, 0 = the product's
-    int queues = 2;                // 8192 points, deep pipelining: launch queues (2 .. 4)
-    bool cull_65536 = true;        // tile culling at 65536 points (SS_CULL_65536=0: every averaging tile evaluated, as the product did until session 17 of round 4; see ss_create)
-    bool rows256_step = true;      // 65536 points with tile culling: the column half as a launch of its own (the plan of the call before at its front), the ROW tiles as k_scan_step's FFT role (KIND 6) with the deferred stages riding on them (SS_ROWS256_STEP=0: columns as the FFT role, rows and plan as launches of their own)
-    bool win_calc = true;          // 2^20 points in two passes and 65536 points, default window: the column tiles form their Hamming taps instead of loading them (SS_WIN_CALC=0: the table as ever)
-    bool emit_on_rows = false;     // SS_DIAG (SS_EMIT_ON_ROWS=1): 65536 points, the emit stage on the row launch instead of the column launch (A/B)
-    int merge_max_frames = 128;    // ... calls of up to this many frames (SS_MERGE_MAX)
-    bool merge_65536 = true;       // 65536 points, detect-mode calls: ONE launch per call — the column half of call k beside the row half of call k - 1 (scan_step.h KIND 7; SS_MERGE_65536=0: two launches per call, session 20's form)
-    bool det_lag2 = true;          // 65536 points with tile culling: detect(k - 2) on the column launch of call k (SS_DET_LAG2=0: detect(k - 1) on the row launch, session 19's form)
-    bool dif8 = true;              // 65536 points, int8 IQ, default window, calls that keep no plane: NO work buffer — the radix-8 fold in the load stage of the 8192-point transform, eight workgroups per frame, one launch per call whatever its length (scan_step.h KIND 8, fft65536_dif8.h; SS_DIF8=0: the four-step forms of round 4)
-    int plan_first = 0;            // 8192 points: the first plan_first pairs of every list of the launch's tile plan on detect workgroups of their own ahead of the FFT role (SS_PLAN_FIRST=n; 0: every pair behind an FFT workgroup's frame)
-    bool rows1024x256 = true;      // 262144 points (what getFft picks at 61.44 MS/s): rows through the 1024-point row tile with run maxima and ring rows — culled, no dB plane in detect mode, the 65536-point two-launch pipeline (SS_ROWS1024X256=0: round 2's path, k_fft_rows256xR_psd, every tile evaluated)
-    long long abs_start = 0;       // SS_ABS_START=n: the frame counter starts at n instead of 0 at creation and after ss_reset — sessions that cross 2^30 frames (the counter's 30-bit form indexes the long transforms' run maxima) without the twenty seconds of scanning it takes to get there (tests/test_gpu_cull.py)
-    bool drain_tail_event = true;  // 8192 points, deep pipelining: an event recorded behind the drain's last command on the public stream (SS_DRAIN_TAIL_EVENT=0: none, as until session 18 of round 6): the 20-step form 25.2 against 25.85 us per step, medians of eight alternating runs (s20)
-    int chunk_65536 = 256;         // 65536 points with tile culling: calls of more frames go through in chunks of this many (SS_CHUNK_65536=0: in one piece)
-    int chunk_long = 16;           // 2^20 points in two passes: calls of more frames go through in chunks of this many (SS_CHUNK_LONG=0: in one piece)
-    bool halo_maxima = true;       // 8192 points, deep pipelining: the re-transformed halo frames leave per-column maxima, so that the tiles of a batch's first two frame tiles are tested like the others (SS_HALO_MAXIMA=0: evaluated whatever they hold, as until session 36 of round 5)
-    int list_first_fold = -1;      // ... in the fold's launches: -1 = by the launch's size (launch_step), k > 0 = k - 1 pairs
-    int list_first = 64;           // long transforms with tile culling: the first pairs of the plan's list go to detect workgroups of their own, dispatched ahead of the launch's FFT role (SS_LIST_FIRST=0: every pair behind an FFT workgroup's tile, as until session 19 of round 4)
-    bool plan_fused = true;        // 2^20 points in two passes: the plan of call k at the front of call k + 1's column launch (SS_PLAN_FUSED=0: a launch of its own behind call k's rows, as until session 14 of round 4)
-    int ablate_roles = 0;          // SS_DIAG timing ablation (garbage results): 1 = launches carry no detect role, 2 = no emit role
-    bool cull = true;              // 8192 points: detect tiles that cannot hold a candidate are not evaluated (detect_fused.h)
-    bool deep = true;              // 8192 points: consecutive step launches independent of each other, alternating over two queues (see ss_ctx::deep)
-    bool step_long = true;         // n >= 16384: the column half of the FFT as the FFT role of k_scan_step (false: one launch per stage)
-    // Dispatch order of k_scan_step's work items when all three roles ride one launch: "prefix|cycle", comma-separated
-    // segments of a role letter (E emit, D detect, F FFT) and a workgroup count ('*' = all that are left); the cycle repeats
-    // until every item is placed, a role that has run out is skipped.
-    std::string step_order = "E*|D128,F1024";
-    // n >= 16384 (the FFT role is the column half, short workgroups): detect first. 65536 x 128 frames: 63.3 us per step
-    // against 64.7 with the order above and 70.7 with one launch per stage; 2^20 x 16: 216.8 / 235 / 216.9 (profiles/r02/s18).
-    std::string step_order_long = "E*|D*,F*";
-    // one launch per call (KIND 7): the column tiles of this call first, the row tiles of the call before behind them — two rounds of
-    // workgroups whose phases overlap. In turn (R1,F1) they took 45.7 us per 128-frame call against 41.0-41.7 in two runs, 26.2 against
-    // 24.0 per 64-frame call (rows first: 41.0 / 26.7): profiles/r04/s35_summary.txt
-    std::string step_order_merged = "E*|D*,F*,R*";
-    // ... of the radix-8 fold's launch (KIND 8; the plan's few dozen workgroups always first): the fold workgroups, then the candidate
-    // lists, then the listed tiles' detect workgroups. A detect workgroup lives 10-20 us, and every one dispatched ahead of the fold
-    // workgroups holds up one of the launch's last round by as much: detect first (the long transforms' order above) 52.8 us per
-    // 128-frame call, this order 40.3; passengers spread between the fold workgroups (F8,E2,D1 and the like) 47-52
-    // (profiles/r05/s5_summary.txt, s6_summary.txt); emit ahead of the fold workgroups: 71.7 / 129.5 us per 256- / 512-frame call against
-    // 69.8 / 126.5 (s9_summary.txt)
-    std::string step_order_fold = "F*,P*,E*,D*";
-#ifdef SS_DIAG
-    void read() {
-      const auto is = [](const char* name, const char* value) {
-        const char* v = getenv(name);
-        return v && strcmp(v, value) == 0;
-      };
-      const auto tri = [](const char* name) {
-        const char* v = getenv(name);
-        return !v ? -1 : (v[0] == '1' ? 1 : 0);
-      };
-      const auto num = [](const char* name, int dflt) {
-        const char* v = getenv(name);
-        return v ? atoi(v) : dflt;
-      };
-      backend_unfused = is("SS_BACKEND", "unfused");
-      fft_generic = is("SS_FFT_IMPL", "generic");
-      fft_rows_r = tri("SS_FFT_ROWSR");
-      fft_sub = tri("SS_FFT_SUB");
-      fft_twopass = tri("SS_FFT_TWOPASS") != 0;
-      ring_only = tri("SS_RING_ONLY") != 0;
-      fft_xcd_map = tri("SS_FFT_XCDMAP") != 0;
-      spec_standalone = is("SS_SPEC_IMPL", "standalone");
-      pipeline = tri("SS_PIPELINE") != 0;
-      fft_tw = num("SS_FFT_TW", 2);
-      fft_swz = tri("SS_FFT_SWZ") != 0;
-      prio_fft = num("SS_STEP_PRIO_FFT", 0);
-      prio_other = num("SS_STEP_PRIO_OTHER", 0);
-      if (const char* v = getenv("SS_STEP_STAMPS")) stamp_path = v;
-      emit_wide = tri("SS_EMIT_WIDE") != 0;
-      step_long = tri("SS_STEP_LONG") != 0;
-      deep = tri("SS_DEEP") != 0;
-      cull = tri("SS_CULL") != 0;
-      ablate_roles = num("SS_ABLATE_ROLES", 0);
-      cull_65536 = tri("SS_CULL_65536") != 0;
-      rows256_step = tri("SS_ROWS256_STEP") != 0;
-      plan_fused = tri("SS_PLAN_FUSED") != 0;
-      list_first = num("SS_LIST_FIRST", list_first);
-      halo_maxima = tri("SS_HALO_MAXIMA") != 0;
-      list_first_fold = getenv("SS_LIST_FIRST") ? list_first + 1 : num("SS_LIST_FIRST_FOLD", list_first_fold);
-      chunk_long = num("SS_CHUNK_LONG", chunk_long);
-      chunk_65536 = num("SS_CHUNK_65536", chunk_65536);
-      rows1024x256 = tri("SS_ROWS1024X256") != 0;
-      if (const char* v = getenv("SS_ABS_START")) abs_start = atoll(v);
-      drain_tail_event = tri("SS_DRAIN_TAIL_EVENT") != 0;
-      plan_first = num("SS_PLAN_FIRST", plan_first);
-      det_lag2 = tri("SS_DET_LAG2") != 0;
-      dif8 = tri("SS_DIF8") != 0;
-      emit_on_rows = tri("SS_EMIT_ON_ROWS") == 1;
-      merge_65536 = tri("SS_MERGE_65536") != 0;
-      merge_max_frames = num("SS_MERGE_MAX", merge_max_frames);
-      win_calc = tri("SS_WIN_CALC") != 0;
-      canary = tri("SS_CANARY") == 1;
-      queues = num("SS_QUEUES", queues);
-      hint_mode = num("SS_HINT_MODE", 0);
-      wait_limit = num("SS_WAIT_LIMIT", 0);
-      no_order_table = tri("SS_ORDER_TABLE") == 0;
-      if (tri("SS_PLAN_NOZERO") == 1) d_cull_stats = reinterpret_cast<unsigned*>(1);
-      else if (tri("SS_CULL_STATS") == 1 && hipMalloc(&d_cull_stats, 3 * sizeof(unsigned)) == hipSuccess) (void)hipMemset(d_cull_stats, 0, 3 * sizeof(unsigned));
-      if (const char* v = getenv("SS_STEP_ORDER")) step_order = step_order_long = step_order_fold = v;
-      if (const char* v = getenv("SS_STEP_ORDER_MERGED")) step_order_merged = v;
-    }
-#else
-    void read() {}
-#endif
-  } diag;
-  uint8_t* d_pass = nullptr;
+  // constant tables (upload_tables; which of them exist: ScanForm)
+  ss::device_buffer<float> d_win;
+  ss::device_buffer<float2> d_tw;
+  ss::device_buffer<float2> d_tw8k;   // 8192 points: tw2[256] ++ tw3a[1024] ++ tw3b[2048] (first-generation tables, SS_DIAG A/B runs)
+  ss::device_buffer<float2> d_tw8v2;  // 8192 points: tw2[256] ++ lane[384] ++ wave[96] (fft8192_v2.h)
+  Diag diag;  // the implementation choices (scan_form.h); what they own on the device:
+  ss::device_buffer<long long> d_stamps;  // Diag::stamp_path
+  int stamp_launches = 0;
+  ss::device_buffer<unsigned> d_cull_stats;  // Diag::cull_stats
+  std::vector<int> canary_pairs;             // Diag::canary (d_canary, ev_canary: CtxBuffers): slots whose two sums have both been enqueued
+  unsigned canary_seq = 0;
+  int canary_prev_slot = -1;                 // the slot that holds the first sum of the previous call's frames (-1: none taken)
   bool pass_dirty = true;
   // state
   std::vector<NoiseState> noise;
   // spectrogram side branch (SS_FLAG_SPECTROGRAM)
-  int spec_n = 0, spec_m = 0;  // output bins, input bins per output bin (spectrogram.cpp:14-15)
-  bool spec_in_detect = false;  // accumulated by k_detect_fused instead of the two stand-alone kernels
   // in-detect form: the partial sums of a launch are folded into their container by the next launch (or by
-  // spectrogram_flush); two buffers alternate
-  float* d_spec_part2[2] = {nullptr, nullptr};
+  // spectrogram_flush); two buffers (d_spec_part2) alternate
   int spec_cur = 0;
   // deep pipelining: detect stages of overlapping launches cannot add to a container one after the other, so every call's
   // partial sums keep a slot of their own until the next drain adds them, call by call and tile by tile — the same
   // additions in the same order as the in-detect form — on the public stream (drain_deep); a full ring drains.
-  float* d_spec_ring = nullptr;
-  size_t spec_slot_floats = 0;
   int spec_ring_next = 0;
   struct PendFold {
     const float* partial;
@@ -281,8 +138,6 @@ struct ss_ctx {
   // The additions run on a stream of their own (the public stream stays idle, so the queues need no fork): every
   // kDeepFoldBatch calls, behind one event from each queue, call by call in order. A slot is written again only after the
   // host has seen the event behind its additions complete.
-  hipStream_t s_fold = nullptr;
-  hipEvent_t ev_fold_src[kMaxQueues] = {}, ev_fold_done[16] = {};
   unsigned fold_batches = 0;
   int slot_batch[kDeepSpecSlots];  // the batch (index into ev_fold_done) that added the slot's sums, -1: nothing outstanding
   bool fold_dirty = false;         // s_fold holds work the public stream has not been made to wait for
@@ -290,32 +145,25 @@ struct ss_ctx {
   float* spec_pending_sum = nullptr;  // container (SpecState::d_sum) the partial sums in d_spec_part2[spec_cur ^ 1] belong to
   int spec_pending_tiles = 0;
   std::vector<SpecState> spec;
-  float* d_spec_partial = nullptr;
   int frames_pushed = 0;  // Averager::m_frames, saturates at grouping_y
   int rot_frames = 0;     // rows of the previous batch still to be folded into the history rows (lazy ring rotation)
   // planes (frame-major rows of n floats)
   // back end, fused path (grouping 21 x 21, max_batch <= 65536): ring and counters are double-buffered
-  bool fused = false;
   // Averager ring: the newest kHistRows rel rows (newest last) are a WINDOW [hist_start, hist_start + kHistRows) of a
   // longer buffer. A batch shorter than the ring appends its rows behind the window and the window slides (nothing is
   // copied until the buffer's end is reached); a longer batch writes a fresh window clear of the one it reads.
-  float* d_hist = nullptr;
-  int hist_rows = 0;   // capacity in rows
   int hist_start = 0;
   long long abs_frames = 0;               // frames since the last reset: frame tiles are aligned to this index
   // per-frame candidate counts, three buffers in rotation: batch k accumulates into [k % 3]; its emit stage — which may
   // run two launches later, next to the detect stage of batch k + 1 — reads them and zeroes [(k + 2) % 3] for batch k + 2
   // (deep pipelining, below: six buffers, the emit stage of batch k runs four launches after its FFT stage and zeroes
   // [(k + 4) % 6], whose last reader ran two launches earlier on the same queue)
-  int* d_cnt3[3 * kMaxQueues] = {};
   int cnt_cur = 0;
   int cnt_frames[3 * kMaxQueues] = {};  // how many entries of each buffer may be non-zero
-  int ncnt = 3, nbuf = 1, npsd = 1, lag = 1;  // buffers in rotation: counters, mask / avg planes / offsets, internal PSD planes; launches between a call's stages
-  float* d_relplane = nullptr;            // full rel plane, only when a caller asks for it (lazy)
+  ss::device_buffer<float> d_relplane;           // full rel plane, only when a caller asks for it (lazy)
   int last_n_learn = 0;
   // Stage pipelining (scan_step.h): the stages of the last calls are kept as arguments until a later launch carries them (or
   // flush_stages drains them) — which stage waits for what, and the schedule of every form: stage_slots.h.
-  bool step_path = false;
   struct PendDet {
     ss::DetectArgs a;  // (a.tile_list points at the list its plan fills)
     int tiles;
@@ -335,23 +183,15 @@ struct ss_ctx {
   };
   using Waiting = ss::StageSlots<PendDet, PendPlan, ss::EmitArgs, PendRows>;
   Waiting wait;
-  bool x256_tile = false;     // 262144 points: the row half through the 1024-point row tile (k_fft_rows1024_psd<8>) in every context, culled or not — the same bits either way
-  bool rows1024x256 = false;  // 262144 points with tile culling (round 6): 256-point column tiles as k_scan_step's FFT role with the plan of the call before, detect(k - 2) and emit(k - 3); the rows as a launch of k_fft_rows1024_psd<8>
-  bool rows256_step = false;  // 65536 points with tile culling: columns as their own launch, rows as k_scan_step's FFT role (see Diag::rows256_step)
-  bool det_lag2 = false;      // a call's detect stage waits for its plan and rides on the column launch two calls later (the schedule headed DET_LAG2 in stage_slots.h)
   // 65536 points, int8 IQ (fft65536_dif8.h): calls that keep no plane go through the radix-8 fold — one launch of 8 x frames
   // workgroups (4 x frames since two residues share one) that leaves dB rows in the fold's BLOCKED order (32 Q bins per block,
   // fft65536_dif8.h: dif_bin_offset; ring_db_rows) in the averager ring's buffer and run maxima in the plan's layout 2; every other call (learning frames, planes handed out, stream-ordered contexts) takes the four-step form, whose rows
   // are in bin order. ring_perm8 says which order the ring's window and the stages that wait are in; a call of the other kind
   // drains what waits and has the window's 35 rows rewritten first (set_ring_form).
-  bool dif8 = false;
-  int dif_logq = 3;               // log2 of the fold's radix: 3 (65536 points) or 4 (131072 points: sixteen residues, KIND 9)
   // SS_FLAG_NO_CULL where the fold runs: the fold IS the culling context's transform (its rows go to the ring's buffer, the plan hands its
   // tiles out), and the four-step form the flag used to fall back to rounds its dB values differently — the lists agreed, cand_avg
   // was off by an ulp in a third of the candidates (tests/test_gpu_detect_settings.py). So the flag keeps the context there and the
   // plan lists every tile untested (PlanLongDet::planes_out): the same transform, the same bits.
-  bool plan_all = false;
-  bool cull_fold_only = false;    // 131072 points: the culling machinery (run maxima, plan, ring rows by the FFT stage) serves the fold's calls only — the four-step form of that size has no such epilogue
   bool ring_perm8 = false;
   bool last_rows_perm8 = false;   // ... and the rows ss_read_window serves (last_hist, last_rel_rows)
   // Long transforms, detect-mode calls (ring-only): the FFT stage leaves its rows in the ring's buffer as dB values and the tiles that
@@ -364,13 +204,9 @@ struct ss_ctx {
   bool last_rows_db = false;      // ... when the last call left such rows at all
   const float* last_settled_lo = nullptr;  // ... except the rows in [last_settled_lo, last_settled_hi): settle_ring_db has turned them into noise-relative
   const float* last_settled_hi = nullptr;  //     rows since (a retune or ss_reset_noise after the call) — ss_read_window must not subtract the ceiling twice
-  float2* d_dif8_tab = nullptr;   // the fold's tables (dif8_host_tables)
-  float* d_perm_tmp = nullptr;    // 35 rows: the window on its way from one order to the other
+  ss::device_buffer<float2> d_dif8_tab;   // the fold's tables (dif8_host_tables)
   ss::RingPrev hist_prev{0, -1, 0};  // what the detect stage of the last call reads of the ring's buffer (ring_place.h)
   ss::RingPrev hist_prev2{0, -1, 0}; // ... of the call before it (merged contexts protect two)
-  bool merge = false;   // 65536 / 262144 points, ONE launch per call for calls that keep no dB plane (the schedule headed MERGED in stage_slots.h; two work buffers)
-  int merge_max = 128;  // the largest call (frames) that is one launch
-  float2* d_work2 = nullptr;
   int work_cur = 0;
   int buf_cur = 0;               // which of the rotating buffers the NEXT batch writes
   int psd_cur = 0;
@@ -388,15 +224,10 @@ struct ss_ctx {
   // (flush_stages: the two queues drain their last stages side by side, then the public stream waits for both). Calls
   // that cannot overlap (learning frames, fewer frames than the ring holds, a caller reusing a buffer too soon) drain
   // first and run their three stages in order on the public stream.
-  bool deep = false;
   // (Round 3: nq queues instead of two — launch L on queue L mod nq carries FFT(L), detect(L - nq), emit(L - 2 nq). With two,
   // a queue's next launch cannot start before its previous one has wholly finished, and while that one's last workgroups
   // drain, the OTHER queue's launch has long been dispatched in full: a third of the CU slots stand empty around every
   // hand-over. Everything said about "even" distances below reads "multiples of nq".)
-  int nq = 2;
-  hipStream_t s_ab[kMaxQueues] = {};
-  hipEvent_t ev_launch[32] = {}, ev_in[4] = {}, ev_join[kMaxQueues] = {}, ev_tail = nullptr;
-  float* d_halo[2 * kMaxQueues] = {};  // [kHistRows][n] each: written by launch L, read by detect(L) in launch L + nq
   const void* deep_prev_iq = nullptr;  // the previous call's frames (caller's buffer: untouched until ss_sync by contract)
   long long deep_prev_stride = 0;
   long deep_L = 0;             // launches since the last drain
@@ -405,7 +236,6 @@ struct ss_ctx {
   // whole ring. A ring-reading detect stage — the first of an overlapped run, launch 2 — is finished for both queues by
   // the run's first synchronisation (launch kDeepSyncPhase): with more windows than that, the window it reads is not
   // written again while it runs, and nobody has to wait for it.
-  bool deep_ring_safe = false;
   unsigned deep_forks = 0;
   struct PendEmit {
     ss::EmitArgs a;
@@ -447,69 +277,35 @@ struct ss_ctx {
   bool deep_iq_recycled = false;  // the caller was seen refilling an input buffer a call in flight still reads: no overlap for this context any more
   bool deep_events = false;   // record ev_launch after every launch
   long deep_events_from = 0;  // first launch of this run of launches that has its event
-  // k_scan_step's dispatch-order table for the current launch shape (rebuilt when the shape changes; two buffers so that a
-  // launch still in flight keeps the table it was given)
-  struct OrderTable {
-    int key[6];  // FFT / detect / emit / plan / row workgroups of the launch shape, and which order pattern it was built from
-    uint32_t* d;
-    unsigned long long used;       // 0: free
-    std::vector<uint32_t> host;    // what was uploaded (kept alive: the copy is asynchronous)
-    hipStream_t stream;            // the stream it was uploaded on
-  };
-  std::vector<OrderTable> order_tables;  // one per launch shape met so far (a handful: steady state, pipeline fill, drain)
-  size_t order_capacity = 0;
   unsigned long long order_clock = 0;
   int n_cus = 256;
-  uint32_t* d_mask2[2 * kMaxQueues] = {};
-  float* d_avg2[2 * kMaxQueues] = {};
-  int* d_off4[2 * kMaxQueues] = {};  // the library's copy of the candidate offsets, per rotating set (d_off = the latest)
-  float* d_psd2[2 * kMaxQueues + 1] = {};
-  // Tile culling (8192 points, detect_fused.h): the FFT role's per-column maxima of a call's PSD rows, [32][max_batch],
-  // rotating with the mask / avg / offset buffers (written by the call's FFT launch, read by its detect stage)
-  float* d_segsum[2 * kMaxQueues] = {};
-  int* d_live[2 * kMaxQueues] = {};  // DetectArgs::live: the tiles of a call that must be evaluated (plan role -> the launch's other workgroups)
-  bool cull = false;
   // Tile culling, long transforms (65536 points and 2^19 / 2^20: the sizes whose rows go through k_fft_rows256_psd): the rows
   // kernel leaves the maximum of every 32-bin run per frame in d_smax, a ring of smax_rows frames (>= max_batch + 35) indexed by
   // the frame count since the last reset, and writes the averager ring itself in calls without learning frames; k_plan_long
   // lists the tiles that must be evaluated in d_tlist (rotating with the mask buffers). clean_abs: the first frame (counted
   // since the last reset) from which every frame is a non-learning frame under the current noise ceiling — a tile is only
   // tested when all 36 of its rows are at or behind it.
-  bool cull_long = false;
-  float* d_smax = nullptr;
-  int smax_rows = 0;
-  int* d_tlist[2 * kMaxQueues] = {};
   long long clean_abs = 0;
   const float* last_avg = nullptr;  // the avg plane (sparse or kept) of the last batch
   const float* last_hist = nullptr;       // ring rows as they were before the last batch
   float* last_thr = nullptr;
-  // back end, unfused path (any other grouping): one buffer holds the ring rows + the batch rows
-  float* d_rel = nullptr;   // (G-1) history rows + max_batch rows
-  float* d_hist_tmp = nullptr;
-  float* d_avgy = nullptr;
-  float2* d_work = nullptr;  // four-step intermediate (N > 8192)
-  float2* d_tw256 = nullptr; // W_256^(m r), r*16 + m: second pass of the 256-point register FFTs (N >= 65536)
-  float2* d_tw_rowsR = nullptr;  // N = 2^17 .. 2^19: [q][k'] W_N2^(q k') for k_fft_rows256xR_psd (N2 = 512 .. 2048)
-  float2* d_tw_small = nullptr;  // N = 1024, 2048, 4096: [q][k'] W_N^(q k') for the final radix-R pass of k_fft256xR_psd
-  float2* d_tw_sub = nullptr;   // N = 2^19, 2^20: [c][b] W_N2^(b c) for k_fft_sub_dft (N2 = N / 256 = 256 A)
-  float2* d_tw_cols = nullptr;  // N >= 65536: step-A twiddle factored for k_fft_cols256, [j][n2] W_N^(n2 j) then [k][n2] W_N^(16 n2 k)
-  // N = 2^20 as 1024 x 1024 (fft1024_kernels.h): two passes over the work buffer instead of three
-  bool two_pass = false;  // (its tables: one block in d_tw_cols)
+  ss::device_buffer<float2> d_tw256; // W_256^(m r), r*16 + m: second pass of the 256-point register FFTs (N >= 65536)
+  ss::device_buffer<float2> d_tw_rowsR;  // N = 2^17 .. 2^19: [q][k'] W_N2^(q k') for k_fft_rows256xR_psd (N2 = 512 .. 2048)
+  ss::device_buffer<float2> d_tw_small;  // N = 1024, 2048, 4096: [q][k'] W_N^(q k') for the final radix-R pass of k_fft256xR_psd
+  ss::device_buffer<float2> d_tw_sub;   // N = 2^19, 2^20: [c][b] W_N2^(b c) for k_fft_sub_dft (N2 = N / 256 = 256 A)
+  ss::device_buffer<float2> d_tw_cols;  // N >= 65536: step-A twiddle factored for k_fft_cols256, [j][n2] W_N^(n2 j) then [k][n2] W_N^(16 n2 k)
   // Detect mode at 2^20 points (BASELINE config 5): the rows kernel writes the batch's rows as noise-relative rows (rel = dB - thr)
   // into the averager ring's buffer — behind the window for calls shorter than the ring, as a region of their own whose last 35 rows
   // are the next window otherwise (place_ring) — and no dB plane is written at all: the detect tiles take the batch's rows from
   // there, with a ceiling of zeros to subtract (x - 0.0f is x: the same bits) — unless somebody wants a plane.
-  float* d_win1024 = nullptr;        // the window taps in the 1024-point column tiles' order
-  float2* d_wtab1024 = nullptr;      // the default window only: (cos, sin)(2 pi m / (N - 1)), m < N / 16 — the column tiles of 2^20-point (fft1024_kernels.h, WCALC) and of 65536-point frames (fft256_kernels.h) form their taps from it
-  float* d_zero_row = nullptr;       // n zeros
+  ss::device_buffer<float> d_win1024;        // the window taps in the 1024-point column tiles' order
+  ss::device_buffer<float2> d_wtab1024;      // the default window only: (cos, sin)(2 pi m / (N - 1)), m < N / 16 — the column tiles of 2^20-point (fft1024_kernels.h, WCALC) and of 65536-point frames (fft256_kernels.h) form their taps from it
   const float* last_rel_rows = nullptr;  // the last batch's rows as rel values (ring-only calls: last_psd is null then)
-  bool use_fft256 = false;
-  int* d_counts = nullptr;
-  int* d_off = nullptr;
+  int* d_off = nullptr;  // (a view: d_off4 of the latest set)
   // host-entry staging
-  void* d_in = nullptr;
-  int* d_cand_idx = nullptr;
-  float* d_cand_avg = nullptr;
+  ss::device_buffer<unsigned char> d_in;
+  ss::device_buffer<int> d_cand_idx;
+  ss::device_buffer<float> d_cand_avg;
   int cand_cap_alloc = 0;
   const float* last_psd = nullptr;  // where the last batch's PSD plane lives (device)
   // the fused detect stage launched last, as it was launched (launch_step, run_backend_fused): what a sparse tracked feed replays on
@@ -526,7 +322,7 @@ struct ss_ctx {
   bool prof_on = false;
   int prof_every = 1;       // attach events to every prof_every-th launch only (the event packets cost ~4 us of GPU timeline each)
   unsigned prof_seen = 0;
-  std::vector<hipEvent_t> prof_events;  // pairs
+  std::vector<ss::hip_event> prof_events;  // pairs
   std::vector<int> prof_slots;          // which kernel of the chain each pair timed (SS_KSLOT_*)
   std::vector<int> prof_frames;         // ... and how many frames that launch covered (a call taken through in chunks: the chunk's)
   int prof_launch_frames = 0;           // frames of the launches being enqueued now (run_batch, its chunk loops)
@@ -534,7 +330,6 @@ struct ss_ctx {
   bool prof_call = false;   // the current call is a sampled one: its other kernels (rows, radix-A step, plan) carry events too
   // ss_get_stats: host-side counters, and the device-side ones (detect_fused.h kStat*: tiles tested / culled, wait fallbacks)
   ss_stats stats{};
-  unsigned long long* d_stats = nullptr;
   // StepArgs::wait_limit. A poll is a ~0.25 us sleep and a load, ~0.75 us in all; the plan role publishes within 5-10 us of its launch's
   // start, so a consumer normally polls not at all (FFT role: it asks two thirds into its frame) or a dozen times (drain launches);
   // 128 polls are 0.1 ms. The bound is not decoration: with TWO PROCESSES on one GPU (bench.py --gpus 2 on a one-GPU box) the circular
@@ -544,15 +339,10 @@ struct ss_ctx {
   // (profiles/r04/s9_summary.txt); round 3's spin would have hung there. A consumer that helps itself early costs 5 us.
   int wait_limit = 128;
   // ss_input_wait: the launches (or, in order on the public stream, the calls) whose events a producer may wait on
-  hipEvent_t ev_call[32] = {};   // in-order contexts: recorded on the public stream behind every call once ss_input_wait has been used
+  ss::hip_event ev_call[32];   // in-order contexts: recorded on the public stream behind every call once ss_input_wait has been used
   bool input_events = false;
   long input_events_from = 0;    // deep pipelining: first launch of the current run of launches that has its event (ev_launch)
   unsigned long long call_seq = 0;  // device calls so far (ss_process_device)
-  // SS_FLAG_REFERENCE_NAN (reference_nan.h): per-frame first non-finite bins of the batch, the state carried between batches, per-frame poison limits
-  bool ref_nan = false;
-  int* d_nf = nullptr;        // [max_batch][4]: first NaN / -inf / +inf bin of every frame of the batch (n: none)
-  int* d_nan_state = nullptr; // ss::NanState
-  int* d_bad_from = nullptr;  // [max_batch]: bins >= this are NaN in the reference's avg row (n: none)
   NanStage nan_pending{};     // of the call whose detect stage is still deferred
   std::mutex mtx;
   char err[512] = "";
@@ -611,13 +401,6 @@ hipError_t stream_wait(hipStream_t stream) {
 static_assert(ss::FMT_CF32 == SS_FMT_CF32 && ss::FMT_CS8 == SS_FMT_CS8 && ss::FMT_CU8 == SS_FMT_CU8 && ss::FMT_CS16 == SS_FMT_CS16, "ss_format");
 size_t in_bytes_per_sample(int fmt) { return (size_t)ss::fmt_bytes(fmt); }
 
-// getFft — sources/utils/radio_utils.cpp:98-104
-int get_fft(int32_t sample_rate, int32_t max_step) {
-  uint32_t v = 1;
-  while ((double)max_step < (double)sample_rate / v) v <<= 1;
-  return (int)v;
-}
-
 // isIndexInRange (sources/radio/sdr_device.cpp:153-158) && !isIndexIgnored (transmission.cpp:156-164),
 // evaluated once per retune on the host and kept as one byte per bin on the device.
 void build_pass_mask(const ss_ctx* c, std::vector<uint8_t>& out) {
@@ -649,10 +432,10 @@ NoiseState* noise_for(ss_ctx* c, int32_t center) {
 bool prof_take(ss_ctx* c, int slot, hipEvent_t* a, hipEvent_t* b) {
   if (c->prof_used + 2 > c->prof_events.size()) {
     if (c->prof_events.size() >= 2 * 8192) return false;
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return false;
-    c->prof_events.push_back(e0);
-    c->prof_events.push_back(e1);
+    ss::hip_event e0, e1;
+    if (e0.create(hipEventDefault) != hipSuccess || e1.create(hipEventDefault) != hipSuccess) return false;
+    c->prof_events.push_back(std::move(e0));
+    c->prof_events.push_back(std::move(e1));
     c->prof_slots.push_back(0);
     c->prof_frames.push_back(0);
   }
@@ -689,7 +472,7 @@ void launch_lds(ss_ctx* c, const void* d_iq, long long item_stride, int nframes,
   hipEvent_t e0, e1;
   if (prof_pair(c, &e0, &e1)) {
     hipExtLaunchKernelGGL((ss::k_fft_psd_lds<LOGN, LOGTOT, FMT>), dim3(blocks), dim3(ss::kFftThreads), lds, c->stream, e0, e1, 0, d_iq,
-                          item_stride, nframes, c->d_win, c->d_tw, c->db_off, c->cfg.int_scale, d_psd);
+                          item_stride, nframes, c->d_win.get(), c->d_tw.get(), c->db_off, c->cfg.int_scale, d_psd);
   } else {
     hipLaunchKernelGGL((ss::k_fft_psd_lds<LOGN, LOGTOT, FMT>), dim3(blocks), dim3(ss::kFftThreads), lds, c->stream, d_iq, item_stride,
                        nframes, c->d_win, c->d_tw, c->db_off, c->cfg.int_scale, d_psd);
@@ -720,7 +503,7 @@ ss::ColsArgs cols256_args(ss_ctx* c, const void* d_iq, long long item_stride) {
   g.work = c->d_work;
   g.logn2 = c->two_pass ? 10 : c->logn - 8;
   if ((c->two_pass || c->rows1024x256) && c->cull_long) {  // (the column tiles clear the frames' rows of the run-maxima ring: the rows kernel gathers them by atomic maxima)
-    g.smax = reinterpret_cast<unsigned*>(c->d_smax);
+    g.smax = reinterpret_cast<unsigned*>(c->d_smax.get());
     g.smax_mask = c->smax_rows - 1;
     g.abs0 = (int)(c->abs_frames & 0x3fffffff);
   }
@@ -840,7 +623,7 @@ void launch_four_step256(ss_ctx* c, const void* d_iq, long long item_stride, int
       if (!done && c->d_tw_sub) {
         // rows of 256 A points (A = 8, 16) as an in-place radix-A step over the stride-256 index, then 256-point rows
         constexpr int A = 1 << (LOGN2 - 8);
-        SS_LAUNCH_SLOT(c, SS_KSLOT_SUB, (ss::k_fft_sub_dft<A>), dim3(nframes * 256), dim3(256), 0, c->d_work, (const float2*)c->d_tw_sub);
+        SS_LAUNCH_SLOT(c, SS_KSLOT_SUB, (ss::k_fft_sub_dft<A>), dim3(nframes * 256), dim3(256), 0, c->d_work.get(), (const float2*)c->d_tw_sub);
         SS_LAUNCH_SLOT(c, SS_KSLOT_ROWS, ss::k_fft_rows256_psd, dim3(nframes * A * 8), dim3(512), ss::kFft256RowsPsdLdsBytes, (const float2*)c->d_work,
                        (const float2*)c->d_tw256, c->db_off, d_psd, 8 + LOGN2, LOGN2 - 8, rx);
         done = true;
@@ -849,7 +632,7 @@ void launch_four_step256(ss_ctx* c, const void* d_iq, long long item_stride, int
     if (!done) {
       const size_t lds = sizeof(float2) * ((1 << 13) + 128);
       const int row_tiles = 256 >> (13 - LOGN2);
-      SS_LAUNCH_SLOT(c, SS_KSLOT_ROWS, (ss::k_fft_rows_psd<8, LOGN2>), dim3(nframes * row_tiles), dim3(ss::kFftThreads), lds, c->d_work, c->d_tw,
+      SS_LAUNCH_SLOT(c, SS_KSLOT_ROWS, (ss::k_fft_rows_psd<8, LOGN2>), dim3(nframes * row_tiles), dim3(ss::kFftThreads), lds, c->d_work.get(), c->d_tw.get(),
                      c->db_off, d_psd);
     }
   }
@@ -931,7 +714,7 @@ void step_order(ss_ctx* c, ss::StepArgs& a, hipStream_t stream) {
   // keep changing AND whose launches carry detect workgroups of their own — is the least recently used one recycled, after
   // everything in flight has finished. (No table at all is always correct: the roles in segments.)
   if (out.size() > c->order_capacity || c->order_tables.empty()) return;
-  ss_ctx::OrderTable* slot = nullptr;
+  OrderTable* slot = nullptr;
   for (auto& t : c->order_tables)
     if (t.used == 0) {
       slot = &t;
@@ -1105,10 +888,10 @@ void launch_step(ss_ctx* c, const FftRole* fft, const ss_ctx::Waiting::Riders& r
   a.hint_mode = c->diag.hint_mode;
   bool dump_stamps = false;
   if (!c->diag.stamp_path.empty() && fft && det && emit && ss::step_items(a) <= 8192) {
-    if (!c->diag.d_stamps) (void)hipMalloc(&c->diag.d_stamps, sizeof(long long) * 4 * (8192 + 16384));  // (per workgroup, then per tile)
-    if (c->diag.d_stamps && ++c->diag.stamp_launches == 40) {
-      a.stamps = c->diag.d_stamps;
-      a.det.stamp_mid = c->diag.d_stamps + 4 * 8192;  // (4 per tile, behind the per-workgroup stamps)
+    if (!c->d_stamps) (void)c->d_stamps.alloc(4 * (8192 + 16384));  // (per workgroup, then per tile)
+    if (c->d_stamps && ++c->stamp_launches == 40) {
+      a.stamps = c->d_stamps;
+      a.det.stamp_mid = c->d_stamps + 4 * 8192;  // (4 per tile, behind the per-workgroup stamps)
       (void)hipMemsetAsync(a.det.stamp_mid, 0, sizeof(long long) * 4 * 16384, stream);
       dump_stamps = true;
     }
@@ -1133,14 +916,14 @@ void launch_step(ss_ctx* c, const FftRole* fft, const ss_ctx::Waiting::Riders& r
     const int wgs = ss::step_items(a);
     std::vector<long long> h((size_t)4 * wgs);  // (wgs <= 8192 here)
     (void)hipStreamSynchronize(stream);
-    (void)hipMemcpy(h.data(), c->diag.d_stamps, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(h.data(), c->d_stamps, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
     if (FILE* fp = fopen(c->diag.stamp_path.c_str(), "w")) {
       for (int b = 0; b < wgs; ++b)
         fprintf(fp, "%d %lld %lld %lld %lld %lld %lld\n", b, h[4 * b], h[4 * b + 1], h[4 * b + 2] >> 32, h[4 * b + 2] & 0xffffffff, h[4 * b + 3] >> 32, h[4 * b + 3] & 0xffffffff);
       fclose(fp);
       const int n_tiles = std::min(16384, (a.det.n / 256) * ss::plan_frame_tiles(a.det.nframes, a.det.shift));
       std::vector<long long> m((size_t)4 * n_tiles);
-      (void)hipMemcpy(m.data(), c->diag.d_stamps + 4 * 8192, sizeof(long long) * m.size(), hipMemcpyDeviceToHost);
+      (void)hipMemcpy(m.data(), c->d_stamps + 4 * 8192, sizeof(long long) * m.size(), hipMemcpyDeviceToHost);
       if (FILE* fm = fopen((c->diag.stamp_path + ".det").c_str(), "w")) {
         for (int t = 0; t < n_tiles; ++t) fprintf(fm, "%d %lld %lld %lld %lld\n", t, m[4 * t], m[4 * t + 1], m[4 * t + 2], m[4 * t + 3]);
         fclose(fm);
@@ -1276,7 +1059,7 @@ void drain_deep(ss_ctx* c) {
 void launch_nan_stage(ss_ctx* c, const NanStage& g) {
   if (!g.psd || g.nframes <= 0) return;
   hipLaunchKernelGGL(ss::k_nonfinite_scan, dim3(g.nframes), dim3(256), 0, c->stream, g.psd, c->n, g.n_learn, c->d_nf);
-  hipLaunchKernelGGL(ss::k_nan_plan, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<ss::NanState*>(c->d_nan_state), (const int*)c->d_nf, g.nframes, c->n, g.pushed_before, c->d_bad_from);
+  hipLaunchKernelGGL(ss::k_nan_plan, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<ss::NanState*>(c->d_nan_state.get()), (const int*)c->d_nf, g.nframes, c->n, g.pushed_before, c->d_bad_from);
   hipLaunchKernelGGL(ss::k_nan_apply, dim3(g.nframes), dim3(256), 0, c->stream, (const int*)c->d_bad_from, c->n, g.maskbits, g.counts, g.avg_full);
 }
 
@@ -1529,7 +1312,7 @@ int run_backend_fused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, N
   da.stats = c->d_stats;
   c->stats.tiles_total += (unsigned long long)tiles;
 #ifdef SS_DIAG
-  da.cull_stats = c->diag.d_cull_stats;
+  da.cull_stats = c->diag.plan_nozero ? reinterpret_cast<unsigned*>(1) : c->d_cull_stats.get();  // (SS_DIAG: the sentinel, or the counters)
 #endif
   if (spec) {
     da.spec_partial = c->d_spec_part2[c->spec_cur];
@@ -1613,12 +1396,8 @@ SpecState* spectrogram_container(ss_ctx* c) {
     if (s.center == center) return &s;
   SpecState ns;
   ns.center = center;
-  if (hipMalloc(&ns.d_sum, sizeof(float) * (size_t)c->spec_n) != hipSuccess) return nullptr;
-  if (hipMemsetAsync(ns.d_sum, 0, sizeof(float) * (size_t)c->spec_n, c->stream) != hipSuccess) {
-    (void)hipFree(ns.d_sum);
-    return nullptr;
-  }
-  c->spec.push_back(ns);
+  if (!ss::hip_steps().alloc(ns.d_sum, (size_t)c->spec_n).zero_async(ns.d_sum, (size_t)c->spec_n, c->stream).ok()) return nullptr;
+  c->spec.push_back(std::move(ns));
   return &c->spec.back();
 }
 
@@ -1642,7 +1421,7 @@ int spectrogram_accumulate(ss_ctx* c, SpecState* g, const float* d_psd, int nfra
 }
 
 #ifdef SS_DIAG
-// (input canary, Diag::d_canary) position-weighted sum of `nwords` 32-bit words: one workgroup, result in *out
+// (input canary, Diag::canary: ss_ctx::d_canary) position-weighted sum of `nwords` 32-bit words: one workgroup, result in *out
 __global__ __launch_bounds__(1024) void k_iq_checksum(const uint32_t* __restrict__ words, size_t nwords, unsigned long long* __restrict__ out) {
   __shared__ unsigned long long part[16];
   unsigned long long acc = 0;
@@ -1764,9 +1543,9 @@ int run_call_deep(ss_ctx* c, const void* d_iq, long long item_stride, int nframe
                      (size_t)(c->deep_prev_frames - role.n_halo) * (size_t)c->deep_prev_stride * in_bytes_per_sample(c->cfg.in_format);
       role.halo_psd = c->d_halo[L % (2 * c->nq)];
 #ifdef SS_DIAG
-      if (c->diag.d_canary && c->diag.canary_prev_slot >= 0) {  // the frames this launch reads once more: are they what the launch before saw?
-        canary_sum(c, c->deep_prev_iq, c->deep_prev_stride, c->deep_prev_frames, q, c->diag.d_canary + 2 * c->diag.canary_prev_slot + 1);
-        c->diag.canary_pairs.push_back(c->diag.canary_prev_slot);
+      if (c->d_canary && c->canary_prev_slot >= 0) {  // the frames this launch reads once more: are they what the launch before saw?
+        canary_sum(c, c->deep_prev_iq, c->deep_prev_stride, c->deep_prev_frames, q, c->d_canary + 2 * c->canary_prev_slot + 1);
+        c->canary_pairs.push_back(c->canary_prev_slot);
       }
 #endif
     }
@@ -1783,12 +1562,12 @@ int run_call_deep(ss_ctx* c, const void* d_iq, long long item_stride, int nframe
   }
   launch_step(c, &role, {has_det ? &d : nullptr, has_emit ? &e.a : nullptr}, q);
 #ifdef SS_DIAG
-  c->diag.canary_prev_slot = -1;
-  if (overlap && c->diag.d_canary && nframes >= kHistRows && c->diag.canary_pairs.size() < 60) {
-    c->diag.canary_prev_slot = (int)(c->diag.canary_seq++ & 63);
-    canary_sum(c, d_iq, item_stride, nframes, q, c->diag.d_canary + 2 * c->diag.canary_prev_slot);
-    SS_HIP(c, hipEventRecord(c->diag.ev_canary, q));
-    SS_HIP(c, hipStreamWaitEvent(c->stream, c->diag.ev_canary, 0));
+  c->canary_prev_slot = -1;
+  if (overlap && c->d_canary && nframes >= kHistRows && c->canary_pairs.size() < 60) {
+    c->canary_prev_slot = (int)(c->canary_seq++ & 63);
+    canary_sum(c, d_iq, item_stride, nframes, q, c->d_canary + 2 * c->canary_prev_slot);
+    SS_HIP(c, hipEventRecord(c->ev_canary, q));
+    SS_HIP(c, hipStreamWaitEvent(c->stream, c->ev_canary, 0));
   }
 #endif
   if (overlap) {
@@ -2267,102 +2046,123 @@ int get_noise(ss_ctx* c, NoiseState** out) {
     NoiseState nz;
     nz.center = center;
     const size_t extra = (size_t)std::max(32, c->n / 256);  // + the per-tile-column minima (tile culling)
-    SS_HIP(c, hipMalloc(&nz.d_thr, sizeof(float) * ((size_t)c->n + extra)));
-    hipLaunchKernelGGL(ss::k_fill, dim3(grid_for((size_t)c->n + extra, 256)), dim3(256), 0, c->stream, nz.d_thr, (size_t)c->n + extra, -FLT_MAX);
-    c->noise.push_back(nz);
+    SS_HIP(c, nz.d_thr.alloc((size_t)c->n + extra));
+    hipLaunchKernelGGL(ss::k_fill, dim3(grid_for((size_t)c->n + extra, 256)), dim3(256), 0, c->stream, nz.d_thr.get(), (size_t)c->n + extra, -FLT_MAX);
+    c->noise.push_back(std::move(nz));
     z = &c->noise.back();
   }
   *out = z;
   return SS_OK;
 }
 
-void free_ctx(ss_ctx* c) {
-  if (!c) return;
-  (void)hipSetDevice(c->cfg.device_id);
-  for (hipStream_t q : c->s_ab)
-    if (q) (void)hipStreamSynchronize(q);
-  if (c->s_fold) (void)hipStreamSynchronize(c->s_fold);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-#ifdef SS_DIAG
-  if (c->diag.d_cull_stats > reinterpret_cast<unsigned*>(1)) {
-    unsigned h[3] = {0, 0, 0};
-    if (hipMemcpy(h, c->diag.d_cull_stats, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess)
-      fprintf(stderr, "[specscan diag] detect tiles %u, on the culling path %u, culled %u\n", h[0], h[1], h[2]);
-    (void)hipFree(c->diag.d_cull_stats);
+}  // namespace
+
+namespace {
+
+float2 unit_root(double num, double den) {  // W_den^num
+  const double ang = -2.0 * M_PI * num / den;
+  return make_float2((float)cos(ang), (float)sin(ang));
+}
+
+// W_256^(m r) at r * 16 + m: second pass of the 256-point register FFTs
+std::vector<float2> w256_table() {
+  std::vector<float2> t(256);
+  for (int r = 0; r < 16; ++r)
+    for (int m = 0; m < 16; ++m) t[(size_t)(r * 16 + m)] = unit_root((double)(m * r), 256.0);
+  return t;
+}
+
+// [q][k] W_period^(q k), k < 256: the radix-R passes behind (or in front of) 256-point transforms
+std::vector<float2> radix_table(int R, double period) {
+  std::vector<float2> t((size_t)R * 256);
+  for (int q = 0; q < R; ++q)
+    for (int k = 0; k < 256; ++k) t[(size_t)q * 256 + k] = unit_root((double)q * k, period);
+  return t;
+}
+
+std::vector<float2> fft8192_v2_table() {  // tw2[256] ++ lane[384] ++ wave[96]
+  std::vector<float2> v2((size_t)(256 + 384 + 96));
+  ss::fft8192_v2_host_tables(v2.data(), v2.data() + 256, v2.data() + 256 + 384);
+  return v2;
+}
+
+// The constant tables the form names. Window: caller's taps or gr::fft::window::hamming(N) (sdr_device.cpp:164; GNU Radio's
+// definition: 0.54 - 0.46*cos(2*pi*n/(N-1)) in double, stored as float). Twiddles W_N^k from double.
+void upload_tables(ss_ctx* c, const float* window, ss::hip_steps& made) {
+  const int n = c->n;
+  std::vector<float> win((size_t)n);
+  if (window) {
+    memcpy(win.data(), window, sizeof(float) * (size_t)n);
+  } else {
+    const float M = (float)(n - 1);
+    for (int i = 0; i < n; ++i) win[(size_t)i] = (float)(0.54 - 0.46 * cos((2.0 * M_PI * i) / M));
   }
-#endif
-  for (hipStream_t q : c->s_ab)
-    if (q) (void)hipStreamDestroy(q);
-  if (c->s_fold) (void)hipStreamDestroy(c->s_fold);
-  for (hipEvent_t e : c->ev_fold_src)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->ev_fold_done)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->ev_launch)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->ev_in)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->ev_join)
-    if (e) (void)hipEventDestroy(e);
-  if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
-  for (auto& z : c->noise) (void)hipFree(z.d_thr);
-  for (auto& g : c->spec) (void)hipFree(g.d_sum);
-  (void)hipFree(c->d_spec_partial);
-  for (auto e : c->prof_events) (void)hipEventDestroy(e);
-  (void)hipFree(c->d_win);
-  (void)hipFree(c->d_tw);
-  (void)hipFree(c->d_tw8k);
-  (void)hipFree(c->d_pass);
-  (void)hipFree(c->d_rel);
-  (void)hipFree(c->d_tw8v2);
-  (void)hipFree(c->d_dif8_tab);
-  (void)hipFree(c->d_perm_tmp);
-  (void)hipFree(c->diag.d_stamps);
-  for (auto& t : c->order_tables) (void)hipFree(t.d);
-  (void)hipFree(c->d_hist);
-  for (auto p : c->d_cnt3) (void)hipFree(p);
-  for (auto p : c->d_mask2) (void)hipFree(p);
-  for (auto p : c->d_avg2) (void)hipFree(p);
-  for (auto p : c->d_off4) (void)hipFree(p);
-  for (auto p : c->d_psd2) (void)hipFree(p);
-  for (auto p : c->d_segsum) (void)hipFree(p);
-  for (auto p : c->d_live) (void)hipFree(p);
-  for (auto p : c->d_tlist) (void)hipFree(p);
-  (void)hipFree(c->diag.d_canary);
-  if (c->diag.ev_canary) (void)hipEventDestroy(c->diag.ev_canary);
-  (void)hipFree(c->d_smax);
-  for (auto p : c->d_halo) (void)hipFree(p);
-  (void)hipFree(c->d_relplane);
-  (void)hipFree(c->d_hist_tmp);
-  (void)hipFree(c->d_avgy);
-  (void)hipFree(c->d_work);
-  (void)hipFree(c->d_tw256);
-  (void)hipFree(c->d_tw_cols);
-  (void)hipFree(c->d_zero_row);
-  (void)hipFree(c->d_win1024);
-  (void)hipFree(c->d_wtab1024);
-  (void)hipFree(c->d_work2);
-  (void)hipFree(c->d_tw_sub);
-  (void)hipFree(c->d_tw_small);
-  (void)hipFree(c->d_tw_rowsR);
-  (void)hipFree(c->d_spec_ring);
-  (void)hipFree(c->d_spec_part2[0]);
-  (void)hipFree(c->d_spec_part2[1]);
-  (void)hipFree(c->d_counts);
-  (void)hipFree(c->d_stats);
-  (void)hipFree(c->d_nf);
-  (void)hipFree(c->d_bad_from);
-  (void)hipFree(c->d_nan_state);
-  for (hipEvent_t e : c->ev_call)
-    if (e) (void)hipEventDestroy(e);
-  (void)hipFree(c->d_in);
-  (void)hipFree(c->d_cand_idx);
-  (void)hipFree(c->d_cand_avg);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  std::vector<float2> tw((size_t)n);
+  for (int k = 0; k < n; ++k) tw[(size_t)k] = unit_root((double)k, (double)n);
+  made.upload(c->d_win, win).upload(c->d_tw, tw);
+  if (c->tw256) made.upload(c->d_tw256, w256_table());
+  if (c->tw_small) made.upload(c->d_tw_small, radix_table(n / 256, (double)n));
+  const int n2size = n / 256;
+  if (c->tw_cols && c->two_pass) {  // one block of tables for both halves (fft1024_kernels.h), in the place of the 256-point column tiles' tables
+    std::vector<float2> tab((size_t)ss::kFft1024TableEntries);
+    ss::fft1024_host_tables(tab.data());
+    made.upload(c->d_tw_cols, tab);
+  } else if (c->tw_cols) {
+    std::vector<float2> tc((size_t)32 * (size_t)n2size);
+    for (int i = 0; i < 16; ++i)
+      for (int n2 = 0; n2 < n2size; ++n2) {
+        tc[(size_t)i * n2size + n2] = unit_root((double)n2 * i, (double)n);
+        tc[(size_t)(16 + i) * n2size + n2] = unit_root(16.0 * (double)n2 * i, (double)n);
+      }
+    made.upload(c->d_tw_cols, tc);
+  }
+  if (c->tw_rowsR) made.upload(c->d_tw_rowsR, radix_table(n2size / 256, (double)n2size));
+  if (c->tw_sub) made.upload(c->d_tw_sub, radix_table(n2size / 256, (double)n2size));
+  if (c->tw8k) {
+    std::vector<float2> t8 = w256_table();
+    t8.resize((size_t)(256 + 1024 + 2048));
+    for (int r1 = 0; r1 < 4; ++r1)
+      for (int t = 0; t < 256; ++t) t8[(size_t)(256 + r1 * 256 + t)] = unit_root((double)t * r1, 8192.0);
+    for (int r2 = 0; r2 < 8; ++r2)
+      for (int t = 0; t < 256; ++t) t8[(size_t)(256 + 1024 + r2 * 256 + t)] = unit_root((double)t * r2, 2048.0);
+    made.upload(c->d_tw8k, t8);
+  }
+  if (c->tw8v2) made.upload(c->d_tw8v2, fft8192_v2_table());
+  if (c->win1024) {  // the same taps in the 1024-point column tiles' own order (fft1024_kernels.h)
+    std::vector<float> wk((size_t)n);
+    ss::fft1024_window_order(win.data(), wk.data(), 4);
+    made.upload(c->d_win1024, wk);
+  }
+  if (c->wtab) {  // the default window: the column tiles form their Hamming taps (2^20 points: fft1024_kernels.h; 65536: fft256_kernels.h)
+    std::vector<float2> wt(c->two_pass ? 65536 : 4096);
+    if (c->two_pass) ss::fft1024_window_rotation_table(wt.data());
+    else ss::fft65536_window_rotation_table(wt.data());
+    made.upload(c->d_wtab1024, wt);
+  }
+  if (c->dif8_tab) {  // the radix-8 fold's own tables
+    std::vector<float2> dt((size_t)ss::dif_table_float2(1 << c->dif_logq));
+    ss::dif8_host_tables(dt.data(), (double)c->cfg.int_scale, 1 << c->dif_logq);  // (the scale load_iq multiplies with in the other front ends)
+    made.upload(c->d_dif8_tab, dt);
+  }
 }
 
 }  // namespace
+
+// What going away takes beyond freeing, which the members do themselves: nothing of the context may still be running.
+ss_ctx::~ss_ctx() {
+  (void)hipSetDevice(cfg.device_id);
+  for (hipStream_t q : s_ab)
+    if (q) (void)hipStreamSynchronize(q);
+  if (s_fold) (void)hipStreamSynchronize(s_fold);
+  if (stream) (void)hipStreamSynchronize(stream);
+#ifdef SS_DIAG
+  if (d_cull_stats) {
+    unsigned h[3] = {0, 0, 0};
+    if (hipMemcpy(h, d_cull_stats, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess)
+      fprintf(stderr, "[specscan diag] detect tiles %u, on the culling path %u, culled %u\n", h[0], h[1], h[2]);
+  }
+#endif
+}
 
 // exhaustive check of div_const<21> (detect_fused.h) against the hardware IEEE division
 __global__ void k_selftest_div21(unsigned long long* mismatches) {
@@ -2385,13 +2185,12 @@ extern "C" {
 long long ss_selftest(int device_id, int which) {
   if (which != 0) return SS_ERR_INVALID;
   if (hipSetDevice(device_id) != hipSuccess) return SS_ERR_NO_DEVICE;
-  unsigned long long* d = nullptr;
+  ss::device_buffer<unsigned long long> d;
   unsigned long long h = 0;
-  if (hipMalloc(&d, sizeof(h)) != hipSuccess) return SS_ERR_HIP;
+  if (d.alloc(1) != hipSuccess) return SS_ERR_HIP;
   (void)hipMemset(d, 0, sizeof(h));
-  hipLaunchKernelGGL(k_selftest_div21, dim3(256 * 8), dim3(256), 0, 0, d);
+  hipLaunchKernelGGL(k_selftest_div21, dim3(256 * 8), dim3(256), 0, 0, d.get());
   const hipError_t e = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   return e == hipSuccess ? (long long)h : (long long)SS_ERR_HIP;
 }
 
@@ -2436,374 +2235,52 @@ int ss_create(const ss_config* cfg, ss_ctx** out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, SS_ERR_NO_DEVICE, "no HIP device available");
   if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(nullptr, SS_ERR_NO_DEVICE, "device_id %d out of range (%d devices)", cfg->device_id, ndev);
 
+  Diag diag;
+  diag.read();
+  ScanForm form;
+  if (decide_form(*cfg, diag, form, g_create_err) != SS_OK) return SS_ERR_INVALID;
+
   ss_ctx* c = new (std::nothrow) ss_ctx();
   if (!c) return fail(nullptr, SS_ERR_NOMEM, "out of host memory");
+  static_cast<ScanForm&>(*c) = form;
+  c->diag = diag;
   c->cfg = *cfg;
   c->cfg.window = nullptr;
   c->cfg.ignored = nullptr;
-  c->n = cfg->fft_size;
   c->db_off = (float)(10.0 * log10((double)cfg->sample_rate));
-  while ((1 << c->logn) < c->n) ++c->logn;
   c->range_lo = cfg->range_lo;
   c->range_hi = cfg->range_hi;
   c->ignored.assign(cfg->ignored, cfg->ignored + 2 * (size_t)cfg->n_ignored);
   if (c->cfg.int_scale == 0.0f) c->cfg.int_scale = cfg->in_format == SS_FMT_CU8 ? 1.0f / 127.5f : cfg->in_format == SS_FMT_CS16 ? 1.0f / 32768.0f : 1.0f / 128.0f;
+  c->abs_frames = c->clean_abs = diag.abs_start;
+  if (diag.wait_limit > 0) c->wait_limit = diag.wait_limit;
+  for (auto& b : c->slot_batch) b = -1;
 
-  const int n = c->n;
-  const int G = cfg->grouping_y;
-  const size_t plane = sizeof(float) * (size_t)n * (size_t)cfg->max_batch;
-#define CREATE_HIP(call)                                                                      \
-  do {                                                                                        \
-    hipError_t e_ = (call);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      fail(nullptr, SS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));               \
-      free_ctx(c);                                                                            \
-      return SS_ERR_HIP;                                                                      \
-    }                                                                                         \
-  } while (0)
-  CREATE_HIP(hipSetDevice(cfg->device_id));
-  CREATE_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  CREATE_HIP(hipMalloc(&c->d_win, sizeof(float) * (size_t)n));
-  CREATE_HIP(hipMalloc(&c->d_tw, sizeof(float2) * (size_t)n));
-  CREATE_HIP(hipMalloc(&c->d_pass, (size_t)n));
-  c->diag.read();
-  c->abs_frames = c->clean_abs = c->diag.abs_start;
-  c->fused = G == 21 && cfg->grouping_x == 21 && cfg->max_batch <= 65536 && !c->diag.backend_unfused;
-  // 8192 points (and the four-step sizes) with the fused back end: stages of consecutive calls overlap (scan_step.h), so
-  // what a deferred stage reads rotates over several buffers; every other configuration uses set 0 only
-  c->step_path = c->fused && !c->diag.fft_generic && (n == 8192 || (n >= 16384 && c->diag.step_long));
-  if (cfg->flags & SS_FLAG_SPECTROGRAM) {
-    // output size rule of the Spectrogram block: min(SPECTROGRAM_MAX_FFT, getFft(fs, SPECTROGRAM_PREFERRED_MAX_STEP)),
-    // sources/radio/blocks/spectrogram.cpp:14, config.h:36-37
-    int out_n = get_fft(cfg->sample_rate, 1000);
-    if (out_n > 16384) out_n = 16384;
-    if (out_n > n) out_n = n;
-    c->spec_n = out_n;
-    c->spec_m = n / out_n;
-    // inside the detect kernel when that kernel runs and a tile's 256 bins hold whole groups of m: one partial row per
-    // frame tile (a batch that starts inside a tile touches one more)
-    c->spec_in_detect = c->fused && c->spec_m <= 256 && !c->diag.spec_standalone;
-  }
-  c->ref_nan = (cfg->flags & SS_FLAG_REFERENCE_NAN) != 0;
-  if (c->ref_nan && !c->fused) {
-    fail(nullptr, SS_ERR_INVALID, "SS_FLAG_REFERENCE_NAN needs the 21 x 21 grouping (and max_batch <= 65536)");
-    free_ctx(c);
-    return SS_ERR_INVALID;
-  }
-  c->deep = c->step_path && n == 8192 && c->diag.deep && !(cfg->flags & (SS_FLAG_STREAM_ORDERED | SS_FLAG_REFERENCE_NAN)) && cfg->max_batch >= kHistRows && (!(cfg->flags & SS_FLAG_SPECTROGRAM) || c->spec_in_detect);
-  if (c->diag.wait_limit > 0) c->wait_limit = c->diag.wait_limit;
-  CREATE_HIP(hipMalloc(&c->d_stats, sizeof(unsigned long long) * ss::kStatShards * ss::kStatShardStride));
-  CREATE_HIP(hipMemsetAsync(c->d_stats, 0, sizeof(unsigned long long) * ss::kStatShards * ss::kStatShardStride, c->stream));
-  if (c->ref_nan) {
-    CREATE_HIP(hipMalloc(&c->d_nf, sizeof(int) * 4 * (size_t)cfg->max_batch));
-    CREATE_HIP(hipMalloc(&c->d_bad_from, sizeof(int) * (size_t)cfg->max_batch));
-    CREATE_HIP(hipMalloc(&c->d_nan_state, sizeof(ss::NanState)));
-    hipLaunchKernelGGL(ss::k_nan_state_reset, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<ss::NanState*>(c->d_nan_state), n);
-  }
-  c->nq = c->deep ? std::min(std::max(c->diag.queues, 2), kMaxQueues) : 1;
-  // 65536 points with tile culling: a call's detect stage rides two calls later (ss_ctx::det_lag2) — decided here, where the rotating
-  // buffers are sized: two more sets than launches in order need
-  // (131072 points — what getFft picks at 20 MS/s — have the pipeline of 65536 points where the fold can run at all: int8 IQ, default window)
-  const bool fold_ok = c->diag.dif8 && c->diag.emit_wide && c->diag.ring_only && (cfg->in_format == SS_FMT_CS8 || cfg->in_format == SS_FMT_CU8) && !cfg->window &&
-                       !(cfg->flags & (SS_FLAG_STREAM_ORDERED | SS_FLAG_REFERENCE_NAN | SS_FLAG_KEEP_PLANES | SS_FLAG_SPECTROGRAM));
-  const bool x256_ok = n == 262144 && c->diag.rows1024x256 && c->diag.emit_wide && c->diag.fft_rows_r < 0 && c->diag.fft_sub < 0 && !(cfg->flags & SS_FLAG_SPECTROGRAM);
-  c->plan_all = (cfg->flags & SS_FLAG_NO_CULL) && fold_ok && (n == 65536 || n == 131072);  // (see ss_ctx::plan_all)
-  const bool no_cull = (cfg->flags & SS_FLAG_NO_CULL) && !c->plan_all;
-  c->det_lag2 = !c->deep && c->step_path && (n == 65536 || (n == 131072 && fold_ok) || x256_ok) && !c->diag.fft_generic && c->diag.cull_65536 && c->diag.cull && !no_cull &&
-                c->diag.rows256_step && c->diag.step_long && c->diag.det_lag2 && c->fused;
-  c->merge = c->det_lag2 && (n == 65536 || x256_ok) && c->diag.merge_65536 && c->diag.emit_wide;  // (one launch per call: scan_step.h KIND 7 / KIND 12, whose emit role is the wide one)
-  c->merge_max = std::max(1, (int)((long long)c->diag.merge_max_frames * 65536 / n));  // (128 frames of 65536 points, 32 of 262144: 64 MiB of work buffer either way)
-  // ... and with int8 IQ and the default window no work buffer at all: the radix-8 fold (scan_step.h KIND 8). It takes every call the
-  // one-launch form above would take — and longer ones — so that form is off then.
-  c->dif8 = c->det_lag2 && fold_ok && (n == 65536 || n == 131072);
-  c->dif_logq = n == 131072 ? 4 : 3;
-  c->cull_fold_only = c->dif8 && n == 131072;
-  if (c->dif8) c->merge = false;
-  c->lag = c->deep ? c->nq : (c->det_lag2 ? 2 : 1);
-  c->ncnt = c->deep ? 3 * c->nq : (c->merge ? 8 : c->det_lag2 ? 6 : 3);
-  c->nbuf = c->deep ? 2 * c->nq : (c->merge ? 6 : c->det_lag2 ? 4 : (c->step_path ? 2 : 1));
-  c->npsd = c->deep ? 2 * c->nq : (c->step_path ? 2 : 1);  // (deep: written by launch L, read by launch L + nq, written again by launch L + 2 nq on the same queue)
-  if (c->fused) {
-    {
-      // ring capacity: at least three windows (a long batch needs a free one next to the one it reads), more when rows
-      // are small, so that short batches slide for a long time before the window is moved back to the front
-      // (the window slides by a batch's frames; when it reaches the end, kHistRows rows are copied back to the front:
-      // 147 MB for 2^20-point rows, so long rows get at least ten windows — one copy per ~20 sixteen-frame batches)
-      long long rows = (64ll << 20) / ((long long)n * 4);
-      const long long min_rows = (long long)n >= 65536 ? 10 * kHistRows : 3 * kHistRows;
-      if (rows < min_rows) rows = min_rows;
-      if (rows > 64 * kHistRows) rows = 64 * kHistRows;
-      // (round 6: long transforms on the step path get 1024 rows — 1 GiB at 262144 points, 4 GiB at 2^20: a call shorter than the window
-      // slides it along the buffer, and every return to the front is a drain of the stages that still read the old place; with 350 rows
-      // 32-frame calls of 262144 points drained every eighth call, 74 us each: 9.6 of their 63 us per call, profiles/r06/s7_summary.txt;
-      // 16-frame calls of 2^20 points every thirteenth. HBM is what this chip has most of.)
-      if (c->step_path && n >= 65536 && rows < 1024) rows = 1024;
-      // (long transforms, whose rows kernel may write ALL of a batch's rows into this buffer: three batches and the averager's reach,
-      // so that a batch can go back to the front of the buffer while the one before it is still to be read — ring_place.h)
-      if (n >= 65536 && c->step_path && rows < 3ll * cfg->max_batch + 3 * kHistRows) rows = 3ll * cfg->max_batch + 3 * kHistRows;
-      if ((c->merge || c->dif8) && rows < 4ll * (cfg->max_batch + kHistRows)) rows = 4ll * (cfg->max_batch + kHistRows);  // (two spans to protect: ring_place.h)
-      c->hist_rows = (int)rows;
-      CREATE_HIP(hipMalloc(&c->d_hist, sizeof(float) * (size_t)n * (size_t)rows));
-      CREATE_HIP(hipMemsetAsync(c->d_hist, 0, sizeof(float) * (size_t)n * (size_t)kHistRows, c->stream));  // Averager ctor, averager.cpp:7-12
-    }
-    for (int k = 0; k < c->ncnt; ++k) {
-      CREATE_HIP(hipMalloc(&c->d_cnt3[k], sizeof(int) * (size_t)cfg->max_batch));
-      CREATE_HIP(hipMemsetAsync(c->d_cnt3[k], 0, sizeof(int) * (size_t)cfg->max_batch, c->stream));
-    }
-  } else {
-    CREATE_HIP(hipMalloc(&c->d_rel, sizeof(float) * (size_t)n * (size_t)(G - 1 + cfg->max_batch)));
-    CREATE_HIP(hipMalloc(&c->d_hist_tmp, sizeof(float) * (size_t)n * (size_t)(G > 1 ? G - 1 : 1)));
-    CREATE_HIP(hipMalloc(&c->d_avgy, plane));
-    CREATE_HIP(hipMemsetAsync(c->d_rel, 0, sizeof(float) * (size_t)n * (size_t)(G - 1 + cfg->max_batch), c->stream));
-  }
-  for (int k = 0; k < c->npsd; ++k) CREATE_HIP(hipMalloc(&c->d_psd2[k], plane));
-  for (int k = 0; k < c->nbuf; ++k) {
-    CREATE_HIP(hipMalloc(&c->d_avg2[k], plane));
-    CREATE_HIP(hipMalloc(&c->d_mask2[k], sizeof(uint32_t) * (size_t)(n / 32) * (size_t)cfg->max_batch));
-    CREATE_HIP(hipMemsetAsync(c->d_mask2[k], 0, sizeof(uint32_t) * (size_t)(n / 32) * (size_t)cfg->max_batch, c->stream));  // (tile culling relies on it: EmitArgs::clear_masks)
-    CREATE_HIP(hipMalloc(&c->d_off4[k], sizeof(int) * ((size_t)cfg->max_batch + 1)));
-  }
+  ss::hip_steps made;
+  made.then([&] { return hipSetDevice(cfg->device_id); }, "hipSetDevice");
+  alloc_ctx_buffers(*c, form, *cfg, diag.canary, made);
   c->d_off = c->d_off4[0];
-  c->cull = c->fused && n == 8192 && !c->diag.fft_generic && !(cfg->flags & SS_FLAG_NO_CULL) && c->diag.cull;
-  if (c->cull)
-    for (int k = 0; k < c->nbuf; ++k) {
-      CREATE_HIP(hipMalloc(&c->d_segsum[k], sizeof(float) * 32 * (size_t)cfg->max_batch));
-      static_assert(ss::kLiveHeader + ss::kLiveLists * ss::kLiveCap <= ss::kLiveCounts, "the lists end before the count copies");
-      const size_t live_ints = ss::kLiveInts;
-      CREATE_HIP(hipMalloc(&c->d_live[k], sizeof(int) * live_ints));
-      CREATE_HIP(hipMemsetAsync(c->d_live[k], 0, sizeof(int) * live_ints, c->stream));
-    }
-  if (c->deep) {
-#ifdef SS_DIAG
-    if (c->diag.canary) {
-      CREATE_HIP(hipMalloc(&c->diag.d_canary, sizeof(unsigned long long) * 128));
-      CREATE_HIP(hipMemset(c->diag.d_canary, 0, sizeof(unsigned long long) * 128));
-      CREATE_HIP(hipEventCreateWithFlags(&c->diag.ev_canary, hipEventDisableTiming));
-    }
-#endif
-    c->deep_ring_safe = c->hist_rows / kHistRows >= kDeepSyncPhase + 8;
-    for (int k = 0; k < c->nq; ++k) CREATE_HIP(hipStreamCreateWithFlags(&c->s_ab[k], hipStreamNonBlocking));
-    for (int k = 0; k < 2 * c->nq; ++k)  // (+ the halo frames' per-column maxima behind their rows: halo_segsum_of)
-      CREATE_HIP(hipMalloc(&c->d_halo[k], sizeof(float) * ((size_t)n * (size_t)kHistRows + 32 * (size_t)ss::kHaloSegPitch)));
-    for (auto& e : c->ev_launch) CREATE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : c->ev_in) CREATE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : c->ev_join) CREATE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    CREATE_HIP(hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming));
+  if (c->ref_nan && made.ok()) hipLaunchKernelGGL(ss::k_nan_state_reset, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<ss::NanState*>(c->d_nan_state.get()), c->n);
+  if (diag.cull_stats) made.alloc(c->d_cull_stats, 3).then([&] { return hipMemset(c->d_cull_stats, 0, 3 * sizeof(unsigned)); }, "hipMemset");
+  if (c->step_path)
+    made.then([&] {
+      hipDeviceProp_t prop;
+      const hipError_t e = hipGetDeviceProperties(&prop, cfg->device_id);
+      if (e == hipSuccess) c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+      return e;
+    }, "hipGetDeviceProperties");
+  upload_tables(c, cfg->window, made);
+  // 64 KiB of dynamic LDS needs no opt-in on gfx950 (160 KiB/CU)
+  made.then([&] { return hipStreamSynchronize(c->stream); }, "hipStreamSynchronize");
+  if (!made.ok()) {
+    delete c;
+    return fail(nullptr, SS_ERR_HIP, "%s failed: %s", made.what(), hipGetErrorString(made.error()));
   }
-  if (c->step_path) {
-    hipDeviceProp_t prop;
-    CREATE_HIP(hipGetDeviceProperties(&prop, cfg->device_id));
-    c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    const size_t max_items = (size_t)(cfg->max_batch + kHistRows) * (size_t)(n / 8192) + ((size_t)cfg->max_batch / kFusedTF + 2) * (size_t)(n / 256) / 2 + (size_t)cfg->max_batch + 4 +
-                             (n >= 65536 ? (size_t)cfg->max_batch * (size_t)(n / 8192) + 512 : 0) +  // (one launch per call: the row tiles of the call before, the plan workgroups)
-                             (size_t)ss::kLiveLists * (ss::kLiveCap / 2 + 1);  // (a planned detect stage without an FFT role: 256 consumers per list, + the plan workgroups)
-    c->order_capacity = max_items;
-    c->order_tables.resize(16);
-    for (auto& t : c->order_tables) {
-      t.used = 0;
-      t.d = nullptr;
-      CREATE_HIP(hipMalloc(&t.d, sizeof(uint32_t) * c->order_capacity));
-    }
-  }
-  CREATE_HIP(hipMalloc(&c->d_counts, sizeof(int) * (size_t)cfg->max_batch));
-  if (cfg->flags & SS_FLAG_SPECTROGRAM) {
-    const int out_n = c->spec_n;
-    if (c->spec_in_detect) {
-      const size_t tiles = (size_t)(cfg->max_batch + kFusedTF - 1) / kFusedTF + 1;
-      for (int k = 0; k < 2; ++k) CREATE_HIP(hipMalloc(&c->d_spec_part2[k], sizeof(float) * (size_t)out_n * tiles));
-      if (c->deep) {  // one slot of partial sums per call in flight or not yet added to its container (ss_ctx::deep_folds)
-        c->spec_slot_floats = (size_t)out_n * tiles;
-        CREATE_HIP(hipMalloc(&c->d_spec_ring, sizeof(float) * c->spec_slot_floats * (size_t)kDeepSpecSlots));
-        CREATE_HIP(hipStreamCreateWithFlags(&c->s_fold, hipStreamNonBlocking));
-        for (auto& e : c->ev_fold_src) CREATE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto& e : c->ev_fold_done) CREATE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto& b : c->slot_batch) b = -1;
-      }
-    } else {
-      CREATE_HIP(hipMalloc(&c->d_spec_partial, sizeof(float) * (size_t)out_n * ((size_t)(cfg->max_batch + 31) / 32)));
-    }
-  }
-  if (c->logn > 13) CREATE_HIP(hipMalloc(&c->d_work, sizeof(float2) * (size_t)n * (size_t)cfg->max_batch));
-  // (the one-launch form only takes calls of up to merge_max_frames: the second work buffer need not hold more)
-  if (c->merge) CREATE_HIP(hipMalloc(&c->d_work2, sizeof(float2) * (size_t)n * (size_t)std::min(cfg->max_batch, c->merge_max)));
-
-  // window: caller's taps or gr::fft::window::hamming(N) (sdr_device.cpp:164; GNU Radio's definition:
-  // 0.54 - 0.46*cos(2*pi*n/(N-1)) in double, stored as float). Twiddles W_N^k from double.
-  {
-    std::vector<float> win((size_t)n);
-    if (cfg->window) {
-      memcpy(win.data(), cfg->window, sizeof(float) * (size_t)n);
-    } else {
-      const float M = (float)(n - 1);
-      for (int i = 0; i < n; ++i) win[(size_t)i] = (float)(0.54 - 0.46 * cos((2.0 * M_PI * i) / M));
-    }
-    std::vector<float2> tw((size_t)n);
-    for (int k = 0; k < n; ++k) {
-      const double ang = -2.0 * M_PI * (double)k / (double)n;
-      tw[(size_t)k] = make_float2((float)cos(ang), (float)sin(ang));
-    }
-    if ((n == 1024 || n == 2048 || n == 4096) && !c->diag.fft_generic) {
-      const int R = n / 256;
-      std::vector<float2> t256(256), tn((size_t)R * 256);
-      for (int r = 0; r < 16; ++r)
-        for (int m = 0; m < 16; ++m) {
-          const double ang = -2.0 * M_PI * (double)(m * r) / 256.0;
-          t256[(size_t)(r * 16 + m)] = make_float2((float)cos(ang), (float)sin(ang));
-        }
-      for (int q = 0; q < R; ++q)
-        for (int k = 0; k < 256; ++k) {
-          const double ang = -2.0 * M_PI * (double)(q * k) / (double)n;
-          tn[(size_t)(q * 256 + k)] = make_float2((float)cos(ang), (float)sin(ang));
-        }
-      CREATE_HIP(hipMalloc(&c->d_tw256, sizeof(float2) * t256.size()));
-      CREATE_HIP(hipMemcpy(c->d_tw256, t256.data(), sizeof(float2) * t256.size(), hipMemcpyHostToDevice));
-      CREATE_HIP(hipMalloc(&c->d_tw_small, sizeof(float2) * tn.size()));
-      CREATE_HIP(hipMemcpy(c->d_tw_small, tn.data(), sizeof(float2) * tn.size(), hipMemcpyHostToDevice));
-    }
-    if (n >= 16384) {
-      c->use_fft256 = !c->diag.fft_generic;
-      std::vector<float2> t256(256);
-      for (int r = 0; r < 16; ++r)
-        for (int m = 0; m < 16; ++m) {
-          const double ang = -2.0 * M_PI * (double)(m * r) / 256.0;
-          t256[(size_t)(r * 16 + m)] = make_float2((float)cos(ang), (float)sin(ang));
-        }
-      CREATE_HIP(hipMalloc(&c->d_tw256, sizeof(float2) * t256.size()));
-      CREATE_HIP(hipMemcpy(c->d_tw256, t256.data(), sizeof(float2) * t256.size(), hipMemcpyHostToDevice));
-      c->two_pass = c->use_fft256 && c->logn == 20 && c->diag.fft_twopass && c->diag.fft_rows_r < 0 && c->diag.fft_sub < 0;
-      if (c->two_pass) {  // one block of tables for both halves (fft1024_kernels.h), in the place of the 256-point column tiles' tables
-        std::vector<float2> tab((size_t)ss::kFft1024TableEntries);
-        ss::fft1024_host_tables(tab.data());
-        CREATE_HIP(hipMalloc(&c->d_tw_cols, sizeof(float2) * tab.size()));
-        CREATE_HIP(hipMemcpy(c->d_tw_cols, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
-      } else {
-        const int n2size = n / 256;
-        std::vector<float2> tc((size_t)32 * (size_t)n2size);
-        for (int i = 0; i < 16; ++i)
-          for (int n2 = 0; n2 < n2size; ++n2) {
-            const double a1 = -2.0 * M_PI * ((double)n2 * i) / (double)n, a2 = -2.0 * M_PI * (16.0 * (double)n2 * i) / (double)n;
-            tc[(size_t)i * n2size + n2] = make_float2((float)cos(a1), (float)sin(a1));
-            tc[(size_t)(16 + i) * n2size + n2] = make_float2((float)cos(a2), (float)sin(a2));
-          }
-        CREATE_HIP(hipMalloc(&c->d_tw_cols, sizeof(float2) * tc.size()));
-        CREATE_HIP(hipMemcpy(c->d_tw_cols, tc.data(), sizeof(float2) * tc.size(), hipMemcpyHostToDevice));
-        if (n2size >= 512 && n2size <= 4096 && (c->diag.fft_rows_r >= 0 ? c->diag.fft_rows_r == 1 : n2size <= 2048)) {  // 4096-point rows: a tie with the two-kernel form
-          const int R = n2size / 256;
-          std::vector<float2> tr((size_t)R * 256);
-          for (int q = 0; q < R; ++q)
-            for (int k = 0; k < 256; ++k) {
-              const double ang = -2.0 * M_PI * ((double)q * k) / (double)n2size;
-              tr[(size_t)q * 256 + k] = make_float2((float)cos(ang), (float)sin(ang));
-            }
-          CREATE_HIP(hipMalloc(&c->d_tw_rowsR, sizeof(float2) * tr.size()));
-          CREATE_HIP(hipMemcpy(c->d_tw_rowsR, tr.data(), sizeof(float2) * tr.size(), hipMemcpyHostToDevice));
-        }
-        if (n2size > 256 && !c->d_tw_rowsR && (c->diag.fft_sub >= 0 ? c->diag.fft_sub == 1 : n2size >= 2048)) {
-          const int A = n2size / 256;
-          std::vector<float2> ts((size_t)A * 256);
-          for (int cc = 0; cc < A; ++cc)
-            for (int b = 0; b < 256; ++b) {
-              const double ang = -2.0 * M_PI * ((double)b * cc) / (double)n2size;
-              ts[(size_t)cc * 256 + b] = make_float2((float)cos(ang), (float)sin(ang));
-            }
-          CREATE_HIP(hipMalloc(&c->d_tw_sub, sizeof(float2) * ts.size()));
-          CREATE_HIP(hipMemcpy(c->d_tw_sub, ts.data(), sizeof(float2) * ts.size(), hipMemcpyHostToDevice));
-        }
-      }
-    }
-    if (n == 8192) {
-      c->use_fft8192 = !c->diag.fft_generic;
-      std::vector<float2> t8((size_t)(256 + 1024 + 2048));
-      auto W = [](double num, double den) {
-        const double ang = -2.0 * M_PI * num / den;
-        return make_float2((float)cos(ang), (float)sin(ang));
-      };
-      for (int r = 0; r < 16; ++r)
-        for (int m = 0; m < 16; ++m) t8[(size_t)(r * 16 + m)] = W((double)m * r, 256.0);
-      for (int r1 = 0; r1 < 4; ++r1)
-        for (int t = 0; t < 256; ++t) t8[(size_t)(256 + r1 * 256 + t)] = W((double)t * r1, 8192.0);
-      for (int r2 = 0; r2 < 8; ++r2)
-        for (int t = 0; t < 256; ++t) t8[(size_t)(256 + 1024 + r2 * 256 + t)] = W((double)t * r2, 2048.0);
-      CREATE_HIP(hipMalloc(&c->d_tw8k, sizeof(float2) * t8.size()));
-      CREATE_HIP(hipMemcpy(c->d_tw8k, t8.data(), sizeof(float2) * t8.size(), hipMemcpyHostToDevice));
-      std::vector<float2> v2((size_t)(256 + 384 + 96));
-      ss::fft8192_v2_host_tables(v2.data(), v2.data() + 256, v2.data() + 256 + 384);
-      CREATE_HIP(hipMalloc(&c->d_tw8v2, sizeof(float2) * v2.size()));
-      CREATE_HIP(hipMemcpy(c->d_tw8v2, v2.data(), sizeof(float2) * v2.size(), hipMemcpyHostToDevice));
-    }
-    CREATE_HIP(hipMemcpy(c->d_win, win.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
-    if (c->two_pass) {  // the same taps in the 1024-point column tiles' own order (fft1024_kernels.h)
-      std::vector<float> wk((size_t)n);
-      ss::fft1024_window_order(win.data(), wk.data(), 4);
-      CREATE_HIP(hipMalloc(&c->d_win1024, sizeof(float) * (size_t)n));
-      CREATE_HIP(hipMemcpy(c->d_win1024, wk.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
-      if (!cfg->window && c->diag.win_calc) {  // the default window: Hamming taps formed in the kernel
-        std::vector<float2> wt(65536);
-        ss::fft1024_window_rotation_table(wt.data());
-        CREATE_HIP(hipMalloc(&c->d_wtab1024, sizeof(float2) * wt.size()));
-        CREATE_HIP(hipMemcpy(c->d_wtab1024, wt.data(), sizeof(float2) * wt.size(), hipMemcpyHostToDevice));
-      }
-    }
-    CREATE_HIP(hipMemcpy(c->d_tw, tw.data(), sizeof(float2) * (size_t)n, hipMemcpyHostToDevice));
-    if (n == 65536 && c->use_fft256 && !cfg->window && c->diag.win_calc) {  // the default window: the 256-point column tiles form their Hamming taps (fft256_kernels.h)
-      std::vector<float2> wt(4096);
-      ss::fft65536_window_rotation_table(wt.data());
-      CREATE_HIP(hipMalloc(&c->d_wtab1024, sizeof(float2) * wt.size()));
-      CREATE_HIP(hipMemcpy(c->d_wtab1024, wt.data(), sizeof(float2) * wt.size(), hipMemcpyHostToDevice));
-    }
-    if (c->dif8) {  // the radix-8 fold: its own tables and the 8192-point transform's
-      const double scale = (double)c->cfg.int_scale;  // (what load_iq multiplies with in the other front ends)
-      std::vector<float2> dt((size_t)ss::dif_table_float2(1 << c->dif_logq));
-      ss::dif8_host_tables(dt.data(), scale, 1 << c->dif_logq);
-      CREATE_HIP(hipMalloc(&c->d_dif8_tab, sizeof(float2) * dt.size()));
-      CREATE_HIP(hipMemcpy(c->d_dif8_tab, dt.data(), sizeof(float2) * dt.size(), hipMemcpyHostToDevice));
-      std::vector<float2> v2((size_t)(256 + 384 + 96));
-      ss::fft8192_v2_host_tables(v2.data(), v2.data() + 256, v2.data() + 256 + 384);
-      CREATE_HIP(hipMalloc(&c->d_tw8v2, sizeof(float2) * v2.size()));
-      CREATE_HIP(hipMemcpy(c->d_tw8v2, v2.data(), sizeof(float2) * v2.size(), hipMemcpyHostToDevice));
-      CREATE_HIP(hipMalloc(&c->d_perm_tmp, sizeof(float) * (size_t)n * (size_t)kHistRows));
-    }
-  }
-  // Tile culling for long transforms: the sizes whose rows go through k_fft_rows256_psd (N2 = 256, or the radix-A step in front)
-  // and the two-pass form of 2^20 points. On by default where it pays: 2^20 points. At 65536 points it takes 7 B/sample off the
-  // fabric and no time off the call: the column launch gets 10 us shorter, the plan launch costs 6.5 and the ring rows 1.4
-  // (57.4 against 56.9 us per 128-frame call now that detect-mode calls write no dB plane, run_batch: ring_only; 57.1 against
-  // 53.4 before; 38 against 29 us per 16-frame call either way: profiles/r04/s11_summary.txt, profiles/r03/s53_summary.txt).
-  // There only the diagnostics build switches it on (SS_CULL_65536=1; tests/test_gpu_cull.py keeps it honest).
-  c->x256_tile = n == 262144 && c->use_fft256 && c->d_tw_rowsR != nullptr && c->diag.rows1024x256 && c->diag.fft_rows_r < 0 && c->diag.fft_sub < 0;
-  c->rows1024x256 = c->det_lag2 && c->x256_tile;
-  c->cull_long = c->step_path && c->use_fft256 && ((n == 65536 && c->diag.cull_65536) || (n > 65536 && c->d_tw_sub && !c->d_tw_rowsR) || c->two_pass || c->cull_fold_only || c->rows1024x256) &&
-                 !no_cull && c->diag.cull;
-  if (!c->cull_long) c->rows1024x256 = false;
-  if (n == 262144 && !c->rows1024x256) c->merge = false;  // (never: decided from the same switches; the second work buffer and the rotating sets sized for it do no harm)
-  // 65536 points: with the plan of call k at the front of call k + 1's column launch — which therefore is a launch of its own, the
-  // row tiles taking the FFT role of k_scan_step in its place (KIND 6) — the culling pays there too (session 17 of round 4).
-  c->rows256_step = c->cull_long && !c->two_pass && c->logn == 16 && c->diag.rows256_step && c->diag.step_long;  // (no emit stage ever rides on the row launch — KIND 6, whose emit role is the wide one — but under SS_EMIT_ON_ROWS)
-  if (!c->rows256_step && !c->cull_fold_only && !c->rows1024x256) c->det_lag2 = false;  // (never: the two are decided from the same switches; the rotating buffers sized for it do no harm)
-  if (c->dif8 && !c->cull_long) c->dif8 = c->cull_fold_only = false;
-  if (c->cull_long) {
-    CREATE_HIP(hipMalloc(&c->d_zero_row, sizeof(float) * (size_t)n));  // (what a ring-only call's detect stage subtracts from rows that are noise-relative already)
-    CREATE_HIP(hipMemset(c->d_zero_row, 0, sizeof(float) * (size_t)n));
-    int rows = 64;
-    // (two batches and the averager's reach: the plan of call k — which reads the maxima of its frames and of the 35 before —
-    // runs beside the column tiles of call k + 1, which clear the rows of THEIR frames: k_fft_cols1024_plan)
-    // (262144 points in one launch per call: the column tiles of call k clear their frames' words while the plan of call k - 2 rides on the
-    // same launch: three batches)
-    while (rows < ((c->merge && c->rows1024x256) ? 3 : 2) * cfg->max_batch + kHistRows + 1) rows <<= 1;
-    c->smax_rows = rows;
-    CREATE_HIP(hipMalloc(&c->d_smax, sizeof(float) * (size_t)rows * (size_t)(n / 32)));
-    if (c->rows1024x256) CREATE_HIP(hipMemsetAsync(c->d_smax, 0, sizeof(float) * (size_t)rows * (size_t)(n / 32), c->stream));  // (keys: 0 = nothing seen)
-    const size_t max_tiles = ((size_t)cfg->max_batch / kFusedTF + 2) * (size_t)(n / 256);
-    for (int k = 0; k < std::max(2, c->nbuf); ++k) CREATE_HIP(hipMalloc(&c->d_tlist[k], sizeof(int) * (max_tiles + 2)));  // (count, entries, one slot behind an odd count)
-  }
-  // 64 KiB of dynamic LDS needs no opt-in on gfx950 (160 KiB/CU), but say so explicitly for clarity
-  CREATE_HIP(hipStreamSynchronize(c->stream));
-#undef CREATE_HIP
   *out = c;
   return SS_OK;
 }
 
-void ss_destroy(ss_ctx* ctx) { free_ctx(ctx); }
+void ss_destroy(ss_ctx* ctx) { delete ctx; }
 
 const char* ss_last_error(const ss_ctx* ctx) { return ctx ? ctx->err : g_create_err; }
 
@@ -2846,13 +2323,13 @@ int ss_sync(ss_ctx* ctx) {
 #ifdef SS_DIAG
   {
     std::lock_guard<std::mutex> lock(ctx->mtx);
-    if (ctx->diag.d_canary && !ctx->diag.canary_pairs.empty()) {
+    if (ctx->d_canary && !ctx->canary_pairs.empty()) {
       unsigned long long h[128];
-      SS_HIP(ctx, hipMemcpy(h, ctx->diag.d_canary, sizeof(h), hipMemcpyDeviceToHost));
+      SS_HIP(ctx, hipMemcpy(h, ctx->d_canary, sizeof(h), hipMemcpyDeviceToHost));
       int bad = -1;
-      for (int slot : ctx->diag.canary_pairs)
+      for (int slot : ctx->canary_pairs)
         if (h[2 * slot] != h[2 * slot + 1]) bad = slot;
-      ctx->diag.canary_pairs.clear();
+      ctx->canary_pairs.clear();
       if (bad >= 0)
         return fail(ctx, SS_ERR_INVALID, "input canary: the last frames of a call's d_iq changed before the next call's launch had read them again "
                                          "(every buffer of ss_process_device must stay untouched until ss_sync; SS_FLAG_STREAM_ORDERED lifts that)");
@@ -2896,8 +2373,8 @@ int ss_input_wait(ss_ctx* c, void* stream_v, int32_t calls_back) {
   hipStream_t stream = stream_v ? static_cast<hipStream_t>(stream_v) : c->stream;
   const auto behind_public = [&]() -> int {  // whatever the public stream holds now
     if (stream == c->stream) return SS_OK;
-    hipEvent_t& ev = c->ev_call[c->call_seq & 31];
-    if (!ev) SS_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    ss::hip_event& ev = c->ev_call[c->call_seq & 31];
+    if (!ev) SS_HIP(c, ev.create());
     SS_HIP(c, hipEventRecord(ev, c->stream));
     SS_HIP(c, hipStreamWaitEvent(stream, ev, 0));
     ++c->call_seq;
@@ -3021,7 +2498,7 @@ int ss_process(ss_ctx* c, const void* iq, int32_t nframes, const int64_t* t_ms, 
   const int n = c->n;
   const size_t bps = in_bytes_per_sample(c->cfg.in_format);
   const size_t row_bytes = (size_t)n * bps;
-  if (!c->d_in) SS_HIP(c, hipMalloc(&c->d_in, row_bytes * (size_t)c->cfg.max_batch));
+  if (!c->d_in) SS_HIP(c, c->d_in.alloc(row_bytes * (size_t)c->cfg.max_batch));
   lap("set device, input buffer");
   // Decimator: only the first N samples of each N*D item ever reach the GPU (decimator.h:15-22)
   // The caller's buffer is pageable (the scheduler's) and the call hands its results back before it returns: a synchronous copy — D = 1:
@@ -3033,13 +2510,10 @@ int ss_process(ss_ctx* c, const void* iq, int32_t nframes, const int64_t* t_ms, 
   else SS_HIP(c, hipMemcpy2D(c->d_in, row_bytes, iq, row_bytes * (size_t)c->cfg.decim, row_bytes, (size_t)nframes, hipMemcpyHostToDevice));
   lap("copy in");
   if (cand_cap > c->cand_cap_alloc) {
-    (void)hipFree(c->d_cand_idx);
-    (void)hipFree(c->d_cand_avg);
-    c->d_cand_idx = nullptr;
-    c->d_cand_avg = nullptr;
+    ss::reset_all(c->d_cand_idx, c->d_cand_avg);
     c->cand_cap_alloc = 0;
-    SS_HIP(c, hipMalloc(&c->d_cand_idx, sizeof(int) * (size_t)cand_cap));
-    SS_HIP(c, hipMalloc(&c->d_cand_avg, sizeof(float) * (size_t)cand_cap));
+    SS_HIP(c, c->d_cand_idx.alloc((size_t)cand_cap));
+    SS_HIP(c, c->d_cand_avg.alloc((size_t)cand_cap));
     c->cand_cap_alloc = cand_cap;
   }
   NoiseState* z = nullptr;
@@ -3049,7 +2523,7 @@ int ss_process(ss_ctx* c, const void* iq, int32_t nframes, const int64_t* t_ms, 
   const bool want_cands = cand_idx && cand_cap > 0;
   float* d_rel_plane = nullptr;
   if (c->fused && rel_db) {
-    if (!c->d_relplane) SS_HIP(c, hipMalloc(&c->d_relplane, sizeof(float) * (size_t)n * (size_t)c->cfg.max_batch));
+    if (!c->d_relplane) SS_HIP(c, c->d_relplane.alloc((size_t)n * (size_t)c->cfg.max_batch));
     d_rel_plane = c->d_relplane;
   }
   lap("noise state, buffers");
@@ -3119,7 +2593,7 @@ int ss_reset(ss_ctx* c) {  // Transmission::resetBuffers -> Averager::reset: row
   c->rot_frames = 0;
   c->last_n = 0;
   c->deep_iq_recycled = false;  // (a retune is a fresh start for the caller's buffers too; ss_get_stats keeps the count)
-  if (c->ref_nan) hipLaunchKernelGGL(ss::k_nan_state_reset, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<ss::NanState*>(c->d_nan_state), c->n);  // Averager::reset zeroes the sums: the poison goes with them
+  if (c->ref_nan) hipLaunchKernelGGL(ss::k_nan_state_reset, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<ss::NanState*>(c->d_nan_state.get()), c->n);  // Averager::reset zeroes the sums: the poison goes with them
   return SS_OK;
 }
 
@@ -3130,7 +2604,6 @@ int ss_reset_noise(ss_ctx* c) {
   flush_stages(c);
   settle_ring_db(c);  // (ring rows left as dB values: the ceiling they belong to goes away)
   SS_HIP(c, hipStreamSynchronize(c->stream));
-  for (auto& z : c->noise) (void)hipFree(z.d_thr);
   c->noise.clear();
   c->clean_abs = c->abs_frames;
   c->last_thr = nullptr;  // ss_read_window(SS_PLANE_REL) of the last batch has nothing to subtract any more
