@@ -1132,7 +1132,10 @@ __device__ __forceinline__ int tile_column_of(int pass_c, int tid) {
 // from ring_db_from on) —; calls that hand out no plane only (no rel_out). A tile's thread g * 32 + j takes the bin 8 j + g: a wave's 36
 // row loads are 256 contiguous bytes (Q = 8) or four runs of 64 (Q = 16); everything else — the noise ceiling, the pass mask, mask bits,
 // sparse averages — stays in bin order.
-template <int G, int GX, int TF, int TB_ = 256, bool SPEC = false, int PERM8 = 0>
+// ONE_FLIGHT (the fold's rows only; true wherever the scan runs the tile): a thread's two columns in one flight of loads, 124 VGPRs.
+// false: the two passes of the paths for rows in bin order, on the fold's addresses — the same arithmetic on the same values in 62 VGPRs,
+// for a launch of tiles alone that nothing waits for (track_digest_sparse.h: k_digest_tiles).
+template <int G, int GX, int TF, int TB_ = 256, bool SPEC = false, int PERM8 = 0, bool ONE_FLIGHT = true>
 __device__ __forceinline__ void detect_tile(const DetectArgs& a, int block, int tid, float* __restrict__ tile, int* __restrict__ cnt, bool valid) {
   using T = DetectTile<G, GX, TF, TB_>;
   constexpr int A = T::A, TB = T::TB, P = T::P, ROWS = T::ROWS, H = T::H, SEGW = T::SEGW, NSEG = T::NSEG, YW = T::YW;
@@ -1164,7 +1167,7 @@ __device__ __forceinline__ void detect_tile(const DetectArgs& a, int block, int 
   const bool writes_hist = f0 + TF > first_hist;
 
   // ---------------- phase 1: time means, thread = column ----------------
-  if constexpr (PERM8 != 0) {
+  if constexpr (PERM8 != 0 && ONE_FLIGHT) {
     // The fold's rows (KIND 8 / 9 of k_scan_step: 128 registers per thread). A pair of tiles holds a workgroup slot that a residue's
     // transform is waiting for, or ends the launch: what counts is how long ONE wave takes, and a wave issues an instruction every
     // four or five cycles — 1000 instructions are 2 us. Measured per tile, alone on the chip (profiles/r05/s29_*): first pass

@@ -53,10 +53,35 @@ ss::RelRows rel_rows(const ss_ctx* c, const digest_rows& r) {
   return rows;
 }
 
+// ... of a batch whose call left no dB plane (st_create_sparse): ss_ctx::last_rel_rows, in the averager ring's buffer (track_digest_sparse.h)
+ss::RingRows ring_rows(const ss_ctx* c, const digest_rows& r, int nframes) {
+  ss::RingRows rows{};
+  rows.rows = c->last_rel_rows;
+  rows.thr = c->last_thr;
+  rows.tail = r.d_tail[r.tail_cur].get();
+  rows.n = c->n;
+  rows.n_learn = c->last_n_learn;
+  rows.tail_rows = r.tail_rows;
+  rows.logq = c->last_rows_perm8 ? c->dif_logq : 0;
+  // Defence only: rows settled since the call (settle_ring_db, ss_read_window's last_settled_lo / hi) follow a retune or ss_reset_noise,
+  // and st_digest refuses both before it gets here (last_retunes; last_n = 0) — as things stand the range is empty and db_from / db_to
+  // say last_rows_db for the whole batch. Kept so that the kernels read the rows by ss_read_window's rule whatever settles them one day.
+  long long a = 0, b = 0;
+  if (c->last_settled_lo) {
+    a = (c->last_settled_lo - c->last_rel_rows) / (ptrdiff_t)c->n;
+    b = (c->last_settled_hi - c->last_rel_rows) / (ptrdiff_t)c->n;
+  }
+  const ss::RingDbRange db = ss::ring_db_range(nframes, c->last_rows_db, a, b);
+  rows.db_from = db.from;
+  rows.db_to = db.to;
+  return rows;
+}
+
 // the candidates' kernel over the last batch: lists on the device in, cand_best and cand_avg out
-void launch_cand_best(const ss_ctx* c, const digest_rows& r, const ss::RelRows& rows, int nframes, const int32_t* cand_off, const int32_t* cand_idx, int32_t* cand_best,
-                      float* cand_avg) {
-  ss::CandBestArgs a{};
+template <class Rows, class Kernel>
+void launch_cand_best_of(Kernel kernel, const ss_ctx* c, const digest_rows& r, const Rows& rows, int nframes, const int32_t* cand_off, const int32_t* cand_idx,
+                         int32_t* cand_best, float* cand_avg) {
+  ss::CandBestArgsOf<Rows> a{};
   a.rows = rows;
   a.avg = c->last_avg;
   a.cand_off = cand_off;
@@ -69,14 +94,26 @@ void launch_cand_best(const ss_ctx* c, const digest_rows& r, const ss::RelRows& 
   a.nrows = r.nrows;
   a.width = ss::kTrackTile + 2 * a.half;
   a.start_level = r.start_level;
-  hipLaunchKernelGGL(ss::k_best_blocked, dim3((unsigned)((size_t)nframes * a.tiles)), dim3(ss::kTrackTile), ss::blocked_lds_bytes(r.nrows, a.half), c->stream, a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((size_t)nframes * a.tiles)), dim3(ss::kTrackTile), ss::blocked_lds_bytes(r.nrows, a.half), c->stream, a);
+}
+void launch_cand_best(const ss_ctx* c, const digest_rows& r, const ss::RelRows& rows, int nframes, const int32_t* cand_off, const int32_t* cand_idx, int32_t* cand_best,
+                      float* cand_avg) {
+  launch_cand_best_of(ss::k_best_blocked, c, r, rows, nframes, cand_off, cand_idx, cand_best, cand_avg);
+}
+void launch_cand_best(const ss_ctx* c, const digest_rows& r, const ss::RingRows& rows, int nframes, const int32_t* cand_off, const int32_t* cand_idx, int32_t* cand_best,
+                      float* cand_avg) {
+  launch_cand_best_of(ss::k_ring_best, c, r, rows, nframes, cand_off, cand_idx, cand_best, cand_avg);
 }
 
 // the batch's last rows into the other tail; flip_tail makes it the current one
+unsigned save_tail_grid(const ss_ctx* c, const digest_rows& r) { return (unsigned)std::min<size_t>(((size_t)r.tail_rows * (size_t)c->n + 255) / 256, 1024); }
 void launch_save_tail(const ss_ctx* c, const digest_rows& r, const ss::RelRows& rows, int nframes) {
   if (r.tail_rows == 0) return;
-  const size_t total = (size_t)r.tail_rows * (size_t)c->n;
-  hipLaunchKernelGGL(ss::k_save_tail, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream, rows, nframes, r.d_tail[r.tail_cur ^ 1].get());
+  hipLaunchKernelGGL(ss::k_save_tail, dim3(save_tail_grid(c, r)), dim3(256), 0, c->stream, rows, nframes, r.d_tail[r.tail_cur ^ 1].get());
+}
+void launch_save_tail(const ss_ctx* c, const digest_rows& r, const ss::RingRows& rows, int nframes) {
+  if (r.tail_rows == 0) return;
+  hipLaunchKernelGGL(ss::k_ring_tail, dim3(save_tail_grid(c, r)), dim3(256), 0, c->stream, rows, nframes, r.d_tail[r.tail_cur ^ 1].get());
 }
 
 void flip_tail(digest_rows& r) {
@@ -98,6 +135,14 @@ struct SS_HIDDEN st_ctx {
   size_t cand_alloc = 0;  // elements of d_idx / d_best / d_cavg and their host twins (grown as needed, cfg.cand_cap at most)
   std::vector<int32_t> merged;  // the watch list being formed
   std::vector<uint8_t> mark;    // [n], all zero between digests
+  // st_create_sparse on a context that keeps no planes (include/specscan_track_digest_sparse.h, kernels: track_digest_sparse.h)
+  bool sparse = false;
+  int ncols = 0;                                         // ceil(n / 256): the tile columns
+  ss::device_buffer<uint32_t> d_sp_mask;                 // [(n / 32) x max_batch] the replayed tiles' mask words: never read
+  ss::device_buffer<int> d_sp_counts;                    // [max_batch] ... and their counts
+  ss::device_buffer<int32_t> d_col_flag;                 // [ncols] the tile columns the batch's watch windows touch
+  ss::device_buffer<unsigned long long> d_sp_evaluated;  // tiles the replay ran, since st_create_sparse / st_reset
+  uint64_t sp_tiles_in_batches = 0;
   char err[512] = "";
 };
 
@@ -134,15 +179,69 @@ int st_grow_peaks(st_ctx* t, size_t need) {
   return SS_OK;
 }
 
-}  // namespace
+// A sparse object, between the watch list and the peaks: avg in the tile columns the watch windows touch, by the batch's own detect
+// stage once more — stf_replay_watch_tiles' recipe (host_track_feed.h has the list of what is switched off and why) on ss_ctx::last_det,
+// with the tile of the form the batch took: its rows in bin order, or in the fold's order (scan_step.h: step_detect_layout).
+// What the replay reads, and why it is all still there: st_digest holds the context's lock and has run flush_stages — no stage waits,
+// nothing is in flight on the library's queues, and the next call, which is what moves the ring's window (place_ring), settles dB
+// rows in place (settle_ring_db), rewrites the window in the other order (set_ring_form), raises the ceiling or rotates the planes,
+// cannot start before the lock is released. So last_det's psd (the dB plane, or the rows a no-plane call left in the ring's buffer),
+// hist_in / halo_psd (the rows before the batch), thr and pass are as the batch's own tiles saw them. A retune or ss_reset_noise
+// since the batch settles rows too: st_digest has refused those already.
+bool last_det_is_the_batch(const ss_ctx* c, int nframes) {
+  const float* batch_rows = c->last_psd ? c->last_psd : c->last_rel_rows;
+  return c->last_det_ok && c->last_det.psd == batch_rows && c->last_det.nframes == nframes && c->last_det.n == c->n && c->last_det.avg_sparse == c->last_avg;
+}
 
-extern "C" {
+int st_replay_watch_tiles(st_ctx* t, int nframes, int nwatch) {
+  ss_ctx* c = t->scan;
+  const int n = c->n;
+  // (st_digest has checked last_det_is_the_batch before its first launch)
+  hipLaunchKernelGGL(ss::k_digest_cols, dim3(1), dim3(256), 0, c->stream, (const int32_t*)t->d_watch.get(), nwatch, n, t->rows.group_size / 2, t->d_col_flag.get());
+  ss::WatchTilesArgs wa{};
+  wa.det = c->last_det;
+  wa.det.maskbits = t->d_sp_mask.get();
+  wa.det.counts = t->d_sp_counts.get();
+  wa.det.rel_out = nullptr;
+  wa.det.avg_out = const_cast<float*>(c->last_avg);
+  wa.det.hist_out = nullptr;
+  wa.det.hist_by_fft = 1;
+  wa.det.segsum = nullptr;
+  wa.det.halo_segsum = nullptr;
+  wa.det.live = nullptr;
+  wa.det.tile_list = nullptr;
+  wa.det.stats = nullptr;
+  wa.det.spec_partial = nullptr;
+  wa.det.spec_prev_partial = nullptr;
+  wa.det.spec_prev_sum = nullptr;
+  wa.det.spec_prev_tiles = 0;
+  wa.det.spec_m = wa.det.spec_n = 0;
+#ifdef SS_DIAG
+  wa.det.stamp_mid = nullptr;
+  wa.det.cull_stats = nullptr;
+#endif
+  wa.col_flag = t->d_col_flag.get();
+  wa.evaluated = t->d_sp_evaluated.get();
+  const int frame_tiles = (nframes + wa.det.shift + kFusedTF - 1) / kFusedTF;
+  const dim3 grid((unsigned)(frame_tiles * t->ncols));
+  const int layout = c->last_rows_perm8 ? (c->dif_logq == 4 ? 4 : 3) : 0;
+  if (layout == 4) hipLaunchKernelGGL(ss::k_digest_tiles<4>, grid, dim3(256), 0, c->stream, wa);
+  else if (layout == 3) hipLaunchKernelGGL(ss::k_digest_tiles<3>, grid, dim3(256), 0, c->stream, wa);
+  else hipLaunchKernelGGL(ss::k_digest_tiles<0>, grid, dim3(256), 0, c->stream, wa);
+  return SS_OK;
+}
 
-int st_create(ss_ctx* scan, const st_config* cfg, st_ctx** out) {
+// st_create and st_create_sparse: allow_sparse = the context may lack SS_FLAG_KEEP_PLANES (the object is a sparse one if it does)
+int st_create_any(ss_ctx* scan, const st_config* cfg, st_ctx** out, bool allow_sparse) {
   if (create_args_refused(scan, cfg, out, ST_ABI_VERSION)) return SS_ERR_INVALID;
   if (cfg->group_size < 0 || cfg->max_watch <= 0 || cfg->cand_cap <= 0) return obj_fail<st_ctx>(nullptr, SS_ERR_INVALID, "group_size >= 0, max_watch > 0 and cand_cap > 0 required");
   std::lock_guard<std::mutex> lock(scan->mtx);
-  if (!(scan->cfg.flags & SS_FLAG_KEEP_PLANES)) return obj_fail<st_ctx>(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_KEEP_PLANES (the digest reads the kept dB and avg planes)");
+  const bool sparse = allow_sparse && !(scan->cfg.flags & SS_FLAG_KEEP_PLANES);
+  if (!allow_sparse && !(scan->cfg.flags & SS_FLAG_KEEP_PLANES)) return obj_fail<st_ctx>(nullptr, SS_ERR_INVALID, "the scan context needs SS_FLAG_KEEP_PLANES (the digest reads the kept dB and avg planes)");
+  if (sparse && !scan->fused)
+    return obj_fail<st_ctx>(nullptr, SS_ERR_INVALID, "sparse tracking needs the fused back end (grouping 21 x 21; this context has %d x %d): the unfused back end keeps no sparse avg plane",
+                            scan->cfg.grouping_x, scan->cfg.grouping_y);
+  if (sparse && scan->ref_nan) return obj_fail<st_ctx>(nullptr, SS_ERR_INVALID, "sparse tracking on a SS_FLAG_REFERENCE_NAN context: its NaN stage patches the planes behind the tiles");
   digest_rows rows;
   if (const int st = digest_rows_plan(rows, scan, cfg->group_size, cfg->start_level, create_err<st_ctx>()); st != SS_OK) return st;
   st_ctx* t = new (std::nothrow) st_ctx();
@@ -154,12 +253,53 @@ int st_create(ss_ctx* scan, const st_config* cfg, st_ctx** out) {
   const size_t frames = (size_t)scan->cfg.max_batch, mw = (size_t)cfg->max_watch;
   ss::hip_steps made;
   made.then([&] { return hipSetDevice(scan->cfg.device_id); }).then([&] { return tails_alloc(t->rows, scan); }).then([&] { return tails_zero(t->rows, scan); });
-  made.alloc(t->d_off, frames + 1).alloc(t->h_off, frames + 1).alloc(t->d_watch, mw).alloc(t->h_watch, mw).then([&] { return hipStreamSynchronize(scan->stream); });
+  made.alloc(t->d_off, frames + 1).alloc(t->h_off, frames + 1).alloc(t->d_watch, mw).alloc(t->h_watch, mw);
+  if (sparse) {
+    t->sparse = true;
+    t->ncols = (scan->n + ss::kWatchCol - 1) / ss::kWatchCol;
+    const size_t words = ((size_t)scan->n / 32) * frames, plane = sizeof(float) * (size_t)scan->n * frames, ncols = (size_t)t->ncols;
+    made.alloc(t->d_sp_mask, words).alloc(t->d_sp_counts, frames).alloc(t->d_col_flag, ncols).alloc(t->d_sp_evaluated, 1);
+    made.then([&] { return hipMemsetAsync(t->d_sp_mask.get(), 0, sizeof(uint32_t) * words, scan->stream); });
+    made.then([&] { return hipMemsetAsync(t->d_sp_counts.get(), 0, sizeof(int) * frames, scan->stream); });
+    made.then([&] { return hipMemsetAsync(t->d_col_flag.get(), 0, sizeof(int32_t) * ncols, scan->stream); });
+    made.then([&] { return hipMemsetAsync(t->d_sp_evaluated.get(), 0, sizeof(unsigned long long), scan->stream); });
+    // every sparse plane to NaN, once (all bytes 0xff), as stf_create_sparse does: a cell of a watch window the replay failed to write
+    // would be a NaN peak, not a plausible value some earlier batch left there
+    made.then([&] {
+      flush_stages(scan);
+      return hipSuccess;
+    });
+    for (int k = 0; k < scan->nbuf; ++k) made.then([&] { return hipMemsetAsync(scan->d_avg2[k], 0xff, plane, scan->stream); });
+  }
+  made.then([&] { return hipStreamSynchronize(scan->stream); });
   if (!made.ok()) {
     delete t;
     return obj_fail<st_ctx>(nullptr, SS_ERR_NOMEM, "allocating the digest's buffers failed: %s", hipGetErrorString(made.error()));
   }
   *out = t;
+  return SS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int st_create(ss_ctx* scan, const st_config* cfg, st_ctx** out) { return st_create_any(scan, cfg, out, false); }
+
+int st_create_sparse(ss_ctx* scan, const st_config* cfg, st_ctx** out) { return st_create_any(scan, cfg, out, true); }
+
+int st_sparse_stats(st_ctx* t, uint64_t* tiles_evaluated, uint64_t* tiles_in_batches) {
+  if (!t) return SS_ERR_INVALID;
+  if (!tiles_evaluated || !tiles_in_batches) return obj_fail(t, SS_ERR_INVALID, "null argument");
+  ss_ctx* c = t->scan;
+  std::lock_guard<std::mutex> lock(c->mtx);
+  if (!t->sparse) return obj_fail(t, SS_ERR_INVALID, "not a sparse object: the scan context keeps its planes (st_create, or st_create_sparse with SS_FLAG_KEEP_PLANES), nothing is replayed");
+  unsigned long long ev = 0;
+  ST_HIP(t, hipSetDevice(c->cfg.device_id));
+  ST_HIP(t, hipMemcpyAsync(&ev, t->d_sp_evaluated.get(), sizeof(ev), hipMemcpyDeviceToHost, c->stream));
+  ST_HIP(t, hipStreamSynchronize(c->stream));
+  *tiles_evaluated = ev;
+  *tiles_in_batches = t->sp_tiles_in_batches;
   return SS_OK;
 }
 
@@ -181,7 +321,9 @@ int st_reset(st_ctx* t) {
   std::lock_guard<std::mutex> lock(c->mtx);
   ST_HIP(t, hipSetDevice(c->cfg.device_id));
   ST_HIP(t, hipMemsetAsync(t->rows.d_tail[t->rows.tail_cur].get(), 0, sizeof(float) * tail_floats(t->rows, c), c->stream));
+  if (t->sparse) ST_HIP(t, hipMemsetAsync(t->d_sp_evaluated.get(), 0, sizeof(unsigned long long), c->stream));
   ST_HIP(t, hipStreamSynchronize(c->stream));
+  t->sp_tiles_in_batches = 0;
   t->seen_batch = c->batch_no;
   return SS_OK;
 }
@@ -197,7 +339,12 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
   if (c->batch_no != t->seen_batch + 1)
     return obj_fail(t, SS_ERR_INVALID, "%llu batches went by without st_digest: the kept rel rows are stale until st_reset", c->batch_no - t->seen_batch - 1);
   if (c->last_retunes != c->retunes) return obj_fail(t, SS_ERR_INVALID, "ss_set_frequency_range since the last batch: its noise ceiling is not the current one");
-  if (!c->last_avg || (c->fused && (!c->last_psd || !c->last_thr))) return obj_fail(t, SS_ERR_INVALID, "the last batch left no dB plane, avg plane or noise ceiling to digest");
+  // (a sparse object also digests a call that left no dB plane: its rows are in the averager ring's buffer, track_digest_sparse.h)
+  const bool ring_call = t->sparse && c->fused && !c->last_psd && c->last_rel_rows;
+  if (!c->last_avg || (c->fused && ((!c->last_psd && !ring_call) || !c->last_thr))) return obj_fail(t, SS_ERR_INVALID, "the last batch left no dB plane, avg plane or noise ceiling to digest");
+  // (defence only, see ring_rows: nothing settles rows between a call and its digest that is not refused above)
+  if (ring_call && c->last_settled_lo && c->last_settled_lo > c->last_rel_rows && c->last_settled_hi < c->last_rel_rows + (size_t)nframes * (size_t)n)
+    return obj_fail(t, SS_ERR_INVALID, "rows in the middle of the last batch were settled since it ran: nothing a call leaves looks like that");
   // the lists: offsets clipped to what the batch's call could write (SS_ERR_CAND_OVERFLOW leaves truncated lists), bins checked
   int32_t* const h_off = t->h_off.get();
   const int64_t cap = c->last_cand_cap > 0 ? c->last_cand_cap : 0;
@@ -223,12 +370,15 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
   for (int k = 0; k < nkeys; ++k)
     if (keys[k] < 0 || keys[k] >= n) return obj_fail(t, SS_ERR_INVALID, "key %d: bin %d outside [0, %d)", k, keys[k], n);
   flush_stages(c);
-  const ss::RelRows rows = rel_rows(c, t->rows);
+  if (t->sparse && !last_det_is_the_batch(c, nframes)) return obj_fail(t, SS_ERR_INVALID, "sparse digest: the detect stage launched last is not this batch's");
+  const ss::RelRows rows = ring_call ? ss::RelRows{} : rel_rows(c, t->rows);  // one of the two sources
+  const ss::RingRows ring = ring_call ? ring_rows(c, t->rows, nframes) : ss::RingRows{};
   uint64_t d2h = 0;
   if (ncand > 0) {
     ST_HIP(t, hipMemcpyAsync(t->d_off.get(), h_off, sizeof(int32_t) * ((size_t)nframes + 1), hipMemcpyHostToDevice, c->stream));
     ST_HIP(t, hipMemcpyAsync(t->d_idx.get(), t->h_idx.get(), sizeof(int32_t) * (size_t)ncand, hipMemcpyHostToDevice, c->stream));
-    launch_cand_best(c, t->rows, rows, nframes, t->d_off.get(), t->d_idx.get(), t->d_best.get(), t->d_cavg.get());
+    if (ring_call) launch_cand_best(c, t->rows, ring, nframes, t->d_off.get(), t->d_idx.get(), t->d_best.get(), t->d_cavg.get());
+    else launch_cand_best(c, t->rows, rows, nframes, t->d_off.get(), t->d_idx.get(), t->d_best.get(), t->d_cavg.get());
     ST_HIP(t, hipGetLastError());
     ST_HIP(t, hipMemcpyAsync(t->h_best.get(), t->d_best.get(), sizeof(int32_t) * (size_t)ncand, hipMemcpyDeviceToHost, c->stream));
     ST_HIP(t, hipMemcpyAsync(t->h_cavg.get(), t->d_cavg.get(), sizeof(float) * (size_t)ncand, hipMemcpyDeviceToHost, c->stream));
@@ -260,6 +410,10 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
     if (st != SS_OK) return st;
     memcpy(t->h_watch.get(), w.data(), sizeof(int32_t) * (size_t)nwatch);
     ST_HIP(t, hipMemcpyAsync(t->d_watch.get(), t->h_watch.get(), sizeof(int32_t) * (size_t)nwatch, hipMemcpyHostToDevice, c->stream));
+    if (t->sparse) {  // avg where the windows lie: nothing but the tiles with hits has written the sparse plane
+      const int st_replay = st_replay_watch_tiles(t, nframes, nwatch);
+      if (st_replay != SS_OK) return st_replay;
+    }
     ss::WindowPeaksArgs p{};
     p.avg = c->last_avg;
     p.watch = t->d_watch.get();
@@ -276,11 +430,13 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
     ST_HIP(t, hipMemcpyAsync(t->h_pavg.get(), t->d_pavg.get(), sizeof(float) * items, hipMemcpyDeviceToHost, c->stream));
     d2h += 8ull * (uint64_t)items;
   }
-  launch_save_tail(c, t->rows, rows, nframes);
+  if (ring_call) launch_save_tail(c, t->rows, ring, nframes);
+  else launch_save_tail(c, t->rows, rows, nframes);
   ST_HIP(t, hipGetLastError());
   ST_HIP(t, stream_wait(c->stream));
   flip_tail(t->rows);
   t->seen_batch = c->batch_no;
+  if (t->sparse) t->sp_tiles_in_batches += (uint64_t)((nframes + c->last_det.shift + kFusedTF - 1) / kFusedTF) * (uint64_t)t->ncols;
   out->nframes = nframes;
   out->ncand = ncand;
   out->nwatch = nwatch;

@@ -36,6 +36,7 @@
 #include "../../include/specscan_track.h"
 #include "../../include/specscan_track_feed.h"
 #include "../../include/specscan_track_sparse.h"
+#include "../../include/specscan_track_digest_sparse.h"
 #include "../../include/specscan_record_feed.h"
 #include "../../include/specscan_spectrogram_feed.h"
 #include "chan_ranges.h"
@@ -57,6 +58,7 @@
 #include "track_digest_blocked.h"
 #include "track_feed.h"
 #include "track_sparse.h"
+#include "track_digest_sparse.h"
 
 namespace {
 

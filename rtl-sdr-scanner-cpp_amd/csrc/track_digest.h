@@ -102,12 +102,16 @@ __global__ __launch_bounds__(256) void k_window_peaks(const WindowPeaksArgs a) {
 
 // tail_out[k] = rel row of frame nframes - tail_rows + k (k < tail_rows): from the batch, or — a batch shorter than the tail — from
 // the old tail (another buffer). n is a multiple of 4 (fft sizes are powers of two >= 64) but the rows are taken bin by bin.
-__global__ __launch_bounds__(256) void k_save_tail(const RelRows rows, int nframes, float* __restrict__ tail_out) {
+// Rows: where the rel rows live — RelRows, or track_digest_sparse.h's RingRows; anything with n, tail_rows and a rel_at.
+template <class Rows>
+__device__ __forceinline__ void save_tail_rows(const Rows& rows, int nframes, float* __restrict__ tail_out) {
   const size_t total = (size_t)rows.tail_rows * rows.n;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
     const int k = (int)(e / rows.n), bin = (int)(e % rows.n);
     tail_out[e] = rel_at(rows, nframes - rows.tail_rows + k, bin);
   }
 }
+
+__global__ __launch_bounds__(256) void k_save_tail(const RelRows rows, int nframes, float* __restrict__ tail_out) { save_tail_rows(rows, nframes, tail_out); }
 
 }  // namespace ss

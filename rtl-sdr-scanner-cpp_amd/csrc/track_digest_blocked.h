@@ -193,8 +193,10 @@ SS_BLOCKED_HD size_t blocked_lds_bytes(int nrows, int half) {
 
 static_assert(kBlockedLanes == kTrackTile, "one lane per bin of a tile");
 
-struct CandBestArgs {
-  RelRows rows;
+// Rows: where the rel rows live — RelRows (k_best_blocked), or track_digest_sparse.h's RingRows; anything with n and a rel_at
+template <class Rows>
+struct CandBestArgsOf {
+  Rows rows;
   const float* avg;         // the batch's avg plane
   const int32_t* cand_off;  // [nframes + 1], clipped to ncand
   const int32_t* cand_idx;  // [ncand], ascending inside a frame
@@ -207,6 +209,7 @@ struct CandBestArgs {
   int width;       // staged bins of a row: kTrackTile + 2 * half
   float start_level;
 };
+using CandBestArgs = CandBestArgsOf<RelRows>;
 
 // first candidate of the frame's list [a, b) at or above bin: the lists are ascending
 __device__ __forceinline__ int cand_lower_bound(const int32_t* idx, int a, int b, int bin) {
@@ -231,9 +234,9 @@ __device__ __forceinline__ SegBest seg_shfl_down(SegBest x, int d) {
 // grid nframes * tiles, 256 threads. A workgroup whose tile of its frame holds no candidate returns at once; otherwise it stages, row
 // by row, the bins its candidates' windows can touch, and lane t takes the tile's t-th candidate (a tile holds at most 256).
 // Dynamic LDS (blocked_lds_bytes): width floats (the row), nrows * 256 ints (the lanes' ascending lists), width + width 16-bit
-// offsets (P, S), 16 words (wave totals).
-__global__ __launch_bounds__(kTrackTile) void k_best_blocked(const CandBestArgs a) {
-  extern __shared__ float lds_blocked[];
+// offsets (P, S), 16 words (wave totals). The body over the row source; lds_blocked is the kernel's dynamic LDS.
+template <class Rows>
+__device__ __forceinline__ void best_blocked_tile(const CandBestArgsOf<Rows>& a, float* lds_blocked) {
   const int n = a.rows.n;
   const int f = blockIdx.x / a.tiles;
   const int t0 = (blockIdx.x % a.tiles) * kTrackTile;
@@ -307,6 +310,11 @@ __global__ __launch_bounds__(kTrackTile) void k_best_blocked(const CandBestArgs 
   if (!active) return;
   a.cand_best[j] = list_mode(mine, kTrackTile, m, c);  // no row qualifies: the candidate itself (signal_tracker.cpp, getBestIndex)
   a.cand_avg[j] = a.avg[(size_t)f * n + c];
+}
+
+__global__ __launch_bounds__(kTrackTile) void k_best_blocked(const CandBestArgs a) {
+  extern __shared__ float lds_blocked[];
+  best_blocked_tile(a, lds_blocked);
 }
 
 #endif  // __HIPCC__

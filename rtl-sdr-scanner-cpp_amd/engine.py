@@ -131,13 +131,16 @@ class SpectrumEngine(abi.Chain):
                                          _ptr(cand_idx), _ptr(cand_avg), cap)
         self._check(st)
 
-    def track_digest(self, group_size: int, start_level: float | None = None, max_watch: int = 1024, cand_cap: int | None = None):
+    def track_digest(self, group_size: int, start_level: float | None = None, max_watch: int = 1024, cand_cap: int | None = None, sparse: bool = False):
         """A device-side tracking digest bound to this chain (include/specscan_track.h; needs ``flags=SS_FLAG_KEEP_PLANES``):
         ``digest(cand_off, cand_idx, keys)`` after every batch gives what ``tracker.SignalTracker.process_batch_digest`` runs on
-        instead of the rel and avg planes."""
+        instead of the rel and avg planes.
+        ``sparse=True`` (include/specscan_track_digest_sparse.h): the chain needs no SS_FLAG_KEEP_PLANES — it keeps culling and keeps the
+        forms that write no dB plane, ``digest`` evaluates the tile columns the watch windows touch once more, and ``sparse_stats()``
+        says how many tiles that took."""
         from .tracker import TrackDigest
         return TrackDigest(self, group_size, self.cfg.start_level if start_level is None else start_level, max_watch,
-                           min(self.cfg.max_batch * 1024, 1 << 22) if cand_cap is None else cand_cap)
+                           min(self.cfg.max_batch * 1024, 1 << 22) if cand_cap is None else cand_cap, sparse=sparse)
 
     def sync(self):
         """Drain the deferred stages of earlier process_device calls and wait for the chain's stream."""

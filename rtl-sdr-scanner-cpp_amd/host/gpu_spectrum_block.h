@@ -19,7 +19,9 @@
 // enableDeviceTracker does the same without the planes: the config carries SS_FLAG_KEEP_PLANES, work() asks ss_process for neither the
 // rel nor the avg plane (8 B/sample of PCIe traffic and a host copy of every row), st_digest (include/specscan_track.h) computes on
 // the device what the tracker would have read of them, and SignalTracker::processFrameDigest runs the same bookkeeping on that. The
-// callback sees the same sequence either way (tests/test_gpu_track_digest.py).
+// callback sees the same sequence either way (tests/test_gpu_track_digest.py). enableSparseDeviceTracker is the same on a config WITHOUT
+// the flag (st_create_sparse, include/specscan_track_digest_sparse.h): the scan keeps the form it takes untracked
+// (tests/test_gpu_track_digest_sparse.py).
 //
 // With SS_FLAG_SPECTROGRAM in the config the Spectrogram side branch runs on the GPU as well (enableSpectrogram): the
 // block keeps Spectrogram::send's 1000 ms gate per centre frequency (spectrogram.cpp:62-75) and hands the int8 row to a
@@ -34,6 +36,7 @@
 #include <gnuradio/sync_block.h>
 #include <specscan.h>
 #include <specscan_track.h>
+#include <specscan_track_digest_sparse.h>
 
 #include "signal_tracker.h"
 
@@ -99,22 +102,12 @@ class GpuSpectrum : virtual public gr::sync_block {
   }
   // The same, fed by the device-side digest instead of the rel / avg planes. The block's config must carry SS_FLAG_KEEP_PLANES.
   void enableDeviceTracker(const specscan::TrackerConfig& config, TransmissionCallback on_transmissions, int32_t max_watch = 4096) {
-    st_config sc{};
-    sc.abi_version = ST_ABI_VERSION;
-    sc.group_size = config.group_size;
-    sc.start_level = config.start_level;
-    sc.max_watch = max_watch;
-    // (a limit, not an allocation: the lists this block hands over grow after an overflow, fft_size x max_batch bounds them for good)
-    sc.cand_cap = static_cast<int32_t>(std::min<int64_t>(static_cast<int64_t>(m_config.max_batch) * m_config.fft_size, INT32_MAX));
-    st_ctx* digest = nullptr;
-    if (st_create(m_ctx, &sc, &digest) != SS_OK) throw std::runtime_error(std::string("GpuSpectrum: ") + st_last_error(nullptr));
-    std::lock_guard<std::mutex> lock(m_mutex);
-    st_destroy(m_digest);
-    m_digest = digest;
-    m_tracker = std::make_unique<specscan::SignalTracker>(config);
-    m_onTransmissions = std::move(on_transmissions);
-    m_rel.clear();
-    m_avgPlane.clear();
+    enableDigestTracker(config, std::move(on_transmissions), max_watch, false);
+  }
+  // The same on a block whose config does NOT carry SS_FLAG_KEEP_PLANES (st_create_sparse, specscan_track_digest_sparse.h): the scan keeps
+  // culling and keeps the forms that write no dB plane; the digest evaluates the tile columns the watch windows touch once more.
+  void enableSparseDeviceTracker(const specscan::TrackerConfig& config, TransmissionCallback on_transmissions, int32_t max_watch = 4096) {
+    enableDigestTracker(config, std::move(on_transmissions), max_watch, true);
   }
   void setClock(Clock clock) { m_clock = std::move(clock); }
 
@@ -228,6 +221,26 @@ class GpuSpectrum : virtual public gr::sync_block {
   int candidateOverflows() const { return m_overflows; }  // work() calls whose lists were cut (capacity grows each time)
 
  private:
+  // enableDeviceTracker and enableSparseDeviceTracker
+  void enableDigestTracker(const specscan::TrackerConfig& config, TransmissionCallback on_transmissions, int32_t max_watch, bool sparse) {
+    st_config sc{};
+    sc.abi_version = ST_ABI_VERSION;
+    sc.group_size = config.group_size;
+    sc.start_level = config.start_level;
+    sc.max_watch = max_watch;
+    // (a limit, not an allocation: the lists this block hands over grow after an overflow, fft_size x max_batch bounds them for good)
+    sc.cand_cap = static_cast<int32_t>(std::min<int64_t>(static_cast<int64_t>(m_config.max_batch) * m_config.fft_size, INT32_MAX));
+    st_ctx* digest = nullptr;
+    if ((sparse ? st_create_sparse : st_create)(m_ctx, &sc, &digest) != SS_OK) throw std::runtime_error(std::string("GpuSpectrum: ") + st_last_error(nullptr));
+    std::lock_guard<std::mutex> lock(m_mutex);
+    st_destroy(m_digest);
+    m_digest = digest;
+    m_tracker = std::make_unique<specscan::SignalTracker>(config);
+    m_onTransmissions = std::move(on_transmissions);
+    m_rel.clear();
+    m_avgPlane.clear();
+  }
+
   ss_config m_config;
   ss_ctx* m_ctx = nullptr;
   CandidateCallback m_onCandidates;

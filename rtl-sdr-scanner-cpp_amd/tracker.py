@@ -1,7 +1,8 @@
 """ctypes binding of host/libspecscan_host.so — the host-side signal tracker (host/signal_tracker.h), the part of
 the reference's Transmission block that turns per-frame candidates into the Scanner's (shift Hz, flush) list — and of the
 st_* entry points of libspecscan.so (include/specscan_track.h), the device-side digest that tracker can run on instead of
-the rel and avg planes — and of the stf_* entry points (include/specscan_track_feed.h), the same digest behind the pipelined feed, with
+the rel and avg planes, with its form for engines that keep no planes
+(include/specscan_track_digest_sparse.h) — and of the stf_* entry points (include/specscan_track_feed.h), the same digest behind the pipelined feed, with
 its form for engines that keep no planes (include/specscan_track_sparse.h)."""
 from __future__ import annotations
 
@@ -149,11 +150,22 @@ def bind_track(lib: C.CDLL) -> None:
     lib.st_digest.restype = C.c_int
 
 
+ST_SPARSE_EXPORTS = ("st_create_sparse", "st_sparse_stats")  # include/specscan_track_digest_sparse.h
+
+
+def bind_track_digest_sparse(lib: C.CDLL) -> None:
+    lib.st_create_sparse.argtypes = [C.c_void_p, C.POINTER(StConfig), C.POINTER(C.c_void_p)]
+    lib.st_create_sparse.restype = C.c_int
+    lib.st_sparse_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.st_sparse_stats.restype = C.c_int
+
+
 class TrackDigest:
     """One st_ctx bound to a SpectrumEngine created with SS_FLAG_KEEP_PLANES (SpectrumEngine.track_digest). Call ``digest`` once
-    after every batch, ``reset`` with the engine's ``reset``."""
+    after every batch, ``reset`` with the engine's ``reset``.
+    ``sparse=True``: st_create_sparse — the engine may lack SS_FLAG_KEEP_PLANES (fused back end, any size)."""
 
-    def __init__(self, engine, group_size: int, start_level: float = 8.0, max_watch: int = 1024, cand_cap: int = 1 << 20):
+    def __init__(self, engine, group_size: int, start_level: float = 8.0, max_watch: int = 1024, cand_cap: int = 1 << 20, sparse: bool = False):
         from .abi import SpecscanError
         self._err = SpecscanError
         self._engine = engine  # (the scan context must outlive the digest object)
@@ -161,7 +173,9 @@ class TrackDigest:
         bind_track(self._lib)
         cfg = StConfig(ST_ABI_VERSION, int(group_size), float(start_level), int(max_watch), int(cand_cap))
         h = C.c_void_p()
-        st = self._lib.st_create(engine._h, C.byref(cfg), C.byref(h))
+        if sparse:
+            bind_track_digest_sparse(self._lib)
+        st = (self._lib.st_create_sparse if sparse else self._lib.st_create)(engine._h, C.byref(cfg), C.byref(h))
         if st != 0:
             raise SpecscanError(st, (self._lib.st_last_error(None) or b"").decode())
         self._h = h
@@ -184,6 +198,14 @@ class TrackDigest:
 
     def reset(self):
         self._check(self._lib.st_reset(self._h))
+
+    def sparse_stats(self) -> dict:
+        """{"tiles_evaluated", "tiles_in_batches"} since the object was made or reset: the tiles the replay inside ``digest`` ran, out
+        of the tiles the digested batches have. SpecscanError on an object whose engine keeps its planes (nothing is replayed there)."""
+        bind_track_digest_sparse(self._lib)
+        ev, tot = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.st_sparse_stats(self._h, C.byref(ev), C.byref(tot)))
+        return {"tiles_evaluated": int(ev.value), "tiles_in_batches": int(tot.value)}
 
     def digest(self, cand_off, cand_idx, keys) -> dict:
         """The digest of the engine's last batch as numpy copies: cand_off (clipped to the lists), cand_idx, cand_best, cand_avg,
