@@ -19,7 +19,10 @@ def _psd_rows(rng, nframes, n):
     return x
 
 
-@pytest.mark.parametrize("n,fs", [(8192, 2_048_000), (2048, 512_000), (65536, 20_000_000), (1024, 250_000), (32768, 8_000_000)])
+@pytest.mark.parametrize("n,fs", [(8192, 2_048_000), (2048, 512_000), (65536, 20_000_000), (1024, 250_000), (32768, 8_000_000),
+                                  # what getFft picks at 20 and 61.44 MS/s, and 2^20 points: m = 8, 16, 64 input bins per output bin under
+                                  # the 16384-bin cap — the sizes tests/test_gpu_spectrogram_long.py trusts the restatement at
+                                  (131072, 20_000_000), (262144, 61_440_000), (1 << 20, 61_440_000)])
 def test_restatement_equals_the_reference_spectrogram(ref_mod, n, fs):
     O = ref_mod
     rng = np.random.default_rng(n)
@@ -27,10 +30,12 @@ def test_restatement_equals_the_reference_spectrogram(ref_mod, n, fs):
     ref = O.RefSpectrogram(n, fs, 100_000_000)
     orc = L.orc_spectrogram_create(n, fs)
     assert L.orc_spectrogram_size(orc) == ref.size == min(16384, O.ref().ref_get_fft(fs, 1000), n)
+    if n > 65536:
+        assert ref.size == 16384 and n // ref.size == {131072: 8, 262144: 16, 1 << 20: 64}[n]
     now = 5_000
     sent = 0
     for burst in range(6):
-        rows = _psd_rows(rng, int(rng.integers(1, 40)), n)
+        rows = _psd_rows(rng, int(rng.integers(1, 40 if n <= 65536 else 5)), n)  # (a few rows per burst at the long sizes: the test stays in seconds)
         # inside a burst the clock stands still: Spectrogram::send's gate (now > last + 1000 ms) stays shut
         assert ref.work(rows, now) == 0
         for r in rows:
