@@ -236,8 +236,8 @@ int ss_feed_submit(ss_feed* f, int32_t nframes, const int64_t* t_ms, int64_t use
   if (st != SS_OK) return st;
   const int n_learn = plan_learning(c, z, nframes, t_ms);
   const bool want_cands = f->cand_cap > 0;
-  st = run_batch(c, s.d_in.get(), (long long)n, nframes, n_learn, z, nullptr, nullptr, nullptr, s.d_off.get(), want_cands ? s.d_idx.get() : nullptr,
-                 want_cands ? s.d_avg.get() : nullptr, f->cand_cap);
+  st = run_batch(c, s.d_in.get(), (long long)n, nframes, n_learn, z,
+                 CallOut{nullptr, nullptr, nullptr, s.d_off.get(), want_cands ? s.d_idx.get() : nullptr, want_cands ? s.d_avg.get() : nullptr, f->cand_cap});
   if (st != SS_OK) return st;
   flush_stages(c);  // the slot's results are copied out right behind the batch
   SS_HIP(c, hipMemcpyAsync(s.h_off.get(), s.d_off.get(), sizeof(int32_t) * ((size_t)nframes + 1), hipMemcpyDeviceToHost, c->stream));

@@ -76,7 +76,7 @@ hipError_t stf_clear(stf_ctx* t) {
 //     ring_place_decide checks), so neither this batch's tiles nor its FFT stage nor the drain's k_ring_fill (hist_out) touched it. The
 //     next writers are a LATER call's rows, or that call's place_ring moving the window to the front (k_hist_shift, on this stream) or
 //     settling dB rows in place (k_rows_sub_thr, on this stream): all enqueued after this replay. Calls through the feed are not
-//     overlapped (run_batch: allow_overlap = false), so they carry no halo_psd; if one did, its halo buffer (d_halo[L mod 2 nq]) is
+//     overlapped (run_batch: device_call = false), so they carry no halo_psd; if one did, its halo buffer (d_halo[L mod 2 nq]) is
 //     next written 2 nq launches on, by a call enqueued later.
 //   * the dB plane (d_psd2 rotation, DetectArgs::psd = last_psd), the noise ceiling and the pass mask: what k_best_blocked and k_save_tail
 //     of the same digest read, on the same grounds (the comment at the top of this file).

@@ -56,6 +56,7 @@ struct Diag {
   bool fft_swz = true;           // 8192 points: 16-byte swizzled first exchange
   int prio_fft = 0, prio_other = 0;  // s_setprio of k_scan_step's roles
   std::string stamp_path;        // SS_DIAG only: dump per-workgroup start / end stamps of the 40th full k_scan_step launch here (ss_ctx::d_stamps)
+  std::string route_path;        // SS_DIAG only (SS_ROUTE_RECORD=file): run_batch appends one line per call here, the ask and the route it decided (call_route.h: print_route)
   bool cull_stats = false;       // SS_DIAG only (SS_CULL_STATS=1): tiles seen / on the culling path / culled, printed when the context goes (ss_ctx::d_cull_stats)
   bool plan_nozero = false;      // SS_DIAG only (SS_PLAN_NOZERO=1): DetectArgs::cull_stats carries the sentinel 1 instead of counters
   // SS_DIAG only, deep pipelining: the input canary. The launch of call L + 1 reads the last frames of call L's input once
@@ -139,6 +140,7 @@ struct Diag {
     prio_fft = num("SS_STEP_PRIO_FFT", 0);
     prio_other = num("SS_STEP_PRIO_OTHER", 0);
     if (const char* v = getenv("SS_STEP_STAMPS")) stamp_path = v;
+    if (const char* v = getenv("SS_ROUTE_RECORD")) route_path = v;
     emit_wide = tri("SS_EMIT_WIDE") != 0;
     step_long = tri("SS_STEP_LONG") != 0;
     deep = tri("SS_DEEP") != 0;

@@ -40,6 +40,7 @@
 #include "../../include/specscan_record_feed.h"
 #include "../../include/specscan_spectrogram_feed.h"
 #include "chan_ranges.h"
+#include "call_route.h"
 #include "ctx_buffers.h"
 #include "detect_fused.h"
 #include "detect_kernels.h"
@@ -84,6 +85,14 @@ struct NoiseState {  // NoiseLearner::Noise, sources/radio/blocks/noise_learner.
   bool ready = false;
   int64_t start_ms = 0;
   bool have_start = false;
+};
+
+// What a call hands out: the planes and the candidate lists, each null where the caller wants none (device memory)
+struct CallOut {
+  float *psd = nullptr, *rel = nullptr, *avg = nullptr;
+  int32_t *cand_off = nullptr, *cand_idx = nullptr;
+  float* cand_avg = nullptr;
+  int cand_cap = 0;
 };
 
 // SS_FLAG_REFERENCE_NAN (reference_nan.h): what the poison stage between a call's detect and emit stages works on
@@ -1190,9 +1199,22 @@ int grid_for(size_t work_items, int block) {
   return (int)g;
 }
 
+// The noise ceiling from a call's learning frames and, where tiles are culled, its per-tile-column minima behind it (get_noise).
+// (cull and cull_long imply step_path, tests/host/scan_form_check.cpp: off the step path this is k_noise_learn alone)
+void launch_learning(ss_ctx* c, const float* d_psd, int n_learn, NoiseState* z) {
+  if (n_learn <= 0) return;
+  hipLaunchKernelGGL(ss::k_noise_learn, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, d_psd, c->n, n_learn, z->d_thr);
+  if (c->cull || c->cull_long) hipLaunchKernelGGL(ss::k_thr_tilemin, dim3(c->n / 256), dim3(64), 0, c->stream, (const float*)z->d_thr, c->n, z->d_thr + c->n);
+}
+
+// Do two buffers overlap? (null or empty: no. Every call has at least one frame, so a plane that is there is never empty.)
+bool clash(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+  return a && b && abytes && bbytes && pa < pb + bbytes && pb < pa + abytes;
+}
+
 // Back end for groupings other than 21 x 21: one simple kernel per reference stage.
-int run_backend_unfused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, NoiseState* z, float* d_rel_out, float* d_avg_out,
-                        int32_t* d_cand_off, int32_t* d_cand_idx, float* d_cand_avg, int cand_cap) {
+int run_backend_unfused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, NoiseState* z, const CallOut& out) {
   const int n = c->n;
   const int G = c->cfg.grouping_y;
   // Fold the previous batch into the ring: history = newest G-1 rows of [history ++ previous batch].
@@ -1214,19 +1236,19 @@ int run_backend_unfused(ss_ctx* c, const float* d_psd, int nframes, int n_learn,
     hipLaunchKernelGGL(ss::k_noise_learn, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_psd, n, n_learn, z->d_thr);
   }
   hipLaunchKernelGGL(ss::k_noise_apply, dim3(grid_for((size_t)nframes * n / 4, 256)), dim3(256), 0, c->stream, d_psd, z->d_thr, n, nframes,
-                     n_learn, rel_batch, d_rel_out);
+                     n_learn, rel_batch, out.rel);
   hipLaunchKernelGGL(ss::k_time_mean, dim3(grid_for((size_t)nframes * n / 4, 256)), dim3(256), 0, c->stream, c->d_rel, n, nframes, G,
                      c->frames_pushed, c->d_avgy);
   const int a = c->cfg.grouping_x / 2;
   const int blocks_per_row = (n + 255) / 256;
   hipLaunchKernelGGL(ss::k_freq_mean_detect, dim3(nframes * blocks_per_row), dim3(256), sizeof(float) * (256 + 2 * a), c->stream, c->d_avgy,
-                     n, nframes, c->cfg.grouping_x, c->cfg.start_level, c->d_pass, c->d_avg2[0], d_avg_out, c->d_mask2[0]);
+                     n, nframes, c->cfg.grouping_x, c->cfg.start_level, c->d_pass, c->d_avg2[0], out.avg, c->d_mask2[0]);
   const int wpr = n / 32;
   hipLaunchKernelGGL(ss::k_cand_count, dim3(nframes), dim3(256), 0, c->stream, c->d_mask2[0], wpr, c->d_counts);
-  hipLaunchKernelGGL(ss::k_cand_scan, dim3(1), dim3(256), 0, c->stream, c->d_counts, nframes, c->d_off, d_cand_off);
-  if (d_cand_idx && cand_cap > 0) {
-    hipLaunchKernelGGL(ss::k_cand_write, dim3(nframes), dim3(256), 0, c->stream, c->d_mask2[0], wpr, n, c->d_off, c->d_avg2[0], cand_cap, d_cand_idx,
-                       d_cand_avg);
+  hipLaunchKernelGGL(ss::k_cand_scan, dim3(1), dim3(256), 0, c->stream, c->d_counts, nframes, c->d_off, out.cand_off);
+  if (out.cand_idx && out.cand_cap > 0) {
+    hipLaunchKernelGGL(ss::k_cand_write, dim3(nframes), dim3(256), 0, c->stream, c->d_mask2[0], wpr, n, c->d_off, c->d_avg2[0], out.cand_cap, out.cand_idx,
+                       out.cand_avg);
   }
   c->rot_frames = nframes;
   c->last_avg = c->d_avg2[0];
@@ -1273,8 +1295,7 @@ RingPlace place_ring(ss_ctx* c, int nframes) {
   return r;
 }
 
-int run_backend_fused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, NoiseState* z, SpecState* spec, float* d_rel_out,
-                      float* d_avg_out, int32_t* d_cand_off, int32_t* d_cand_idx, float* d_cand_avg, int cand_cap, ss_ctx::PendDet* deferred) {
+int run_backend_fused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, NoiseState* z, SpecState* spec, const CallOut& out, ss_ctx::PendDet* deferred) {
   const int n = c->n;
   constexpr int G = 21, GX = 21, TF = kFusedTF, TB = 256;  // measured against 32-frame and 128-bin tiles: 16 x 256 is fastest
   constexpr int H = kHistRows;
@@ -1287,7 +1308,7 @@ int run_backend_fused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, N
   int* counts = c->d_cnt3[cur];
   const int b = c->buf_cur;
   const bool keep_planes = (c->cfg.flags & SS_FLAG_KEEP_PLANES) != 0;
-  float* avg_full = d_avg_out ? d_avg_out : (keep_planes ? c->d_avg2[b] : nullptr);
+  float* avg_full = out.avg ? out.avg : (keep_planes ? c->d_avg2[b] : nullptr);
   const int shift = (int)(c->abs_frames % TF);
   const int tiles = ((nframes + shift + TF - 1) / TF) * ((n + TB - 1) / TB);
   ss::DetectArgs da{};
@@ -1304,7 +1325,7 @@ int run_backend_fused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, N
   da.pass = c->d_pass;
   da.maskbits = c->d_mask2[b];
   da.counts = counts;
-  da.rel_out = d_rel_out;
+  da.rel_out = out.rel;
   da.avg_out = avg_full;
   da.avg_sparse = c->d_avg2[b];
   da.segsum = (c->cull && !spec) ? c->d_segsum[b] : nullptr;
@@ -1338,14 +1359,14 @@ int run_backend_fused(ss_ctx* c, const float* d_psd, int nframes, int n_learn, N
   ea.counts_clear = c->d_cnt3[clr];
   ea.clear_n = c->cnt_frames[clr];
   ea.avg = avg_full ? avg_full : c->d_avg2[b];
-  ea.cap = cand_cap;
+  ea.cap = out.cand_cap;
   ea.off_int = c->d_off4[b];
   ea.live_clear = da.live;
   ea.clear_masks = (c->cull || c->cull_long) ? 1 : 0;  // (every emit stage of a culling context: the mask buffers are all zero between uses)
   c->d_off = c->d_off4[b];
-  ea.off_out = d_cand_off;
-  ea.cand_idx = (d_cand_idx && cand_cap > 0) ? d_cand_idx : nullptr;
-  ea.cand_avg = d_cand_avg;
+  ea.off_out = out.cand_off;
+  ea.cand_idx = (out.cand_idx && out.cand_cap > 0) ? out.cand_idx : nullptr;
+  ea.cand_avg = out.cand_avg;
   c->cnt_frames[cur] = nframes;  // this buffer now holds nframes counts (read by the emit stage, zeroed two batches on)
   c->cnt_frames[clr] = 0;
   c->cnt_cur = (cur + 1) % c->ncnt;
@@ -1449,23 +1470,19 @@ static void canary_sum(ss_ctx* c, const void* d_iq, long long item_stride, int n
 
 // One call on a context with deep pipelining (ss_ctx::deep): launch L = FFT(L) + detect(L - 2) + emit(L - 4) on queue L & 1, or
 // — learning frames, short calls, callers that wait after every call — the three stages in order on the public stream.
-int run_call_deep(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, int n_learn, NoiseState* z, SpecState* spec, float* d_psd,
-                  float* d_psd_out, float* d_rel_out, float* d_avg_out, int32_t* d_cand_off, int32_t* d_cand_idx, float* d_cand_avg, int cand_cap,
-                  bool allow_overlap) {
+int run_call_deep(ss_ctx* c, const void* d_iq, long long item_stride, const CallAsk& ask, const CallRoute& route, NoiseState* z, SpecState* spec, float* d_psd,
+                  const CallOut& out) {
   int st = SS_OK;
+  const int nframes = ask.nframes, n_learn = ask.n_learn;
   const ss::Fft8192Args g = fft8192_args(c, d_iq, item_stride, d_psd);
   FftRole role;
   role.frames = &g;
   role.n = nframes;
-  if (allow_overlap && ++c->deep_calls_since_sync >= 2) c->deep_eager = false;
-  const bool overlap = allow_overlap && !c->deep_eager && !c->deep_iq_recycled && c->diag.pipeline && n_learn == 0 && nframes >= kHistRows;
+  if (ask.device && ++c->deep_calls_since_sync >= 2) c->deep_eager = false;
+  const bool overlap = route.overlap && !c->deep_eager && !c->deep_iq_recycled;
   const size_t plane_bytes = sizeof(float) * (size_t)nframes * (size_t)c->n;
-  const auto clash = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
-    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-    return a && b && abytes && bbytes && pa < pb + bbytes && pb < pa + abytes;
-  };
-  ss_ctx::Buffers mine{{d_psd_out, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg},
-                       {plane_bytes, plane_bytes, plane_bytes, sizeof(int32_t) * ((size_t)nframes + 1), sizeof(int32_t) * (size_t)cand_cap, sizeof(float) * (size_t)cand_cap},
+  ss_ctx::Buffers mine{{out.psd, out.rel, out.avg, out.cand_off, out.cand_idx, out.cand_avg},
+                       {plane_bytes, plane_bytes, plane_bytes, sizeof(int32_t) * ((size_t)nframes + 1), sizeof(int32_t) * (size_t)out.cand_cap, sizeof(float) * (size_t)out.cand_cap},
                        0, ~(uintptr_t)0, 0, 0, 0};
   mine.iq_lo = reinterpret_cast<uintptr_t>(d_iq);
   mine.iq_hi = mine.iq_lo + (size_t)nframes * (size_t)item_stride * in_bytes_per_sample(c->cfg.in_format);
@@ -1579,12 +1596,9 @@ int run_call_deep(ss_ctx* c, const void* d_iq, long long item_stride, int nframe
     if (has_det) c->pe.push_back(ss_ctx::PendEmit{d.emit, L + c->nq});
     if (ring_reader) c->deep_barrier = L;
   }
-  if (n_learn > 0) {
-    hipLaunchKernelGGL(ss::k_noise_learn, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, (const float*)d_psd, c->n, n_learn, z->d_thr);
-    if (c->cull || c->cull_long) hipLaunchKernelGGL(ss::k_thr_tilemin, dim3(c->n / 256), dim3(64), 0, c->stream, (const float*)z->d_thr, c->n, z->d_thr + c->n);
-  }
+  launch_learning(c, d_psd, n_learn, z);
   ss_ctx::PendDet mine_det{};
-  st = run_backend_fused(c, d_psd, nframes, n_learn, z, nullptr, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg, cand_cap, &mine_det);
+  st = run_backend_fused(c, d_psd, nframes, n_learn, z, nullptr, out, &mine_det);
   if (st != SS_OK) return st;
   if (role.n_halo) {
     mine_det.a.halo_psd = role.halo_psd;
@@ -1677,14 +1691,146 @@ void set_ring_form(ss_ctx* c, bool perm8) {
   c->ring_perm8 = perm8;
 }
 
+static_assert(ss_ctx::Waiting::DET == kRideDet && ss_ctx::Waiting::EMIT == kRideEmit && ss_ctx::Waiting::PLAN == kRidePlan && ss_ctx::Waiting::ROWS == kRideRows, "call_route.h");
+
+// CALL_FOLD: the radix-8 / radix-16 fold in the load stage of the 8192-point transform, one launch whatever the call's length; it
+// writes the call's rows where rx says (row f - first_hist of that region is frame f's: RowsExtra, fft256_kernels.h)
+void launch_fold(ss_ctx* c, const CallRoute& route, const void* d_iq, long long item_stride, int nframes, const ss::RowsExtra& rx) {
+  ss::Fft8192Args gf{};
+  gf.tabs = ss::Fft8192V2Tables{c->d_tw8v2, c->d_tw8v2 + 256, c->d_tw8v2 + 256 + 384, nullptr, nullptr};
+  gf.db_off = c->db_off;
+  gf.scale = c->cfg.int_scale;
+  gf.psd = rx.hist_out;
+  ss::Dif8Front df = ss::dif8_front_of(d_iq, item_stride, c->d_dif8_tab, 1 << c->dif_logq);
+  df.smax = rx.smax;
+  df.smax_mask = rx.smax_mask;
+  df.abs0 = rx.abs0;
+  df.first_hist = rx.first_hist;
+  df.nframes = nframes;
+  df.zero_word = rx.zero_word;
+  FftRole drole;
+  drole.frames = &gf;
+  drole.dif = &df;
+  // (two residues per workgroup: four per frame at radix 8, eight at radix 16. One residue per workgroup for short calls was tried,
+  // measured and removed: 16-frame calls 20.6 against 19.5 us, 32-frame calls 26.0 against 20.3, profiles/r06/s13_summary.txt)
+  drole.n = (c->dif_logq == 4 ? 8 : SS_DIF8_W) * nframes;
+  launch_step(c, &drole, c->wait.riding(route.ride_first));
+}
+
+// CALL_MERGED: this call's column half into the work buffer of its turn, beside the row half of the call before (rows_for_next_launch)
+void launch_merged(ss_ctx* c, const CallRoute& route, const ss::ColsArgs& gc, int nframes) {
+  ss::ColsArgs gcm = gc;
+  gcm.work = c->work_cur ? c->d_work2 : c->d_work;
+  FftRole crole;
+  crole.cols = &gcm;
+  crole.n = nframes * (c->n >> 13);
+  launch_step(c, &crole, c->wait.riding(route.ride_first));
+}
+// ... whose own row half waits for the next launch; it reads the work buffer this call's column half has just been told to fill
+void rows_for_next_launch(ss_ctx* c, int nframes, const ss::RowsExtra& rx) {
+  ss_ctx::PendRows& rows = c->wait.rows.v;
+  float2* work = c->work_cur ? c->d_work2 : c->d_work;
+  rows.x1024 = c->rows1024x256;
+  if (rows.x1024) {  // (262144 points: 32 row tiles of 8 rows x 1024 points per frame)
+    rows.r1024 = rows1024x256_args(c, nullptr, rx);
+    rows.r1024.work = work;
+    rows.tiles = nframes * 32;
+  } else {
+    rows.r256 = rows256_args(c, nullptr, rx);
+    rows.r256.work = work;
+    rows.tiles = nframes * 8;
+  }
+  c->wait.rows.have = true;
+  c->work_cur ^= 1;
+}
+
+// CALL_ROWS256_STEP, CALL_ROWS1024X256, CALL_TWO_PASS: per chunk the column half, then the row half (call_route.h: which of the two is a
+// role of k_scan_step, the chunk, and what rides on the first chunk's two launches).
+//   65536 points with tile culling: both halves of the FFT as FFT roles of k_scan_step.
+//   262144 points (round 6): the 65536-point two-launch pipeline (256-point column tiles as k_scan_step's FFT role); the row half is a launch
+//   of k_fft_rows1024_psd<8> that carries nothing.
+//   2^20 points: the column half of call k as a launch of its own (16 columns x 1024 rows per 1024-thread workgroup: too many threads for a
+//   role; it takes the chunk's first frame and the ready plan itself), then ONE launch of k_scan_step whose FFT role is the ROW half of
+//   call k — 8 rows x 1024 points per 512-thread workgroup — with detect(k - 1) and emit(k - 2) riding on it as they ride on the column
+//   launches of the other sizes.
+void launch_chunks(ss_ctx* c, const CallRoute& route, const ss::ColsArgs& gc, const void* d_iq, long long item_stride, int nframes, float* d_psd, const ss::RowsExtra& rx) {
+  const size_t sample = in_bytes_per_sample(c->cfg.in_format);
+  for (int f0 = 0; f0 < nframes; f0 += route.chunk) {
+    const int nf = std::min(route.chunk, nframes - f0);
+    const bool first = f0 == 0;
+    c->prof_launch_frames = nf;
+    if (route.shape == CALL_TWO_PASS) {
+      launch_cols1024(c, d_iq, item_stride, nf, f0);
+    } else {
+      ss::ColsArgs gcc = gc;
+      gcc.iq = static_cast<const char*>(d_iq) + (size_t)f0 * (size_t)item_stride * sample;
+      if (route.shape == CALL_ROWS1024X256) gcc.abs0 += f0;  // (the column tiles clear the ring words of THEIR frames' run maxima)
+      FftRole crole;
+      crole.cols = &gcc;
+      crole.n = nf * (c->n >> 13);
+      launch_step(c, &crole, c->wait.riding(first ? route.ride_first : 0));
+    }
+    ss::RowsExtra rxc = rx;
+    rxc.abs0 += f0;
+    rxc.first_hist -= f0;                 // (hist_out takes the call's frames >= first_hist; the tile sees chunk-local frame numbers)
+    if (!first) rxc.zero_word = nullptr;  // (the first chunk's launch zeroes the count of the list this call's plan appends to)
+    float* psd_c = (route.ring_only || !d_psd) ? nullptr : d_psd + (size_t)f0 * (size_t)c->n;
+    if (route.shape == CALL_ROWS1024X256) {
+      launch_rows1024x256(c, nf, psd_c, rxc);
+      continue;
+    }
+    ss::Rows256Args r256{};
+    ss::Rows1024Args r1024{};
+    FftRole rrole;
+    if (route.shape == CALL_TWO_PASS) {
+      r1024 = rows1024_args(c, psd_c, rxc);
+      rrole.rows1024 = &r1024;
+      rrole.n = nf * 128;
+    } else {
+      r256 = rows256_args(c, psd_c, rxc);
+      rrole.rows256 = &r256;
+      rrole.n = nf * 8;
+    }
+    launch_step(c, &rrole, c->wait.riding(first ? route.ride_second : 0));
+  }
+}
+
+// The plan of a culling call: which tiles of this call can hold a candidate at all (k_plan_long) — behind the rows kernel, ahead of the
+// launch that carries the detect stage nd. Only a stage whose sole products are mask bits and counts is planned.
+void plan_call(ss_ctx* c, const CallRoute& route, ss::DetectArgs& nd, int nframes, int abs0, bool spec) {
+  const int plan_cols = ss::plan_long_cols(nframes, nd.shift, c->n / 256, 8, route.plan_fused ? ss::kPlanFusedFloats : ss::kPlanLongFloats);  // (32 columns per workgroup — whole lines of the two-pass layout — halved the fetches and doubled the time: 128 workgroups are too few, profiles/r04/s6_summary.txt)
+  if (!route.ring_by_rows || spec || nd.rel_out || nd.avg_out || plan_cols <= 0) return;
+  int* list = c->d_tlist[(c->buf_cur + c->nbuf - 1) % c->nbuf];  // (run_backend_fused has moved buf_cur on: the set this call's mask bits go to)
+  ss::PlanLongArgs pl{};
+  pl.smax = c->d_smax;
+  pl.smax_mask = c->smax_rows - 1;
+  pl.abs0 = abs0;
+  pl.clean_rel = (int)std::max<long long>(c->clean_abs - c->abs_frames, -(1ll << 29));
+  pl.cols = plan_cols;
+  pl.logn = c->logn;
+  pl.list = list;
+  pl.layout = c->two_pass ? 1 : route.dif_call ? 2 : c->rows1024x256 ? 3 : 0;
+  ss::PlanLongDet pdet = ss::plan_long_det(nd);
+  if (c->plan_all) pdet.planes_out = 1;  // (SS_FLAG_NO_CULL on the fold's context: every tile listed, none tested)
+  if (route.merged_call || route.plan_fused) {  // (a merged call's is not ready before the call's row half has run: one launch from now)
+    ss::StageSlot<ss_ctx::PendPlan>& plan = c->wait.new_plan(route.merged_call);
+    plan.have = true;
+    plan.v.a = pl;
+    plan.v.det = pdet;
+  } else {
+    const int plan_wgs = ss::plan_blocks_of(pdet, pl, c->n);  // (groups past the band's end find no column)
+    SS_LAUNCH_SLOT(c, SS_KSLOT_PLAN, (ss::k_plan_long<21, 21, kFusedTF, 256>), dim3(plan_wgs), dim3(256), 0, pdet, pl);
+  }
+  nd.tile_list = list;
+}
+
 // The chain for one batch, everything on c->stream, nothing synchronised.
 // n_learn = leading frames that belong to the noise-learning phase (decided by the caller).
+// What the call is and what it hands out decide its route (call_route.h: decide_call); here the route meets the context's state.
 // 8192 points with the fused back end (c->step_path): the call's FFT stage is launched together with the deferred detect
 // stage of the previous call and the emit stage of the one before (scan_step.h); this call's own detect and emit stages
 // stay deferred until the next call or flush_stages.
-int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, int n_learn, NoiseState* z, float* d_psd_out,
-              float* d_rel_out, float* d_avg_out, int32_t* d_cand_off, int32_t* d_cand_idx, float* d_cand_avg, int cand_cap,
-              bool allow_overlap = false) {
+int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, int n_learn, NoiseState* z, const CallOut& out, bool device_call = false) {
   const int G = c->cfg.grouping_y;
   if (c->pass_dirty) {
     flush_stages(c);  // (ss_set_frequency_range drained them already; the mask a deferred stage reads must not change under it)
@@ -1694,8 +1840,8 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
     SS_HIP(c, hipStreamSynchronize(c->stream));  // `pass` is pageable and dies at scope end
     c->pass_dirty = false;
   }
-  float* d_psd = d_psd_out ? d_psd_out : c->d_psd2[c->psd_cur];
-  if (!d_psd_out) c->psd_cur = (c->psd_cur + 1) % c->npsd;
+  float* d_psd = out.psd ? out.psd : c->d_psd2[c->psd_cur];
+  if (!out.psd) c->psd_cur = (c->psd_cur + 1) % c->npsd;
   c->prof_call = false;
   c->prof_launch_frames = nframes;
   int st = SS_OK;
@@ -1705,11 +1851,19 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
     spec = spectrogram_container(c);
     if (!spec) return fail(c, SS_ERR_NOMEM, "spectrogram container");
   }
-  if (c->deep) {
-    st = run_call_deep(c, d_iq, item_stride, nframes, n_learn, z, spec, d_psd, d_psd_out, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg, cand_cap,
-                       allow_overlap);
+  const CallAsk ask{nframes, n_learn, device_call, out.psd != nullptr, out.rel != nullptr, out.avg != nullptr, spec != nullptr};
+  const CallRoute route = decide_call(*c, c->diag, c->cfg.flags, ask);
+#ifdef SS_DIAG
+  if (!c->diag.route_path.empty())
+    if (FILE* fp = fopen(c->diag.route_path.c_str(), "a")) {
+      print_route(fp, ask, route);
+      fclose(fp);
+    }
+#endif
+  if (route.shape == CALL_DEEP) {
+    st = run_call_deep(c, d_iq, item_stride, ask, route, z, spec, d_psd, out);
     if (st != SS_OK) return st;
-  } else if (c->step_path) {
+  } else if (route.shape != CALL_NON_STEP) {
     ss::Fft8192Args g{};
     ss::ColsArgs gc{};
     FftRole role;
@@ -1722,209 +1876,58 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
       role.cols = &gc;
       role.n = nframes * (c->n >> 13);  // tiles of 8192 points either way: 32 columns x 256 rows, or 8 x 1024
     }
-    // Tile culling for long transforms: the rows kernel leaves the run maxima of every frame and, in a call without learning
-    // frames, writes the ring rows of the batch itself (placed now: moving the ring window drains the deferred stages).
-    // 65536 points, int8 IQ: a call that keeps no plane goes through the radix-8 fold (KIND 8) — decided before the ring is placed,
-    // because a change of form rewrites the window
-    // (one predicate for the three decisions below — fold, dB rows in the ring, no dB plane at all: a device call without learning frames
-    // that hands out no plane and keeps none; and the room for a whole batch's rows in the ring's buffer is ring_place.h's `whole` branch,
-    // a function of the sizes alone, so a fold call knows before the window is rewritten that its rows have a place — a call that has
-    // none takes the four-step form)
-    const bool keeps_no_plane = allow_overlap && n_learn == 0 && !d_psd_out && !d_rel_out && !d_avg_out && !spec && !c->ref_nan &&
-                                !(c->cfg.flags & SS_FLAG_KEEP_PLANES) && c->diag.ring_only;
-    const bool ring_room = nframes < kHistRows || kHistRows + nframes <= c->hist_rows;
-    const bool dif_call = c->dif8 && c->cull_long && c->diag.pipeline && keeps_no_plane && ring_room && !(c->cfg.flags & (SS_FLAG_STREAM_ORDERED | SS_FLAG_REFERENCE_NAN));
-    // ... and the rows the FFT stage of a detect-mode call leaves in the ring are dB values (ring_db_rows): a call of any other kind, and
-    // a call under another ceiling, has them turned into noise-relative rows first
-    const bool db_call = c->cull_long && (!c->cull_fold_only || dif_call) && keeps_no_plane;  // (what ring_only below comes to, but for the room in the ring's buffer)
-    if (c->ring_db_rows > 0 && (!db_call || c->ring_db_thr != z->d_thr)) settle_ring_db(c);
-    set_ring_form(c, dif_call);
+    // The state the route meets, in this order: dB rows a call of another kind (or under another ceiling) finds in the ring are settled,
+    // a change between the fold's row order and bin order rewrites the window, the ring is placed (moving the window drains the deferred
+    // stages) — and only then are the waiting stages asked whether this call's planes clash with theirs.
+    if (c->ring_db_rows > 0 && (!route.db_call || c->ring_db_thr != z->d_thr)) settle_ring_db(c);
+    set_ring_form(c, route.dif_call);
     ss::RowsExtra rx{};
-    bool ring_by_rows = false, ring_only = false;
     const float* ring_rows = nullptr;
-    const bool cull_call = c->cull_long && (!c->cull_fold_only || dif_call);  // (131072 points: only the fold's calls leave run maxima and write the ring themselves)
-    if (cull_call) {
+    if (route.cull_call) {
       rx.smax = c->d_smax;
       rx.smax_mask = c->smax_rows - 1;
       rx.abs0 = (int)(c->abs_frames & 0x3fffffff);
-      if (n_learn == 0) {
+      if (route.ring_by_rows) {
         const RingPlace rp = place_ring(c, nframes);
         rx.thr = z->d_thr;
         rx.hist_out = rp.out;
         rx.first_hist = nframes - kHistRows;
         rx.zero_word = c->d_tlist[c->buf_cur];  // (the list this call's plan appends to; its last reader was the detect stage of the call before last)
-        ring_by_rows = true;
-        // no dB plane at all: a device call that hands out no plane, shorter than the ring, whose rows the new rows kernel writes
-        ring_only = keeps_no_plane && (nframes < kHistRows || rp.batch);
-        if (ring_only && nframes < kHistRows) {
+        if (route.ring_only && nframes < kHistRows) {
           ring_rows = rp.in + (size_t)kHistRows * c->n;  // batch frame f = row H + f of the window being read: right behind it (place_ring)
-        } else if (ring_only) {  // every frame of the batch as a row of the region place_ring reserved; its last H rows are the next call's ring
+        } else if (route.ring_only) {  // every frame of the batch as a row of the region place_ring reserved; its last H rows are the next call's ring
           rx.hist_out = rp.batch;
           rx.first_hist = 0;
           ring_rows = rp.batch;
         }
-        if (ring_only) rx.thr = nullptr;  // ... as dB values: the tiles that are evaluated subtract the ceiling (ring_db_rows)
+        if (route.ring_only) rx.thr = nullptr;  // ... as dB values: the tiles that are evaluated subtract the ceiling (ring_db_rows)
       }
     }
-    if (!ring_only && c->ring_db_rows > 0) settle_ring_db(c);  // (a call that was to keep no plane and found no room for its rows in the ring's buffer)
-    // (SS_FLAG_STREAM_ORDERED / SS_FLAG_REFERENCE_NAN: every stage of the call before the call returns, in order on the public stream)
-    const bool overlap = c->diag.pipeline && n_learn == 0 && !(c->cfg.flags & (SS_FLAG_STREAM_ORDERED | SS_FLAG_REFERENCE_NAN));
     ++c->stats.calls_in_order;
     // A caller that hands the same PSD or avg plane to consecutive calls would have this call's stages write what a
     // deferred stage of the previous call still has to read in the same launch: drain first (no overlap for such callers).
     const size_t plane_bytes = sizeof(float) * (size_t)nframes * (size_t)c->n;
-    const auto clash = [](const void* a, size_t abytes, const void* b, size_t bbytes) {
-      const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-      return a && b && pa < pb + bbytes && pb < pa + abytes;
-    };
     const auto clashes = [&](const ss_ctx::PendDet& p) {
       const size_t pend_bytes = sizeof(float) * (size_t)p.a.nframes * (size_t)c->n;
-      return clash(d_psd, plane_bytes, p.a.psd, pend_bytes) || clash(d_avg_out, plane_bytes, p.emit.avg, pend_bytes) || clash(d_psd, plane_bytes, p.a.rel_out, pend_bytes) ||
-             clash(d_rel_out, plane_bytes, p.a.psd, pend_bytes);
+      return clash(d_psd, plane_bytes, p.a.psd, pend_bytes) || clash(out.avg, plane_bytes, p.emit.avg, pend_bytes) || clash(d_psd, plane_bytes, p.a.rel_out, pend_bytes) ||
+             clash(out.rel, plane_bytes, p.a.psd, pend_bytes);
     };
-    using W = ss_ctx::Waiting;
-    W& w = c->wait;
+    ss_ctx::Waiting& w = c->wait;
     const bool reused = (w.det_planned.have && clashes(w.det_planned.v)) || (w.det_wants_plan.have && clashes(w.det_wants_plan.v));  // (a detect stage that waits for its rows keeps no plane)
-    if (!overlap || reused) flush_stages(c);
-    const bool rows_by_step = c->two_pass || c->rows256_step || c->rows1024x256;
-    // one launch per call (SS_MERGE_65536): calls that keep no dB plane, in one piece, with stages allowed to overlap; any other call
-    // drains what waits in that form and goes the two-launch way
-    // (up to 128 frames: two 64 MiB work buffers in flight are what the Infinity Cache holds beside the rest — 256-frame calls lose a tenth
-    // this way and have two rounds of workgroups per launch anyway, profiles/r04/s34_summary.txt)
-    const bool merged_call = c->merge && (c->rows256_step || c->rows1024x256) && overlap && ring_only && !spec && nframes <= c->merge_max;
-    if (c->merge && !merged_call && w.any_merged()) flush_stages(c);
-    if (dif_call) {
-      if (!ring_only || !rx.hist_out) return fail(c, SS_ERR_INVALID, "internal: a fold call without a place for its rows");
-      ss::Fft8192Args gf{};
-      gf.tabs = ss::Fft8192V2Tables{c->d_tw8v2, c->d_tw8v2 + 256, c->d_tw8v2 + 256 + 384, nullptr, nullptr};
-      gf.db_off = c->db_off;
-      gf.scale = c->cfg.int_scale;
-      gf.psd = rx.hist_out;  // row f - first_hist of this region is frame f's (RowsExtra, fft256_kernels.h)
-      ss::Dif8Front df = ss::dif8_front_of(d_iq, item_stride, c->d_dif8_tab, 1 << c->dif_logq);
-      df.smax = rx.smax;
-      df.smax_mask = rx.smax_mask;
-      df.abs0 = rx.abs0;
-      df.first_hist = rx.first_hist;
-      df.nframes = nframes;
-      df.zero_word = rx.zero_word;
-      FftRole drole;
-      drole.frames = &gf;
-      drole.dif = &df;
-      // (two residues per workgroup: four per frame at radix 8, eight at radix 16. One residue per workgroup for short calls was tried,
-      // measured and removed: 16-frame calls 20.6 against 19.5 us, 32-frame calls 26.0 against 20.3, profiles/r06/s13_summary.txt)
-      drole.n = (c->dif_logq == 4 ? 8 : SS_DIF8_W) * nframes;
-      // the plan of the call before, the planned detect stage (of the call before that) and the emit stage behind it ride on the launch
-      launch_step(c, &drole, w.riding(W::DET | W::EMIT | W::PLAN));
-    } else if (merged_call) {
-      ss::ColsArgs gcm = gc;
-      gcm.work = c->work_cur ? c->d_work2 : c->d_work;
-      FftRole crole;
-      crole.cols = &gcm;
-      crole.n = nframes * (c->n >> 13);
-      launch_step(c, &crole, w.riding(W::ALL));
-    } else if (c->rows256_step) {
-      // 65536 points with tile culling: both halves of the FFT as FFT roles of k_scan_step. What ships (det_lag2, stage_slots.h): plan,
-      // planned detect stage and emit stage on the column launch, nothing on the row launch. SS_DET_LAG2=0: plan and emit stage on the
-      // column launch, the detect stage on the row launch (29.5 us for a launch that takes 17 alone: profiles/r04/s17_summary.txt).
-      const bool det_on_cols = c->det_lag2;
-#ifdef SS_DIAG
-      const bool emit_on_rows = c->diag.emit_on_rows;
-#else
-      const bool emit_on_rows = false;
-#endif
-      // A call of many frames goes through in chunks of 256 (a chunk's work buffer: 128 MiB, still in the Infinity Cache when its row
-      // half reads it: the row half of a 512-frame call took 0.206 us per frame against 0.132, profiles/r04/s28_summary.txt); the
-      // deferred stages ride on the first chunk's launches.
-      const size_t sample = in_bytes_per_sample(c->cfg.in_format);
-      const int chunk = (c->diag.chunk_65536 > 0 && nframes > c->diag.chunk_65536) ? c->diag.chunk_65536 : nframes;
-      for (int f0 = 0; f0 < nframes; f0 += chunk) {
-        const int nf = std::min(chunk, nframes - f0);
-        const bool first = f0 == 0;
-        c->prof_launch_frames = nf;
-        ss::ColsArgs gcc = gc;
-        gcc.iq = static_cast<const char*>(d_iq) + (size_t)f0 * (size_t)item_stride * sample;
-        FftRole crole;
-        crole.cols = &gcc;
-        crole.n = nf * (c->n >> 13);
-        launch_step(c, &crole, w.riding(first ? W::PLAN | (det_on_cols ? W::DET : 0) | (emit_on_rows ? 0 : W::EMIT) : 0));
-        ss::RowsExtra rxc = rx;
-        rxc.abs0 += f0;
-        rxc.first_hist -= f0;                 // (hist_out takes the call's frames >= first_hist; the tile sees chunk-local frame numbers)
-        if (!first) rxc.zero_word = nullptr;  // (the first chunk's launch zeroes the count of the list this call's plan appends to)
-        const ss::Rows256Args gr = rows256_args(c, (ring_only || !d_psd) ? nullptr : d_psd + (size_t)f0 * (size_t)c->n, rxc);
-        FftRole rrole;
-        rrole.rows256 = &gr;
-        rrole.n = nf * 8;
-        launch_step(c, &rrole, w.riding(first ? (det_on_cols ? 0 : W::DET) | (emit_on_rows ? W::EMIT : 0) : 0));
-      }
-    } else if (c->rows1024x256) {
-      // 262144 points (round 6): the 65536-point two-launch pipeline (256-point column tiles as k_scan_step's FFT role); the row half is a launch
-      // of k_fft_rows1024_psd<8> that carries nothing. Calls of more than 64 frames go through in chunks (a chunk's work buffer: 128 MiB).
-      const size_t sample = in_bytes_per_sample(c->cfg.in_format);
-      const int chunk = std::min(nframes, 64);
-      for (int f0 = 0; f0 < nframes; f0 += chunk) {
-        const int nf = std::min(chunk, nframes - f0);
-        const bool first = f0 == 0;
-        c->prof_launch_frames = nf;
-        ss::ColsArgs gcc = gc;
-        gcc.iq = static_cast<const char*>(d_iq) + (size_t)f0 * (size_t)item_stride * sample;
-        gcc.abs0 += f0;  // (the column tiles clear the ring words of THEIR frames' run maxima)
-        FftRole crole;
-        crole.cols = &gcc;
-        crole.n = nf * (c->n >> 13);
-        launch_step(c, &crole, w.riding(first ? W::DET | W::EMIT | W::PLAN : 0));
-        ss::RowsExtra rxc = rx;
-        rxc.abs0 += f0;
-        rxc.first_hist -= f0;
-        if (!first) rxc.zero_word = nullptr;
-        launch_rows1024x256(c, nf, (ring_only || !d_psd) ? nullptr : d_psd + (size_t)f0 * (size_t)c->n, rxc);
-      }
-    } else if (rows_by_step) {
-      // 2^20 points: the column half of call k as a launch of its own (16 columns x 1024 rows per 1024-thread workgroup: too many
-      // threads for a role), then ONE launch of k_scan_step whose FFT role is the ROW half of call k — 8 rows x 1024 points per
-      // 512-thread workgroup — with detect(k - 1) and emit(k - 2) riding on it as they ride on the column launches of the other sizes
-      // A call of many frames goes through in chunks of 16: the work buffer of a chunk (128 MiB) is still in the 256 MiB Infinity
-      // Cache when the chunk's row half reads it — 2.8 us per frame for the row half against 4.1-4.3 when a 32- or 64-frame call's
-      // work buffer has to come back from HBM (profiles/r04/s26_summary.txt). The deferred stages ride on the first chunk's row launch,
-      // the plan of the call before on its column launch.
-      const int chunk = (c->diag.chunk_long > 0 && nframes > c->diag.chunk_long) ? c->diag.chunk_long : nframes;
-      for (int f0 = 0; f0 < nframes; f0 += chunk) {
-        const int nf = std::min(chunk, nframes - f0);
-        c->prof_launch_frames = nf;
-        launch_cols1024(c, d_iq, item_stride, nf, f0);
-        ss::RowsExtra rxc = rx;
-        rxc.abs0 += f0;
-        rxc.first_hist -= f0;                  // (hist_out takes the call's frames >= first_hist; the tile sees chunk-local frame numbers)
-        if (f0 > 0) rxc.zero_word = nullptr;   // (the first chunk's launch zeroes the count of the list this call's plan appends to)
-        float* psd_c = (ring_only || !d_psd) ? nullptr : d_psd + (size_t)f0 * (size_t)c->n;
-        const ss::Rows1024Args gr = rows1024_args(c, psd_c, rxc);
-        FftRole rrole;
-        rrole.rows1024 = &gr;
-        rrole.n = nf * 128;
-        const bool first = f0 == 0;
-        launch_step(c, &rrole, w.riding(first ? W::DET | W::EMIT : 0));
-      }
-    } else
-    launch_step(c, &role, w.riding(W::DET | W::EMIT));
-    w.shift();
-    if (merged_call) {  // this call's row half waits for the next launch; it reads the work buffer this call's column half has just been told to fill
-      ss_ctx::PendRows& rows = w.rows.v;
-      float2* work = c->work_cur ? c->d_work2 : c->d_work;
-      rows.x1024 = c->rows1024x256;
-      if (rows.x1024) {  // (262144 points: 32 row tiles of 8 rows x 1024 points per frame)
-        rows.r1024 = rows1024x256_args(c, nullptr, rx);
-        rows.r1024.work = work;
-        rows.tiles = nframes * 32;
-      } else {
-        rows.r256 = rows256_args(c, nullptr, rx);
-        rows.r256.work = work;
-        rows.tiles = nframes * 8;
-      }
-      w.rows.have = true;
-      c->work_cur ^= 1;
+    if (!route.overlap || reused) flush_stages(c);
+    if (c->merge && !route.merged_call && w.any_merged()) flush_stages(c);
+    switch (route.shape) {
+      case CALL_FOLD: launch_fold(c, route, d_iq, item_stride, nframes, rx); break;
+      case CALL_MERGED: launch_merged(c, route, gc, nframes); break;
+      case CALL_ROWS256_STEP:
+      case CALL_ROWS1024X256:
+      case CALL_TWO_PASS: launch_chunks(c, route, gc, d_iq, item_stride, nframes, d_psd, rx); break;
+      default: launch_step(c, &role, w.riding(route.ride_first)); break;  // (CALL_FRAMES_8192, CALL_COLS_ROWS: the rows below)
     }
-    if (!c->use_fft8192 && !rows_by_step && !dif_call) {
-      st = launch_fft_rows(c, nframes, ring_only ? nullptr : d_psd, rx);
+    w.shift();
+    if (route.merged_call) rows_for_next_launch(c, nframes, rx);
+    if (route.shape == CALL_COLS_ROWS) {
+      st = launch_fft_rows(c, nframes, route.ring_only ? nullptr : d_psd, rx);
       if (st != SS_OK) return st;
     }
     if (spec && !c->spec_in_detect) {
@@ -1932,20 +1935,17 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
       if (st != SS_OK) return st;
     }
     if (spec) spec->count += nframes;
-    if (n_learn > 0) {
-      hipLaunchKernelGGL(ss::k_noise_learn, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, (const float*)d_psd, c->n, n_learn, z->d_thr);
-      if (c->cull || c->cull_long) hipLaunchKernelGGL(ss::k_thr_tilemin, dim3(c->n / 256), dim3(64), 0, c->stream, (const float*)z->d_thr, c->n, z->d_thr + c->n);
-    }
+    launch_learning(c, d_psd, n_learn, z);
     // (det_lag2: this call's detect stage waits for its plan, behind the planned one — which, if there is one, rode on this call's column launch)
-    ss::StageSlot<ss_ctx::PendDet>& slot = w.new_detect(merged_call, c->det_lag2);
-    st = run_backend_fused(c, d_psd, nframes, n_learn, z, c->spec_in_detect ? spec : nullptr, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg, cand_cap, &slot.v);
+    ss::StageSlot<ss_ctx::PendDet>& slot = w.new_detect(route.merged_call, route.det_lag2);
+    st = run_backend_fused(c, d_psd, nframes, n_learn, z, c->spec_in_detect ? spec : nullptr, out, &slot.v);
     if (st != SS_OK) return st;
     slot.have = true;
     ss::DetectArgs& nd = slot.v.a;
-    if (cull_call) {
-      nd.hist_by_fft = ring_by_rows ? 1 : 0;
+    if (route.cull_call) {
+      nd.hist_by_fft = route.ring_by_rows ? 1 : 0;
       nd.tile_list = nullptr;
-      if (ring_only) {  // the batch's rows are in the ring's buffer, as dB values — and so are the newest ring_db_rows rows of the window before them
+      if (route.ring_only) {  // the batch's rows are in the ring's buffer, as dB values — and so are the newest ring_db_rows rows of the window before them
         nd.psd = ring_rows;
         nd.thr = z->d_thr;
         nd.ring_db_from = -c->ring_db_rows;
@@ -1954,37 +1954,9 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
         c->ring_db_rows = std::min(kHistRows, c->ring_db_rows + nframes);
         c->ring_db_thr = z->d_thr;
       }
-      // the plan: which tiles of this call can hold a candidate at all (k_plan_long) — behind the rows kernel, ahead of the
-      // launch that carries the detect stage. Only a stage whose sole products are mask bits and counts is planned.
-      // (the plan of call k rides at the front of call k + 1's column launch: four plan blocks share a column tile's LDS)
-      const bool plan_fused = (rows_by_step || dif_call) && c->diag.plan_fused && overlap;
-      const int plan_cols = ss::plan_long_cols(nframes, nd.shift, c->n / 256, 8, plan_fused ? ss::kPlanFusedFloats : ss::kPlanLongFloats);  // (32 columns per workgroup — whole lines of the two-pass layout — halved the fetches and doubled the time: 128 workgroups are too few, profiles/r04/s6_summary.txt)
-      if (ring_by_rows && !spec && !nd.rel_out && !nd.avg_out && plan_cols > 0) {
-        int* list = c->d_tlist[(c->buf_cur + c->nbuf - 1) % c->nbuf];  // (run_backend_fused has moved buf_cur on: the set this call's mask bits go to)
-        ss::PlanLongArgs pl{};
-        pl.smax = c->d_smax;
-        pl.smax_mask = c->smax_rows - 1;
-        pl.abs0 = rx.abs0;
-        pl.clean_rel = (int)std::max<long long>(c->clean_abs - c->abs_frames, -(1ll << 29));
-        pl.cols = plan_cols;
-        pl.logn = c->logn;
-        pl.list = list;
-        pl.layout = c->two_pass ? 1 : dif_call ? 2 : c->rows1024x256 ? 3 : 0;
-        ss::PlanLongDet pdet = ss::plan_long_det(nd);
-        if (c->plan_all) pdet.planes_out = 1;  // (SS_FLAG_NO_CULL on the fold's context: every tile listed, none tested)
-        if (merged_call || plan_fused) {  // (a merged call's is not ready before the call's row half has run: one launch from now)
-          ss::StageSlot<ss_ctx::PendPlan>& plan = w.new_plan(merged_call);
-          plan.have = true;
-          plan.v.a = pl;
-          plan.v.det = pdet;
-        } else {
-          const int plan_wgs = ss::plan_blocks_of(pdet, pl, c->n);  // (groups past the band's end find no column)
-          SS_LAUNCH_SLOT(c, SS_KSLOT_PLAN, (ss::k_plan_long<21, 21, kFusedTF, 256>), dim3(plan_wgs), dim3(256), 0, pdet, pl);
-        }
-        nd.tile_list = list;
-      }
+      plan_call(c, route, nd, nframes, rx.abs0, spec != nullptr);
     }
-    if (!overlap) flush_stages(c);
+    if (!route.overlap) flush_stages(c);
   } else {
     ++c->stats.calls_in_order;
     st = launch_fft(c, d_iq, item_stride, nframes, d_psd);
@@ -1997,10 +1969,10 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
       spec->count += nframes;
     }
     if (c->fused) {
-      if (n_learn > 0) hipLaunchKernelGGL(ss::k_noise_learn, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, (const float*)d_psd, c->n, n_learn, z->d_thr);
-      st = run_backend_fused(c, d_psd, nframes, n_learn, z, c->spec_in_detect ? spec : nullptr, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg, cand_cap, nullptr);
+      launch_learning(c, d_psd, n_learn, z);
+      st = run_backend_fused(c, d_psd, nframes, n_learn, z, c->spec_in_detect ? spec : nullptr, out, nullptr);
     } else {
-      st = run_backend_unfused(c, d_psd, nframes, n_learn, z, d_rel_out, d_avg_out, d_cand_off, d_cand_idx, d_cand_avg, cand_cap);
+      st = run_backend_unfused(c, d_psd, nframes, n_learn, z, out);
     }
     if (st != SS_OK) return st;
   }
@@ -2020,7 +1992,7 @@ int run_batch(ss_ctx* c, const void* d_iq, long long item_stride, int nframes, i
   c->last_rows_db = ring_only_rows != nullptr;  // (... and whether they hold dB values, from frame last_db_from on)
   c->last_settled_lo = c->last_settled_hi = nullptr;
   c->last_n = nframes;
-  c->last_cand_cap = cand_cap;
+  c->last_cand_cap = out.cand_cap;
   c->last_retunes = c->retunes;
   return SS_OK;
 }
@@ -2469,8 +2441,7 @@ int ss_process_device(ss_ctx* c, const void* d_iq, int32_t nframes, float* d_psd
   int st = get_noise(c, &z);
   if (st != SS_OK) return st;
   const int n_learn = plan_learning(c, z, nframes, nullptr);
-  return run_batch(c, d_iq, (long long)c->n * c->cfg.decim, nframes, n_learn, z, d_psd_db, d_rel_db, d_avg_db, d_cand_off, d_cand_idx,
-                   d_cand_avg, cand_cap, true);
+  return run_batch(c, d_iq, (long long)c->n * c->cfg.decim, nframes, n_learn, z, CallOut{d_psd_db, d_rel_db, d_avg_db, d_cand_off, d_cand_idx, d_cand_avg, cand_cap}, true);
 }
 
 int ss_process(ss_ctx* c, const void* iq, int32_t nframes, const int64_t* t_ms, float* psd_db, float* rel_db, float* avg_db,
@@ -2529,8 +2500,9 @@ int ss_process(ss_ctx* c, const void* iq, int32_t nframes, const int64_t* t_ms, 
     d_rel_plane = c->d_relplane;
   }
   lap("noise state, buffers");
-  st = run_batch(c, c->d_in, (long long)n, nframes, n_learn, z, nullptr, d_rel_plane, (c->fused && avg_db) ? c->d_avg2[c->buf_cur] : nullptr, nullptr,
-                 want_cands ? c->d_cand_idx : nullptr, want_cands && cand_avg ? c->d_cand_avg : nullptr, cand_cap);
+  st = run_batch(c, c->d_in, (long long)n, nframes, n_learn, z,
+                 CallOut{nullptr, d_rel_plane, (c->fused && avg_db) ? c->d_avg2[c->buf_cur] : nullptr, nullptr, want_cands ? c->d_cand_idx : nullptr,
+                         want_cands && cand_avg ? c->d_cand_avg : nullptr, cand_cap});
   if (st != SS_OK) return st;
   lap("run_batch (enqueue)");
   flush_stages(c);  // a work() call hands its results back before it returns

@@ -70,6 +70,7 @@ void check_one(const ss_config& cfg, const Diag& d, const char* what) {
   EXPECT(((cfg.flags & SS_FLAG_SPECTROGRAM) != 0) == (f.spec_n > 0) && (f.spec_n == 0 || f.spec_n * f.spec_m == n));
   EXPECT(f.tw8v2 == (n == 8192 || f.dif8) && f.dif8_tab == f.dif8 && f.win1024 == f.two_pass && (!f.two_pass || n == (1 << 20)));
   EXPECT(!f.x256_tile || f.tw_rowsR);
+  EXPECT(!(f.cull || f.cull_long) || f.step_path);  // (launch_learning: off the step path no call forms the per-tile-column minima of the ceiling)
   EXPECT(!(cfg.flags & SS_FLAG_NO_CULL) || (!f.cull && (!f.cull_long || f.plan_all)));
 }
 
