@@ -59,14 +59,18 @@ def build_lib(force: bool = False, verbose: bool = False, diag: bool = False) ->
 
 HOST_DIR = os.path.join(HERE, "host")
 HOST_LIB = os.path.join(HOST_DIR, "libspecscan_host.so")
+# the recording route above the ABI: the two GPU-free classes and the feed recorder that owns them (specscan_replay --record-out)
+RECORDING_HEADERS = ("range_planner.h", "recording_store.h", "feed_recorder.h")
 
 
 def build_host_lib(force: bool = False, verbose: bool = False) -> str:
-    """g++ -> host/libspecscan_host.so: the host-side signal tracker and the raw dump files (no GPU code)."""
-    srcs = [os.path.join(HOST_DIR, f) for f in ("signal_tracker.cpp", "raw_file.cpp")]
-    deps = srcs + [os.path.join(HOST_DIR, f) for f in ("signal_tracker.h", "raw_file.h")]
+    """g++ -> host/libspecscan_host.so: the host-side signal tracker, the raw dump files, the range planner and the recording
+    store (no GPU code)."""
+    srcs = [os.path.join(HOST_DIR, f) for f in ("signal_tracker.cpp", "raw_file.cpp", "recording_host.cpp")]
+    deps = srcs + [os.path.join(HOST_DIR, f) for f in ("signal_tracker.h", "raw_file.h", *RECORDING_HEADERS)] + [
+        os.path.join(INCLUDE, f) for f in ("specscan_channelizer.h", "specscan_record_feed.h")]
     if force or not os.path.exists(HOST_LIB) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(HOST_LIB):
-        cmd = [shutil.which("g++") or "g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Wextra", "-Wpedantic", "-Werror", "-o", HOST_LIB,
+        cmd = [shutil.which("g++") or "g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Wextra", "-Wpedantic", "-Werror", "-I" + INCLUDE, "-o", HOST_LIB,
                *srcs, "-lpthread"]
         if verbose:
             print(" ".join(cmd))
@@ -82,6 +86,8 @@ def build_replay_tool(force: bool = False, verbose: bool = False) -> str:
     src = os.path.join(HOST_DIR, "replay_main.cpp")
     tracker = os.path.join(HOST_DIR, "signal_tracker.cpp")
     deps = [src, tracker, os.path.join(HOST_DIR, "raw_file.h"), os.path.join(HOST_DIR, "signal_tracker.h"), os.path.join(HERE, "..", "include", "specscan.h"),
+            *[os.path.join(HOST_DIR, f) for f in RECORDING_HEADERS], os.path.join(HERE, "..", "include", "specscan_record_feed.h"),
+            os.path.join(HERE, "..", "include", "specscan_channelizer.h"),
             os.path.join(HERE, "..", "include", "specscan_track_feed.h"), os.path.join(HERE, "..", "include", "specscan_track_sparse.h"),
             os.path.join(HERE, "..", "include", "specscan_spectrogram_feed.h"), LIB]
     if force or not os.path.exists(REPLAY_TOOL) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(REPLAY_TOOL):

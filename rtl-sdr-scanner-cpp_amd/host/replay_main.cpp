@@ -6,7 +6,7 @@
 // dump would (`..._power.raw`, sdr_device.cpp:173-176).
 //
 //   specscan_replay <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse [--bandwidth HZ]]
-//                   [--spectrogram-out FILE [--spectrogram-max-rows R]]
+//                   [--spectrogram-out FILE [--spectrogram-max-rows R]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]
 // Prints one JSON line: frames, batches, candidates, seconds, MS/s (file + PCIe inclusive).
 //
 // --track: the feed is a tracked one (include/specscan_track_feed.h) — every batch is digested on the device behind its chain, and
@@ -20,6 +20,14 @@
 // SS_FLAG_SPECTROGRAM). Frame k carries the time nearbyint(k * period), period = 1000 * N * D / fs ms — the clock the reference's
 // per-frame send gate runs on — and every row a batch closes is written to FILE as its DataController::pushSpectrogram payload
 // (ss_spectrogram_payload) behind its length as a little-endian uint32. The JSON line gains `spectrogram_rows`.
+// --record-out FILE (needs --track or --track-sparse): the transmissions the tracker finds are recorded from the feed's own upload
+// (host/feed_recorder.h: RangePlanner -> srf_record -> RecordingStore; --recorders R slots, default 4; the recording bandwidth is
+// --bandwidth). After each stf_collect the consumer runs the tracker over the batch's frames, posts the keys and hands the frames'
+// lists to the FeedRecorder. With decim != 1 the feed is a whole-item feed (ss_feed_create_items) and the dump is read in whole items
+// of N * D samples: only the recorded ranges are uploaded a second time. Every published item is written to FILE as its
+// DataController::pushTransmission payload (sc_transmission_payload) behind its length as a little-endian uint32. The JSON line gains
+// `recorded_ranges`, `recorded_samples`, `published_items`, `dropped_items`, `record_h2d_bytes` and `ignored_shifts_max`.
+// --min-time-ms M / --timeout-ms T: Config::recordingMinTime / recordingTimeout of the tracker (2000 / 2000).
 #include <specscan.h>
 #include <specscan_spectrogram_feed.h>
 #include <specscan_track_feed.h>
@@ -31,18 +39,22 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "feed_recorder.h"
 #include "raw_file.h"
 #include "signal_tracker.h"
 
 namespace {
 
 struct Options {
-  std::string path, power_dir, spectrogram_out;
+  std::string path, power_dir, spectrogram_out, record_out;
+  int recorders = 4;
+  int min_time_ms = -1, timeout_ms = -1;  // < 0: TrackerConfig's own
   int spectrogram_max_rows = 8;
   int fft = 0, decim = 0, batch = 1024, depth = 3, learn_frames = -1;
   bool track = false, track_sparse = false;
@@ -78,6 +90,15 @@ bool parse_args(int argc, char** argv, Options* o) {
       o->spectrogram_out = argv[++i];
     } else if (a == "--spectrogram-max-rows") {
       if (!next(&o->spectrogram_max_rows)) return false;
+    } else if (a == "--record-out") {
+      if (i + 1 >= argc) return false;
+      o->record_out = argv[++i];
+    } else if (a == "--recorders") {
+      if (!next(&o->recorders)) return false;
+    } else if (a == "--min-time-ms") {
+      if (!next(&o->min_time_ms) || o->min_time_ms < 0) return false;
+    } else if (a == "--timeout-ms") {
+      if (!next(&o->timeout_ms) || o->timeout_ms < 0) return false;
     } else if (a == "--power-dir") {
       if (i + 1 >= argc) return false;
       o->power_dir = argv[++i];
@@ -87,6 +108,7 @@ bool parse_args(int argc, char** argv, Options* o) {
       return false;
     }
   }
+  if (!o->record_out.empty() && !o->track) return false;  // nothing to record without the tracker's lists
   return !o->path.empty();
 }
 
@@ -95,7 +117,7 @@ bool parse_args(int argc, char** argv, Options* o) {
 int main(int argc, char** argv) {
   Options opt;
   if (!parse_args(argc, argv, &opt)) {
-    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R]]\n", argv[0]);
+    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]\n", argv[0]);
     return 2;
   }
   specscan::RawFileInfo info;
@@ -125,9 +147,11 @@ int main(int argc, char** argv) {
     return 1;
   }
   const bool want_power = !opt.power_dir.empty();
+  const bool want_record = !opt.record_out.empty();
+  const bool items = want_record && cfg.decim != 1;  // the slots keep the whole items: the recorder has the stream between the frames
   ss_feed* feed = nullptr;
-  if (ss_feed_create(ctx, opt.depth, 1 << 20, want_power ? 1 : 0, &feed) != SS_OK) {
-    fprintf(stderr, "ss_feed_create: %s\n", ss_last_error(ctx));
+  if ((items ? ss_feed_create_items : ss_feed_create)(ctx, opt.depth, 1 << 20, want_power ? 1 : 0, &feed) != SS_OK) {
+    fprintf(stderr, "%s: %s\n", items ? "ss_feed_create_items" : "ss_feed_create", ss_last_error(ctx));
     ss_destroy(ctx);
     return 1;
   }
@@ -138,6 +162,8 @@ int main(int argc, char** argv) {
   tc.start_level = cfg.start_level;
   tc.grouping_y = cfg.grouping_y;
   tc.group_size = (int)((((long long)opt.bandwidth * cfg.fft_size) + info.sample_rate - 1) / info.sample_rate);  // sdr_device.cpp:151
+  if (opt.min_time_ms >= 0) tc.min_time_ms = opt.min_time_ms;
+  if (opt.timeout_ms >= 0) tc.timeout_ms = opt.timeout_ms;
   if (opt.track) {
     stf_config tcfg{STF_ABI_VERSION, tc.group_size, cfg.start_level, 4096};
     if ((opt.track_sparse ? stf_create_sparse(feed, &tcfg, &tracked) : stf_create(feed, &tcfg, &tracked)) != SS_OK) {
@@ -163,8 +189,27 @@ int main(int argc, char** argv) {
   }
   const double frame_period_ms = 1000.0 * cfg.fft_size * cfg.decim / info.sample_rate;
   int rc = 0;
+  FILE* record_file = nullptr;
   try {
-    specscan::RawIqReader reader(opt.path, info.kind, cfg.fft_size, cfg.decim);
+    // the recorder last: its srf_ctx goes before the feed does
+    bool record_failed = false;
+    std::vector<uint8_t> record_payload;
+    std::unique_ptr<specscan::FeedRecorder> recorder;
+    if (want_record) {
+      if (!(record_file = fopen(opt.record_out.c_str(), "wb"))) throw std::runtime_error(opt.record_out + ": cannot open for writing");
+      recorder = std::make_unique<specscan::FeedRecorder>(
+          feed, opt.bandwidth, opt.recorders, (int64_t)cfg.fft_size * cfg.decim, info.frequency,
+          [&](int64_t time_ms, int32_t frequency, int32_t sample_rate, const int8_t* iq, int nsamples) {
+            const int len = sc_transmission_payload((uint64_t)time_ms, frequency, sample_rate, iq, nsamples, nullptr, 0);
+            if (len > 0) record_payload.resize((size_t)len);
+            const uint8_t head[4] = {(uint8_t)len, (uint8_t)(len >> 8), (uint8_t)(len >> 16), (uint8_t)(len >> 24)};
+            if (len <= 0 || sc_transmission_payload((uint64_t)time_ms, frequency, sample_rate, iq, nsamples, record_payload.data(), len) != len ||
+                fwrite(head, 1, 4, record_file) != 4 || fwrite(record_payload.data(), 1, (size_t)len, record_file) != (size_t)len)
+              record_failed = true;
+          });
+    }
+    // whole items of N * D samples for a whole-item feed, as replay.replay_file(items=True) reads them
+    specscan::RawIqReader reader(opt.path, info.kind, items ? cfg.fft_size * cfg.decim : cfg.fft_size, items ? 1 : cfg.decim);
     specscan::RawFileSink power(sizeof(float) * (size_t)cfg.fft_size);  // FileSink<float>(fftSize, false)
     if (want_power) {
       std::tm tm{};
@@ -216,6 +261,7 @@ int main(int argc, char** argv) {
     long long frames = 0, batches = 0, candidates = 0, transmissions = 0, tracked_frames = 0, spectrogram_rows = 0;
     std::vector<uint8_t> payload;
     specscan::SignalTracker tracker(tc);
+    std::vector<specscan::RangePlanner::Frame> lists;  // the tracker's list of every frame of the batch, for the recorder
     const auto frame_time_ms = [&](long long index) { return (int64_t)(1000ll * index * cfg.fft_size * cfg.decim / info.sample_rate); };
     for (;;) {
       {
@@ -237,11 +283,20 @@ int main(int argc, char** argv) {
                                                       d.nwatch, d.peak_idx + (size_t)f * d.nwatch, d.peak_avg + (size_t)f * d.nwatch);
           if (!tx) why = "a tracked key is missing from the digest's watch list";
           else transmissions += (long long)tx->size();
+          if (tx && recorder) {
+            if (lists.size() <= (size_t)f) lists.resize((size_t)f + 1);
+            lists[(size_t)f] = *tx;
+          }
         }
         if (why.empty()) {
           const std::vector<int> keys = tracker.signalKeys();
           tracked_frames += r.nframes;
           if (stf_post_keys(tracked, d.seq, keys.data(), (int32_t)keys.size()) != SS_OK) why = stf_last_error(tracked);
+        }
+        if (why.empty() && recorder) {  // plan the lists, record the ranges from the held batch (or let it go), publish what flushed
+          lists.resize((size_t)r.nframes);
+          if (!recorder->record(lists, frames, frame_time_ms)) why = recorder->error();
+          else if (record_failed) why = "writing the transmission payloads failed";
         }
       } else if (ss_feed_collect(feed, &r) != SS_OK) {
         why = ss_last_error(ctx);
@@ -292,6 +347,7 @@ int main(int argc, char** argv) {
       failed = true;
       error = stf_last_error(tracked);
     }
+    if (recorder) recorder->finish();  // the end of the stream stops every recording
     if (failed) {
       fprintf(stderr, "replay failed: %s\n", error.c_str());
       rc = 1;
@@ -303,12 +359,20 @@ int main(int argc, char** argv) {
       if (tracked) printf(", \"transmissions\": %lld, \"tracked_frames\": %lld", transmissions, tracked_frames);
       if (opt.track_sparse) printf(", \"tiles_evaluated\": %llu, \"tiles_in_batches\": %llu", (unsigned long long)tiles_evaluated, (unsigned long long)tiles_in_batches);
       if (rows) printf(", \"spectrogram_rows\": %lld", spectrogram_rows);
+      if (recorder) {
+        const auto& c = recorder->counters();
+        printf(", \"recorded_ranges\": %llu, \"recorded_samples\": %llu, \"published_items\": %llu, \"dropped_items\": %llu, "
+               "\"record_h2d_bytes\": %llu, \"ignored_shifts_max\": %llu",
+               (unsigned long long)c.ranges, (unsigned long long)c.samples, (unsigned long long)recorder->publishedItems(),
+               (unsigned long long)recorder->droppedItems(), (unsigned long long)c.h2d_bytes, (unsigned long long)c.ignored_max);
+      }
       printf("}\n");
     }
   } catch (const std::exception& e) {
     fprintf(stderr, "%s\n", e.what());
     rc = 1;
   }
+  if (record_file && fclose(record_file) != 0) rc = 1;
   if (rows_file && fclose(rows_file) != 0) rc = 1;
   sgf_destroy(rows);
   stf_destroy(tracked);

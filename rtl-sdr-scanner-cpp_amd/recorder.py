@@ -163,4 +163,161 @@ class RangePlanner:
         return ranges, ends, flushes
 
 
-__all__ = ["RecordedFeed", "RangePlanner", "SRF_EXPORTS", "SRF_ABI_VERSION", "SC_MAX_RANGES", "bind_record_feed"]
+SRP_EXPORTS = ("srp_create", "srp_destroy", "srp_last_error", "srp_plan", "srp_slots", "srp_ignored")
+SRS_EXPORTS = ("srs_create", "srs_destroy", "srs_item_samples", "srs_feed", "srs_finish", "srs_published", "srs_dropped", "srs_pending_samples",
+               "srs_held_items")
+_PUBLISH_FN = C.CFUNCTYPE(None, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int8), C.c_int32, C.c_void_p)  # srs_publish_fn
+_FRAME_TIME_FN = C.CFUNCTYPE(C.c_int64, C.c_int64, C.c_void_p)  # srs_frame_time_fn
+_ENDS = ("stop", "batch")  # specscan::RangeEnd
+
+
+def bind_recording_host(lib: C.CDLL) -> C.CDLL:
+    """srp_* and srs_* of host/libspecscan_host.so (host/recording_host.cpp): the C++ RangePlanner and RecordingStore."""
+    if getattr(lib, "_srp_bound", False):
+        return lib
+    i32p = C.POINTER(C.c_int32)
+    lib.srp_create.argtypes = [C.c_int32, C.c_int64]
+    lib.srp_create.restype = C.c_void_p
+    lib.srp_destroy.argtypes = [C.c_void_p]
+    lib.srp_destroy.restype = None
+    lib.srp_last_error.argtypes = [C.c_void_p]
+    lib.srp_last_error.restype = C.c_char_p
+    lib.srp_plan.argtypes = [C.c_void_p, C.c_int32, i32p, i32p, C.POINTER(C.c_uint8), C.POINTER(ScRange), i32p, i32p]
+    lib.srp_plan.restype = C.c_int32
+    lib.srp_slots.argtypes = [C.c_void_p, i32p, i32p]
+    lib.srp_slots.restype = C.c_int32
+    lib.srp_ignored.argtypes = [C.c_void_p, i32p, C.c_int32]
+    lib.srp_ignored.restype = C.c_int32
+    lib.srs_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _PUBLISH_FN, C.c_void_p]
+    lib.srs_create.restype = C.c_void_p
+    lib.srs_destroy.argtypes = [C.c_void_p]
+    lib.srs_destroy.restype = None
+    lib.srs_item_samples.argtypes = [C.c_void_p]
+    lib.srs_item_samples.restype = C.c_int32
+    lib.srs_feed.argtypes = [C.c_void_p, C.POINTER(ScRange), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, _FRAME_TIME_FN, C.c_void_p]
+    lib.srs_feed.restype = C.c_int32
+    lib.srs_finish.argtypes = [C.c_void_p]
+    lib.srs_finish.restype = None
+    for name in ("srs_published", "srs_dropped"):
+        getattr(lib, name).argtypes = [C.c_void_p]
+        getattr(lib, name).restype = C.c_uint64
+    for name in ("srs_pending_samples", "srs_held_items"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_int32]
+        getattr(lib, name).restype = C.c_int32
+    lib._srp_bound = True
+    return lib
+
+
+def _host_lib() -> C.CDLL:
+    from .tracker import load_host_library
+    return bind_recording_host(load_host_library())
+
+
+class HostRangePlanner:
+    """specscan::RangePlanner (host/range_planner.h) through srp_*: RangePlanner above restated in C++, the planner
+    ``specscan_replay --record-out`` runs. Same ``plan`` and the same state; a plan of more than SC_MAX_RANGES ranges raises
+    ValueError and changes nothing (the Python class returns it: one srf_record would refuse it)."""
+
+    def __init__(self, channels: int, n: int):
+        self._lib = _host_lib()
+        self._h = self._lib.srp_create(int(channels), int(n))
+        if not self._h:
+            raise ValueError("channels")
+        self.n = int(n)
+        self.channels = int(channels)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.srp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def plan(self, frames):
+        frames = [list(f) for f in frames]
+        off = np.zeros(len(frames) + 1, np.int32)
+        off[1:] = np.cumsum([len(f) for f in frames])
+        shifts = np.array([int(s) for f in frames for s, _ in f] + [0], np.int32)  # (+ one: never an empty array's pointer)
+        flush = np.array([bool(x) for f in frames for _, x in f] + [0], np.uint8)
+        ranges, ends, flushes = (ScRange * SC_MAX_RANGES)(), (C.c_int32 * SC_MAX_RANGES)(), (C.c_int32 * SC_MAX_RANGES)()
+        n = self._lib.srp_plan(self._h, len(frames), off.ctypes.data_as(C.POINTER(C.c_int32)), shifts.ctypes.data_as(C.POINTER(C.c_int32)),
+                               flush.ctypes.data_as(C.POINTER(C.c_uint8)), ranges, ends, flushes)
+        if n < 0:
+            raise ValueError((self._lib.srp_last_error(self._h) or b"").decode())
+        return ([(ranges[i].channel, ranges[i].shift_hz, ranges[i].begin, ranges[i].end) for i in range(n)], [_ENDS[ends[i]] for i in range(n)],
+                [bool(flushes[i]) for i in range(n)])
+
+    @property
+    def slots(self):
+        """[{"rec": bool, "shift": int}, ...] as RangePlanner.slots."""
+        sh, rec = (C.c_int32 * self.channels)(), (C.c_int32 * self.channels)()
+        self._lib.srp_slots(self._h, sh, rec)
+        return [{"rec": bool(rec[k]), "shift": int(sh[k])} for k in range(self.channels)]
+
+    @property
+    def ignored(self):
+        n = self._lib.srp_ignored(self._h, None, 0)
+        out = (C.c_int32 * max(n, 1))()
+        self._lib.srp_ignored(self._h, out, n)
+        return {int(out[i]) for i in range(n)}
+
+
+class HostRecordingStore:
+    """specscan::RecordingStore (host/recording_store.h) through srs_*: the 100 ms items of every slot, gathered from the outputs of
+    planned ranges. ``published`` collects (time_ms, frequency, sample_rate, bytes of the int8 (re,im) samples) in publishing
+    order; ``frame_time`` maps an absolute frame index to ms."""
+
+    def __init__(self, channels: int, center_frequency: int, bandwidth: int, stride: int, frame_time):
+        self._lib = _host_lib()
+        self.published = []
+        self._frame_time = frame_time
+        self._publish_cb = _PUBLISH_FN(lambda t, f, rate, iq, n, _u: self.published.append((int(t), int(f), int(rate), C.string_at(iq, 2 * n))))
+        self._time_cb = _FRAME_TIME_FN(lambda frame, _u: int(self._frame_time(int(frame))))
+        self._h = self._lib.srs_create(int(channels), int(center_frequency), int(bandwidth), int(stride), self._publish_cb, None)
+        if not self._h:
+            raise ValueError("channels, bandwidth or stride")
+        self.item_samples = int(self._lib.srs_item_samples(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.srs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def feed(self, rng, end: str, flush: bool, iq_i8: np.ndarray, first_frame: int):
+        """rng: (channel, shift_hz, begin, end); iq_i8: the range's outputs, int8 [count, 2]."""
+        a = np.ascontiguousarray(iq_i8, np.int8).reshape(-1, 2)
+        r = ScRange(*(int(v) for v in rng))
+        if self._lib.srs_feed(self._h, C.byref(r), _ENDS.index(end), int(bool(flush)), a.ctypes.data if len(a) else None, len(a), int(first_frame),
+                              self._time_cb, None) != 0:
+            raise ValueError("srs_feed")
+
+    def finish(self):
+        self._lib.srs_finish(self._h)
+
+    @property
+    def dropped(self) -> int:
+        return int(self._lib.srs_dropped(self._h))
+
+    @property
+    def published_items(self) -> int:
+        return int(self._lib.srs_published(self._h))
+
+    def pending_samples(self, slot: int) -> int:
+        return int(self._lib.srs_pending_samples(self._h, int(slot)))
+
+    def held_items(self, slot: int) -> int:
+        return int(self._lib.srs_held_items(self._h, int(slot)))
+
+
+__all__ = ["RecordedFeed", "RangePlanner", "HostRangePlanner", "HostRecordingStore", "SRF_EXPORTS", "SRF_ABI_VERSION", "SRP_EXPORTS", "SRS_EXPORTS",
+           "SC_MAX_RANGES", "bind_record_feed", "bind_recording_host"]
