@@ -34,8 +34,9 @@ def needs_build(lib: str = LIB) -> bool:
 
 
 def build_variant(tag: str, defines, force: bool = False, verbose: bool = False) -> str:
-    """A/B builds for the measurement scripts: the diagnostics build with extra -D switches (cache-policy bits of the frame
-    loads and so on) -> scripts/ab/libspecscan_<tag>.so (git-ignored; travels to the GPU box). Never loaded by the product."""
+    """A/B builds for the measurement scripts: the diagnostics build of this tree, with extra -D switches where an experiment adds
+    one (the sources define none of their own any more) -> scripts/ab/libspecscan_<tag>.so (git-ignored; travels to the GPU box).
+    How a parent tree's library gets built for a comparison (bench.py --lib). Never loaded by the product."""
     out_dir = os.path.join(HERE, "..", "scripts", "ab")
     os.makedirs(out_dir, exist_ok=True)
     lib = os.path.abspath(os.path.join(out_dir, f"libspecscan_{tag}.so"))

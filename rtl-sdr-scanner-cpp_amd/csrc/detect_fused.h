@@ -35,29 +35,10 @@
 #include "fft256_kernels.h"
 #include "fft8192_v2.h"
 
-// Cache policy of the detect tiles' row loads: 0 = default, 1 = non-temporal (A/B builds)
-#ifndef SS_DET_NT
-#define SS_DET_NT 0
-#endif
-
-// 8192 points, deep pipelining: the averaging tiles whose first rows are halo frames on a straight-line path of their own (1), or on the
-// general path like every non-steady tile (0: ships). Measured in round 6 (profiles/r06/s16_summary.txt, alternating runs, 264 GPU tests
-// green with it): 23.2-23.6 against 23.0-23.1 us per step in 200 steps, 26.2-26.8 against 26.2-26.7 in 20, 31.3 against 31.2 with every
-// tile evaluated — nothing: neither the step nor the drain's detect launch (21.0 / 14.9 us either way) is as long as its slowest tile.
-// Build-time so that the two can be timed against each other (scripts/build_ab.py: steadyhalo).
-#ifndef SS_STEADY_HALO
-#define SS_STEADY_HALO 0
-#endif
-
 namespace ss {
 
-__device__ __forceinline__ float load_row_value(const char* p) {
-#if SS_DET_NT
-  return __builtin_nontemporal_load(reinterpret_cast<const float*>(p));
-#else
-  return *reinterpret_cast<const float*>(p);
-#endif
-}
+// The detect tiles' row loads, default cache policy (tried: non-temporal — no gain)
+__device__ __forceinline__ float load_row_value(const char* p) { return *reinterpret_cast<const float*>(p); }
 
 // Tile culling (8192-point frames): a tile that provably holds no candidate need not read its 36 x 276 rel values at all. The
 // bound: the FFT role leaves, per frame and 256-bin tile column, the maximum dB value M_g over the column's bins and 32 more on
@@ -166,7 +147,7 @@ struct DetectArgs {
   // Written by the plan role (plan_tiles), consumed by the workgroups of the same launch (list_pair), the header set back to
   // zero by the call's emit stage.
   int* live;
-  // Tile culling, long transforms (N = 256 x N2; k_plan_long below): [0] = how many tiles must be evaluated, [1 ...] = their
+  // Tile culling, long transforms (N = 256 x N2; plan_long.h: k_plan_long): [0] = how many tiles must be evaluated, [1 ...] = their
   // numbers, written by a launch of its own between the call's FFT and detect stages; null = every tile. hist_by_fft: no tile
   // writes ring rows — the FFT stage has written those of this batch itself (long transforms: fft256_kernels.h, RowsExtra), or
   // nobody needs them before the pipeline is drained, which then writes them from the call's PSD plane (8192 points, deep
@@ -345,18 +326,16 @@ __device__ __forceinline__ void plan_tiles(const DetectArgs& a, int seg, int col
     // (eight loads in flight per trip: one after the other — load, wait, store, sixteen times for a 1024-frame batch — the copy alone
     // took the plan workgroups 8-13 us, and the launch's frame workgroups are through after 12: they wait for this list)
     // (round 6 tried sixteen at a time — ONE round trip for a 1024-frame batch: 23.2 against 22.8-23.1 us per step in alternating runs,
-    // profiles/r06/s4_summary.txt: no gain, the frame workgroups do not wait for the plan as a rule; SS_PLAN_COPY_LOADS=16 keeps the form)
+    // profiles/r06/s4_summary.txt: no gain, the frame workgroups do not wait for the plan as a rule)
+    constexpr int kPlanCopyLoads = 8;
     float hm = 0.0f;
     if (lane < before) hm = a.halo_segsum[col * kHaloSegPitch + (a.halo_rows - before) + lane];
-#ifndef SS_PLAN_COPY_LOADS  // (A/B builds, scripts/build_ab.py: 16 = one trip)
-#define SS_PLAN_COPY_LOADS 8
-#endif
-    for (int fb = 0; fb < nframes; fb += 64 * SS_PLAN_COPY_LOADS) {
-      float v[SS_PLAN_COPY_LOADS];
+    for (int fb = 0; fb < nframes; fb += 64 * kPlanCopyLoads) {
+      float v[kPlanCopyLoads];
 #pragma unroll
-      for (int u = 0; u < SS_PLAN_COPY_LOADS; ++u) v[u] = src[min(fb + 64 * u + lane, nframes - 1)];
+      for (int u = 0; u < kPlanCopyLoads; ++u) v[u] = src[min(fb + 64 * u + lane, nframes - 1)];
 #pragma unroll
-      for (int u = 0; u < SS_PLAN_COPY_LOADS; ++u) {
+      for (int u = 0; u < kPlanCopyLoads; ++u) {
         const int f = fb + 64 * u + lane;
         if (f < nframes) mine[at(f)] = v[u];
       }
@@ -500,557 +479,22 @@ __global__ __launch_bounds__(64) void k_thr_tilemin(const float* __restrict__ th
   if (lane == 0) tilemin[c] = m;
 }
 
-// Tile culling for long transforms (N = 256 x N2: 65536 points and up, 256 and more tile columns). Same idea as plan_tiles — a
-// tile that provably holds no candidate is not evaluated — from what the rows kernel of the FFT stage left per frame and 32-bin
-// run (RowsExtra::smax, a ring over the frames since the last reset, so that the tile's rows from BEFORE the batch are covered
-// too: a 16-frame call of 2^20-point rows has no others). The bound: with M_g the largest dB value of frame g over the tile's 256
-// bins and one run on either side, and m the minimum of the noise ceiling over the same bins (thr_tilemin), every rel value of
-// frame g in reach of the tile is <= M_g - m, so the 21 x 21 mean that ends at frame f is <= mean(M_{f-20} .. M_f) - m: the tile
-// is dropped when that stays below start_level - kCullMargin for each of its frames (the margin covers the fp32 sums on either
-// side: < 0.01 dB). A frame of zeros (M = -inf) makes the bound -inf for every window that holds it — those produce no candidate
-// either — and a NaN anywhere makes the tile "cannot tell": evaluated. A tile is only tested when all its rows are frames since
-// `clean_rel` (batch-relative, <= 0): no learning frame among them, one noise ceiling for all of them, the averager past its
-// warm-up. The ring rows such a tile would have written are written by the rows kernel itself (RowsExtra::hist_out), its mask
-// words are zero already (EmitArgs::clear_masks). The launch is a stage of its own between the call's rows kernel and the launch
-// that carries its detect stage: kernel boundaries order everything, the lists need no hand-over protocol.
-// A workgroup takes C tile columns with all their frame tiles: every thread first reduces (column, frame) pairs to M
-// (ten ring values each) into LDS, then thread (column, frame tile) slides the 21-frame sum over its 16 frames; the tiles to be
-// evaluated — numbers in detect_tile's numbering — are appended to ONE list (list[0] = count, zeroed before the launch; one
-// atomic per workgroup), so that the detect role can spread whatever there is evenly over a fixed number of workgroups: a
-// workgroup per tile pair, leaving at once when the pair is culled, cost the launch 11 us in DISPATCH alone (1024 workgroups
-// of eight waves take the hardware that long to start). The order of the list depends on the scheduling, the
-// results do not: tiles touch disjoint mask words, and the per-frame counts are integer sums.
-struct PlanLongArgs {
-  const float* smax;
-  int smax_mask;
-  int abs0;       // frames since the last reset before this batch
-  int clean_rel;  // first batch-relative frame (<= 0 in a call without learning frames) from which every row qualifies
-  int cols;       // C: tile columns per workgroup
-  int logn;
-  int* list;
-  // 0: the ring holds dB values where k_fft_rows256_psd puts them (rows_smax_index); 1: 2^20 points in two passes
-  // (fft1024_kernels.h): max_key values at rows1024_smax_index(run) — [k1 group][k2], gathered by atomic maxima;
-  // 2: 65536 points by the radix-8 fold (fft65536_dif8.h): value g of tile column c is the largest dB value among the column's bins
-  // of residue g, at [g][c] — a column's neighbours then count with all eight of their values, not with their nearest run;
-  // 3: 262144 points as 256 columns x 1024-point rows (round 6, fft1024_kernels.h: fft_rows1024_tile<8>): max_key values of the eight
-  // 32-bin runs of tile column c at [run][c] (rows1024x256_smax_index), gathered by atomic maxima like layout 1's — planned by
-  // plan_x256_run below (a block per 32 columns x one frame tile), not by plan_long_run
-  int layout;
-};
-constexpr int kPlanLongFloats = 8192;  // LDS of a plan workgroup: C x (16 nft + 20) values of M
-// max_c: 8, or 32 for the two-pass layout of 2^20 points — there a workgroup's columns are consecutive floats of a frame's row of
-// the ring, and 32 of them are a whole 128-byte line (with 8 the four workgroups that share a line each fetched all of it:
-// 5.9 against 3.0 MB per launch, 12 against 7 us, profiles/r04/s4_summary.txt)
-__host__ __device__ inline int plan_long_cols(int nframes, int shift, int tile_cols, int max_c = 8, int max_floats = 8192) {  // 0: the stage cannot be planned
-  const int nft = (nframes + shift + 15) / 16, rows = 16 * nft + 20;
-  int c = tile_cols / 256 > 1 ? tile_cols / 256 : 1;  // at least 256 workgroups where there are that many columns
-  if (max_c > 8) c = max_c;
-  if (c > max_c) c = max_c;
-  if (c > max_floats / rows) c = max_floats / rows;
-  if (nft > 0 && c > 256 / nft) c = 256 / nft;
-  return c;
-}
-
-// which tile columns a plan workgroup takes: layout 0 — (wc, d0): the columns whose unshifted number is wc + nsub d, d = d0 .. d0 + C;
-// layout 1 — the columns 4 k2 + wc for k2 = d0 .. d0 + C, the 32 / C workgroups whose columns share the 128-byte lines of a frame's row
-// of the ring in consecutive slots of ONE XCD (block b runs on XCD b mod 8)
-__host__ __device__ inline void plan_long_block(int layout, int block, int C, int lognsub, int* wc, int* d0) {
-  if (layout == 2) {  // C consecutive columns (consecutive floats of each of the eight residue rows)
-    *wc = 0;
-    *d0 = block * C;
-  } else if (layout) {
-    const int M = (C <= 32 && (32 % C) == 0) ? 32 / C : 1;
-    const int xcd = block & 7, slot = block >> 3;
-    *wc = xcd & 3;
-    *d0 = ((((slot / M) << 1) | (xcd >> 2)) * M + slot % M) * C;
-  } else {
-    *wc = block & ((1 << lognsub) - 1);
-    *d0 = (block >> lognsub) * C;
-  }
-}
-__host__ __device__ inline int plan_long_blocks(int layout, int C, int n) {  // workgroups of the plan launch
-  if (!layout || layout == 2) return (n >> 16) * ((256 + C - 1) / C);
-  const int line_groups = (C <= 32 && 32 % C == 0) ? 32 / C : 1;
-  return 4 * ((((1024 + C - 1) / C + 2 * line_groups - 1) / (2 * line_groups)) * (2 * line_groups));
-}
-
-// What the plan needs of the call's DetectArgs (the whole struct is 200 bytes of kernel arguments the column launch of a
-// 2^20-point frame — whose first workgroups may run the plan of the call before, k_fft_cols1024_plan — has no use for).
-struct PlanLongDet {
-  int n, nframes, shift, n_learn;
-  int planes_out;  // a rel or avg plane is wanted (or SS_FLAG_NO_CULL on the fold's context, ss_ctx::plan_all): nothing is tested, every tile is listed
-  float start_level;
-  const float* thr_tilemin;
-  unsigned long long* stats;
-};
-__host__ __device__ inline PlanLongDet plan_long_det(const DetectArgs& d) {
-  PlanLongDet a{};
-  a.n = d.n;
-  a.nframes = d.nframes;
-  a.shift = d.shift;
-  a.n_learn = d.n_learn;
-  a.planes_out = (d.rel_out || d.avg_out) ? 1 : 0;
-  a.start_level = d.start_level;
-  a.thr_tilemin = d.thr_tilemin;
-  a.stats = d.stats;
-  return a;
-}
-constexpr int kPlanLongInts = 16;  // bookkeeping words of a plan block behind its values of M
-
-// One plan block: 256 threads (`tid`), `block` = its number (what blockIdx.x is for k_plan_long), `mrow` = room for C x (16 nft + 20)
-// floats, `book` = kPlanLongInts ints. Every __syncthreads() below is reached by all threads of the workgroup whatever the block
-// finds: several blocks may share a workgroup (k_fft_cols1024_plan: four of them in 1024 threads).
-template <int G, int GX, int TF, int TB_ = 256>
-__device__ __forceinline__ void plan_long_run(const PlanLongDet& a, const PlanLongArgs& p, int block_no, int tid, float* __restrict__ mrow, int* __restrict__ book) {
-  using T = DetectTile<G, GX, TF, TB_>;
-  constexpr int TB = T::TB;
-  static_assert(TB == 256 && T::A <= 32 && TF == 16 && G == 21, "eight 32-bin runs per tile column, one more on either side");
-  int* wave_cnt = book;             // [4]
-  int* stat_cnt = book + 4;         // [4][2]
-  int* list_base_p = book + 12;
-  const int n = a.n, nframes = a.nframes;
-  const int tiles_per_row = n / TB, groups = n >> 5;
-  const int nft = (nframes + a.shift + TF - 1) / TF;
-  const int rows = TF * nft + (G - 1);  // frames [-shift - 20, 16 nft - shift) of the batch's frame numbering
-  // this workgroup's C tile columns: the ones whose run maxima lie side by side in a frame's row of smax (rows_smax_index: the
-  // same c, consecutive d) — any C columns would do, these are read with 32-byte requests instead of 4-byte ones
-  const int C = p.cols, lognsub = p.logn - 16;
-  // layout 0: workgroup (wc, d0) takes the columns whose unshifted number is wc + nsub d; layout 1: the columns 4 k2 + wc of C
-  // consecutive k2 — either way the ones whose maxima lie side by side in a frame's row of the ring
-  // (layout 1: the 32 / C workgroups whose columns share the 128-byte lines of the ring are consecutive slots of ONE XCD — block b
-  // runs on XCD b mod 8 — as they are in layout 0 by construction; spread over two XCDs they fetched every line twice: 12 against
-  // 7 us per call, profiles/r04/s4_summary.txt)
-  int wc, d0;
-  plan_long_block(p.layout, block_no, C, lognsub, &wc, &d0);
-  const auto column = [&](int i) {
-    if (p.layout == 2) return d0 + i < 256 ? d0 + i : tiles_per_row;
-    if (p.layout) return d0 + i < 1024 ? 4 * (d0 + i) + wc : tiles_per_row;
-    return d0 + i < 256 ? (wc + ((d0 + i) << lognsub)) ^ (tiles_per_row >> 1) : tiles_per_row;
-  };
-  for (int e = tid; e < C * rows; e += 256) {
-    const int i = e % C, r = e / C, col = column(i);
-    float m = -__builtin_inff();
-    if (col < tiles_per_row) {
-      const int frame = r - a.shift - (G - 1);
-      const float* row = p.smax + ((size_t)((p.abs0 + frame) & p.smax_mask) * groups);
-      // the column's eight runs, the last run of the column below and the first of the one above (the band's edges: its own once more)
-      float v[10];
-      if (p.layout == 2) {
-        float lo = -__builtin_inff(), hi = -__builtin_inff();  // (this layout's values never hold a NaN: fft8192_v2.h takes the maxima with fmaxf)
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-          v[g] = row[256 * g + col];
-          lo = fmaxf(lo, row[256 * g + (col > 0 ? col - 1 : col)]);
-          hi = fmaxf(hi, row[256 * g + (col + 1 < tiles_per_row ? col + 1 : col)]);
-        }
-        v[8] = lo;
-        v[9] = hi;
-      } else if (p.layout) {
-        const unsigned* krow = reinterpret_cast<const unsigned*>(row);
-#pragma unroll
-        for (int g = 0; g < 8; ++g) v[g] = max_key_value(krow[rows1024_smax_index(8 * col + g)]);
-        v[8] = max_key_value(krow[rows1024_smax_index(col > 0 ? 8 * col - 1 : 8 * col)]);
-        v[9] = max_key_value(krow[rows1024_smax_index(col + 1 < tiles_per_row ? 8 * col + 8 : 8 * col + 7)]);
-      } else {
-#pragma unroll
-      for (int g = 0; g < 8; ++g) v[g] = row[rows_smax_index(col, g, p.logn)];
-      v[8] = row[col > 0 ? rows_smax_index(col - 1, 7, p.logn) : rows_smax_index(col, 0, p.logn)];
-      v[9] = row[col + 1 < tiles_per_row ? rows_smax_index(col + 1, 0, p.logn) : rows_smax_index(col, 7, p.logn)];
-      }
-      bool bad = false;
-#pragma unroll
-      for (int g = 0; g < 10; ++g) {
-        bad = bad || (v[g] != v[g]);
-        m = fmaxf(m, v[g]);
-      }
-      if (bad) m = __builtin_nanf("");
-    }
-    mrow[i * rows + r] = m;
-  }
-  __syncthreads();
-  bool live = false, tested = false;
-  int block = 0;
-  if (tid < C * nft && column(tid / nft) < tiles_per_row) {
-    const int cl = tid / nft, ft_seq = tid % nft;
-    const int ft = (ft_seq + nft - 1) % nft;
-    const int f0 = ft * TF - a.shift;
-    block = ft_seq * tiles_per_row + column(cl);
-    live = true;
-    if (a.n_learn == 0 && f0 - (G - 1) >= p.clean_rel && !a.planes_out) {
-      tested = true;
-      const float* mr = mrow + cl * rows + ft * TF;  // mr[k] = M of frame f0 - 20 + k
-      float best = -__builtin_inff();
-      bool unsure = false;
-#pragma unroll
-      for (int j = 0; j < TF; ++j) {
-        float sum = 0.0f;
-#pragma unroll
-        for (int k = 0; k < G; ++k) sum += mr[j + k];
-        if (f0 + j >= 0 && f0 + j < nframes) {  // the frames of this batch the tile answers for
-          unsure = unsure || (sum != sum);
-          best = fmaxf(best, sum);
-        }
-      }
-      const float bound = best * (1.0f / (float)G) - a.thr_tilemin[column(cl)];
-      live = unsure || !(bound < a.start_level - kCullMargin);  // (a NaN difference: live)
-    }
-  }
-  // this workgroup's list, in thread order
-  const int lane = tid & 63, w = tid >> 6;
-  const unsigned long long mask = __ballot(live);
-  if (lane == 0) wave_cnt[w] = __popcll(mask);
-  if (a.stats) {  // ss_get_stats: one pair of additions per workgroup (below), to the copy of its block index
-    const int n_tested = __popcll(__ballot(tested)), n_culled = __popcll(__ballot(tested && !live));
-    if (lane == 0) {
-      stat_cnt[2 * w] = n_tested;
-      stat_cnt[2 * w + 1] = n_culled;
-    }
-  }
-  __syncthreads();
-  int base = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    base += k < w ? wave_cnt[k] : 0;
-    total += wave_cnt[k];
-  }
-  if (tid == 0) *list_base_p = total ? atomicAdd(&p.list[0], total) : 0;
-  if (tid == 1 && a.stats) {
-    const int nt = stat_cnt[0] + stat_cnt[2] + stat_cnt[4] + stat_cnt[6], nc = stat_cnt[1] + stat_cnt[3] + stat_cnt[5] + stat_cnt[7];
-    if (nt) {
-      atomicAdd(stat_word(a.stats, kStatTested), (unsigned long long)nt);
-      atomicAdd(stat_word(a.stats, kStatCulled), (unsigned long long)nc);
-    }
-  }
-  __syncthreads();
-  if (live) p.list[1 + *list_base_p + base + __popcll(mask & ((1ull << lane) - 1ull))] = block;
-}
-
-// The plan for the radix-8 fold's rows (layout 2): one block = 32 consecutive tile columns x ONE frame tile, 256 threads. What
-// plan_long_run does for this layout — a block per tile column with all its frame tiles — fetched every 128-byte line of the run
-// maxima thirty-two times over (a column's eight values per frame sit in eight different lines, each shared with 31 other columns:
-// 143 MB of L1 fills per 512-frame call) and left all but a few dozen of its threads idle through 336 serial LDS reads; as the first
-// 128 workgroups of the fold's launch it cost a 128-frame call 8 us and a 512-frame call 12-16 (profiles/r05/s8_summary.txt). Here:
-//   1  R[colx][row] = max over the eight residues of the run maxima of column colx (34 of them: the block's 32 and one either side)
-//      and frame row (36: the tile's 16 frames and the 20 before) — lanes along the columns, so a wave's load is one line;
-//   2  M = max(R[col - 1], R[col], R[col + 1]) formed on the fly, S[col][j] = the 21-frame window sum that ends at frame j of the tile
-//      (thread per (col, j): 21 x 3 LDS reads);
-//   3  thread per tile: the largest of its window sums -> the same test, the same list, the same statistics as plan_long_run's.
-// Block b: column group b mod 8 (32 columns: the eight groups of a frame tile are consecutive blocks, one per XCD), frame tile b / 8 in
-// dispatch order (plan_long_run's ft_seq). `lds`: kPlanDif8Floats floats + kPlanLongInts ints behind them.
-// Radix Q = 1 << logq (logq = p.logn - 13: 3 or 4): 32 Q tile columns, Q column groups per frame tile; a run of a residue's row (32 of
-// its bins) spans Q / 8 tile columns.
-constexpr int kPlanDif8Floats = 34 * 37 + 32 * 16;
-__host__ __device__ inline int plan_dif8_blocks(int nframes, int shift, int logq = 3) { return ((nframes + shift + 15) / 16) << logq; }
-template <int G, int GX, int TF, int TB_ = 256>
-__device__ __forceinline__ void plan_dif8_run(const PlanLongDet& a, const PlanLongArgs& p, int block_no, int tid, float* __restrict__ lds, int* __restrict__ book) {
-  static_assert(TB_ == 256 && TF == 16 && G == 21, "the fold's rows: tile columns of 256 bins, tiles of 16 frames");
-  constexpr int ROWS = TF + G - 1, RP = ROWS + 1;  // 36 frame rows per tile, LDS pitch 37
-  float* R = lds;              // [34][RP]
-  float* S = lds + 34 * RP;    // [32][TF]
-  int* wave_cnt = book;        // [4]
-  int* stat_cnt = book + 4;    // [4][2]
-  int* list_base_p = book + 12;
-  const int logq = p.logn - 13, nres = 1 << logq;
-  const int nframes = a.nframes, tiles_per_row = 32 << logq;
-  const int nft = (nframes + a.shift + TF - 1) / TF;
-  const int cg = block_no & (nres - 1), ft_seq = block_no >> logq;
-  const bool in_range = ft_seq < nft;  // (a workgroup's second block may lie past the end: it keeps the barriers company)
-  const int ft = in_range ? (ft_seq + nft - 1) % nft : 0;
-  const int f0 = ft * TF - a.shift;  // batch-relative frame of the tile's first row of outputs
-  const int c0 = 32 * cg;
-  if (in_range) {
-    // (a thread's five entries, eight residues each: forty loads in flight at once. One entry after the other, a residue after the
-    // other, this was forty round trips to L2 beside workgroups that keep the memory system busy — a plan workgroup held its slot for
-    // 14 us of a 128-frame launch and the 32 fold workgroups that had to wait for those slots ended it 7 us late, profiles/r05/s24_*)
-    constexpr int NE = (34 * ROWS + 255) / 256;
-    const float* src[NE];
-    float m[NE];
-#pragma unroll
-    for (int i = 0; i < NE; ++i) {
-      const int e = min(tid + 256 * i, 34 * ROWS - 1);
-      const int colx = e % 34, r = e / 34;
-      const int col = min(max(c0 - 1 + colx, 0), tiles_per_row - 1);  // (the band's edges: the edge column once more)
-      src[i] = p.smax + ((size_t)((p.abs0 + f0 - (G - 1) + r) & p.smax_mask) << (8 + logq)) + (col >> (logq - 3));  // (radix 16: a run of a residue's row covers two tile columns)
-      m[i] = -__builtin_inff();
-    }
-    for (int g0 = 0; g0 < nres; g0 += 8) {
-      float v[NE][8];
-#pragma unroll
-      for (int i = 0; i < NE; ++i)
-#pragma unroll
-        for (int g = 0; g < 8; ++g) v[i][g] = src[i][256 * (g0 + g)];
-#pragma unroll
-      for (int i = 0; i < NE; ++i)
-#pragma unroll
-        for (int g = 0; g < 8; ++g) m[i] = fmaxf(m[i], v[i][g]);  // (the fold's maxima hold no NaN: fft8192_v2.h takes them with fmaxf)
-    }
-#pragma unroll
-    for (int i = 0; i < NE; ++i) {
-      const int e = tid + 256 * i;
-      if (e < 34 * ROWS) R[(e % 34) * RP + e / 34] = m[i];
-    }
-  }
-  __syncthreads();
-  if (in_range) {
-    for (int e = tid; e < 32 * TF; e += 256) {
-      const int cl = e >> 4, j = e & 15;
-      const float *r0 = R + cl * RP + j, *r1 = r0 + RP, *r2 = r1 + RP;
-      float sum = 0.0f;
-#pragma unroll
-      for (int k = 0; k < G; ++k) sum += fmaxf(fmaxf(r0[k], r1[k]), r2[k]);  // M of frame f0 - 20 + j + k
-      S[e] = sum;
-    }
-  }
-  __syncthreads();
-  bool live = false, tested = false;
-  int block = 0;
-  if (in_range && tid < 32) {
-    const int col = c0 + tid;
-    block = ft_seq * tiles_per_row + col;
-    live = true;
-    if (a.n_learn == 0 && f0 - (G - 1) >= p.clean_rel && !a.planes_out) {
-      tested = true;
-      float best = -__builtin_inff();
-      bool unsure = false;
-#pragma unroll
-      for (int j = 0; j < TF; ++j) {
-        const float sum = S[tid * TF + j];
-        if (f0 + j >= 0 && f0 + j < nframes) {  // the frames of this batch the tile answers for
-          unsure = unsure || (sum != sum);
-          best = fmaxf(best, sum);
-        }
-      }
-      const float bound = best * (1.0f / (float)G) - a.thr_tilemin[col];
-      live = unsure || !(bound < a.start_level - kCullMargin);  // (a NaN difference: live)
-    }
-  }
-  // this block's share of the list, in thread order (as plan_long_run)
-  const int lane = tid & 63, w = tid >> 6;
-  const unsigned long long mask = __ballot(live);
-  if (lane == 0) wave_cnt[w] = __popcll(mask);
-  if (a.stats) {
-    const int n_tested = __popcll(__ballot(tested)), n_culled = __popcll(__ballot(tested && !live));
-    if (lane == 0) {
-      stat_cnt[2 * w] = n_tested;
-      stat_cnt[2 * w + 1] = n_culled;
-    }
-  }
-  __syncthreads();
-  int base = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    base += k < w ? wave_cnt[k] : 0;
-    total += wave_cnt[k];
-  }
-  if (tid == 0) *list_base_p = total ? atomicAdd(&p.list[0], total) : 0;
-  if (tid == 1 && a.stats) {
-    const int nt = stat_cnt[0] + stat_cnt[2] + stat_cnt[4] + stat_cnt[6], nc = stat_cnt[1] + stat_cnt[3] + stat_cnt[5] + stat_cnt[7];
-    if (nt) {
-      atomicAdd(stat_word(a.stats, kStatTested), (unsigned long long)nt);
-      atomicAdd(stat_word(a.stats, kStatCulled), (unsigned long long)nc);
-    }
-  }
-  __syncthreads();
-  if (live) p.list[1 + *list_base_p + base + __popcll(mask & ((1ull << lane) - 1ull))] = block;
-}
-
-// The plan for 262144-point frames (layout 3): the fold's decomposition — one block = 32 consecutive tile columns x ONE frame tile, 256
-// threads, a thread's forty loads in one flight — over max_key values at [run g < 8][column < 1024] per frame. Block b: column group
-// b mod 32, frame tile b / 32 in dispatch order. A key of "NaN" (a NaN bin in the run: cannot be bounded) counts as +inf: the tile is
-// evaluated. `lds`: kPlanDif8Floats floats + kPlanLongInts ints behind them.
-__host__ __device__ inline int plan_x256_blocks(int nframes, int shift) { return ((nframes + shift + 15) / 16) << 5; }
-template <int G, int GX, int TF, int TB_ = 256>
-__device__ __forceinline__ void plan_x256_run(const PlanLongDet& a, const PlanLongArgs& p, int block_no, int tid, float* __restrict__ lds, int* __restrict__ book) {
-  static_assert(TB_ == 256 && TF == 16 && G == 21, "tile columns of 256 bins, tiles of 16 frames");
-  constexpr int ROWS = TF + G - 1, RP = ROWS + 1;  // 36 frame rows per tile, LDS pitch 37
-  float* R = lds;              // [34][RP]
-  float* S = lds + 34 * RP;    // [32][TF]
-  int* wave_cnt = book;        // [4]
-  int* stat_cnt = book + 4;    // [4][2]
-  int* list_base_p = book + 12;
-  constexpr int tiles_per_row = 1024;
-  const int nframes = a.nframes;
-  const int nft = (nframes + a.shift + TF - 1) / TF;
-  const int cg = block_no & 31, ft_seq = block_no >> 5;
-  const bool in_range = ft_seq < nft;  // (a workgroup's second block may lie past the end: it keeps the barriers company)
-  const int ft = in_range ? (ft_seq + nft - 1) % nft : 0;
-  const int f0 = ft * TF - a.shift;  // batch-relative frame of the tile's first row of outputs
-  const int c0 = 32 * cg;
-  if (in_range) {
-    constexpr int NE = (34 * ROWS + 255) / 256;
-    const unsigned* src[NE];
-    unsigned m[NE];
-#pragma unroll
-    for (int i = 0; i < NE; ++i) {
-      const int e = min(tid + 256 * i, 34 * ROWS - 1);
-      const int colx = e % 34, r = e / 34;
-      const int col = min(max(c0 - 1 + colx, 0), tiles_per_row - 1);  // (the band's edges: the edge column once more)
-      src[i] = reinterpret_cast<const unsigned*>(p.smax) + ((size_t)((p.abs0 + f0 - (G - 1) + r) & p.smax_mask) << 13) + col;
-    }
-    unsigned v[NE][8];
-#pragma unroll
-    for (int i = 0; i < NE; ++i)
-#pragma unroll
-      for (int g = 0; g < 8; ++g) v[i][g] = src[i][1024 * g];
-#pragma unroll
-    for (int i = 0; i < NE; ++i) {
-      m[i] = 0u;
-#pragma unroll
-      for (int g = 0; g < 8; ++g) m[i] = max(m[i], v[i][g]);  // (order-preserving keys: the NaN key is the largest)
-    }
-#pragma unroll
-    for (int i = 0; i < NE; ++i) {
-      const int e = tid + 256 * i;
-      if (e < 34 * ROWS) R[(e % 34) * RP + e / 34] = m[i] == 0xffffffffu ? __builtin_inff() : max_key_value(m[i]);
-    }
-  }
-  __syncthreads();
-  if (in_range) {
-    for (int e = tid; e < 32 * TF; e += 256) {
-      const int cl = e >> 4, j = e & 15;
-      const float *r0 = R + cl * RP + j, *r1 = r0 + RP, *r2 = r1 + RP;
-      float sum = 0.0f;
-#pragma unroll
-      for (int k = 0; k < G; ++k) sum += fmaxf(fmaxf(r0[k], r1[k]), r2[k]);  // M of frame f0 - 20 + j + k (no NaN among them: see above)
-      S[e] = sum;
-    }
-  }
-  __syncthreads();
-  bool live = false, tested = false;
-  int block = 0;
-  if (in_range && tid < 32) {
-    const int col = c0 + tid;
-    block = ft_seq * tiles_per_row + col;
-    live = true;
-    if (a.n_learn == 0 && f0 - (G - 1) >= p.clean_rel && !a.planes_out) {
-      tested = true;
-      float best = -__builtin_inff();
-      bool unsure = false;
-#pragma unroll
-      for (int j = 0; j < TF; ++j) {
-        const float sum = S[tid * TF + j];
-        if (f0 + j >= 0 && f0 + j < nframes) {  // the frames of this batch the tile answers for
-          unsure = unsure || (sum != sum);  // (+inf and -inf in one window)
-          best = fmaxf(best, sum);
-        }
-      }
-      const float bound = best * (1.0f / (float)G) - a.thr_tilemin[col];
-      live = unsure || !(bound < a.start_level - kCullMargin);  // (a NaN difference: live)
-    }
-  }
-  // this block's share of the list, in thread order (as plan_long_run)
-  const int lane = tid & 63, w = tid >> 6;
-  const unsigned long long mask = __ballot(live);
-  if (lane == 0) wave_cnt[w] = __popcll(mask);
-  if (a.stats) {
-    const int n_tested = __popcll(__ballot(tested)), n_culled = __popcll(__ballot(tested && !live));
-    if (lane == 0) {
-      stat_cnt[2 * w] = n_tested;
-      stat_cnt[2 * w + 1] = n_culled;
-    }
-  }
-  __syncthreads();
-  int base = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    base += k < w ? wave_cnt[k] : 0;
-    total += wave_cnt[k];
-  }
-  if (tid == 0) *list_base_p = total ? atomicAdd(&p.list[0], total) : 0;
-  if (tid == 1 && a.stats) {
-    const int nt = stat_cnt[0] + stat_cnt[2] + stat_cnt[4] + stat_cnt[6], nc = stat_cnt[1] + stat_cnt[3] + stat_cnt[5] + stat_cnt[7];
-    if (nt) {
-      atomicAdd(stat_word(a.stats, kStatTested), (unsigned long long)nt);
-      atomicAdd(stat_word(a.stats, kStatCulled), (unsigned long long)nc);
-    }
-  }
-  __syncthreads();
-  if (live) p.list[1 + *list_base_p + base + __popcll(mask & ((1ull << lane) - 1ull))] = block;
-}
-// workgroups (blocks) of a long transform's plan, whatever its layout
-__host__ __device__ inline int plan_blocks_of(const PlanLongDet& a, const PlanLongArgs& p, int n) {
-  if (p.layout == 3) return plan_x256_blocks(a.nframes, a.shift);
-  if (p.layout == 2) return plan_dif8_blocks(a.nframes, a.shift, p.logn - 13);
-  return plan_long_blocks(p.layout, p.cols, n);
-}
-
-template <int G, int GX, int TF, int TB_ = 256>
-__global__ __launch_bounds__(256) void k_plan_long(PlanLongDet a, PlanLongArgs p) {
-  __shared__ float mrow[kPlanLongFloats];
-  __shared__ int book[kPlanLongInts];
-  if (p.layout == 2) return plan_dif8_run<G, GX, TF, TB_>(a, p, (int)blockIdx.x, (int)threadIdx.x, mrow, book);
-  if (p.layout == 3) return plan_x256_run<G, GX, TF, TB_>(a, p, (int)blockIdx.x, (int)threadIdx.x, mrow, book);
-  plan_long_run<G, GX, TF, TB_>(a, p, (int)blockIdx.x, (int)threadIdx.x, mrow, book);
-}
-
-// 2^20 points in two passes: the plan of call k as the FIRST workgroups of the column launch of call k + 1 (fft1024_kernels.h,
-// 16-column tiles by 1024 threads). As a launch of its own between the row launch of call k and the column launch of call k + 1
-// the plan cost a 16-frame call 11.6 us of a chip that waits for 3 MB of run maxima, plus a launch boundary; here its blocks —
-// four to a workgroup of 1024 threads, so that the blocks whose columns share the 128-byte lines of the ring share a workgroup — hold
-// `plan_wgs` of the launch's first slots for a few microseconds while the column tiles stream in beside them. What the plan reads
-// (the run maxima of frames up to call k's last) was complete before this launch began; the rows of the ring the column tiles clear
-// in the same launch are those of call k + 1's frames (the ring holds two batches and the averager's reach: ss_create), which the
-// plan touches only where a ragged frame tile reaches past its batch and then ignores. Its consumer — the detect stage of call k —
-// rides on the launch AFTER this one (the row half of call k + 1). `plan_wgs` is a multiple of 8: the column tiles keep their XCDs.
-constexpr int kPlanFusedFloats = 4096;  // values of M per plan block when four blocks share the column tile's LDS (plan_long_cols: cap)
-template <int FMT, bool WCALC>
-__global__ __launch_bounds__(1024, 8) void k_fft_cols1024_plan(ColsArgs g, PlanLongDet a, PlanLongArgs p, int plan_wgs) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  static_assert(4 * (kPlanFusedFloats + kPlanLongInts) * 4 <= fft1024_cols_lds_bytes(4), "four plan blocks in a column tile's LDS");
-  const int tid = (int)threadIdx.x, b = (int)blockIdx.x;
-  if (b < plan_wgs) {  // (workgroup-uniform)
-    const int sub = tid >> 8;
-    float* mrow = reinterpret_cast<float*>(smem_raw) + sub * (kPlanFusedFloats + kPlanLongInts);
-    // plan block number: XCD b mod 8 as k_plan_long's block numbering has it (plan_long_block), the workgroup's four blocks in
-    // consecutive slots of that XCD
-    plan_long_run<21, 21, 16, 256>(a, p, ((((b >> 3) << 2) + sub) << 3) | (b & 7), tid & 255, mrow, reinterpret_cast<int*>(mrow + kPlanFusedFloats));
-    return;
-  }
-  fft_cols1024_tile<FMT, 4, WCALC>(g, b - plan_wgs, smem_raw, tid);
-}
-__host__ __device__ inline int plan_fused_wgs(int plan_blocks) { return (((plan_blocks + 3) / 4 + 7) / 8) * 8; }
-
-// min of the noise ceiling over bins [256 c - 32, 256 c + 288) is k_thr_tilemin above, one wave per tile column.
-
 // The general path's per-row work, written for the instruction count: a tile that takes this path is evaluated by a workgroup whose
-// end the launch waits for, its waves share their SIMDs with six or seven others, and an instruction of theirs is issued every ~5 ns —
-// the two passes cost such a tile 8.4 us each against 1.8 us for a steady tile's (profiles/r05/s32_*: 20 scalar instructions per row for
-// its address and ~30, branches included, for its value). Both are block-uniform decisions on the row's frame number:
-//   general_row_address   row fr < 0 at `before_end` + fr rows (clamped to the rows there are), fr >= 0 at psd + min(fr, nframes - 1) rows
-//   general_row_value     fr < 0: x - (ceiling or 0.0f);  learning frame: kNoData;  frame of the batch: x - ceiling;  past its end: 0.0f
-//                         — as masks on the operands (x - 0.0f is x bit for bit), no branch
-#ifndef SS_GENERAL_ROW_OLD  // (A/B builds, scripts/build_ab.py: 1 = the expressions as they were until session 33 of round 5)
-#define SS_GENERAL_ROW_OLD 0
-#endif
+// end the launch waits for, its waves share their SIMDs with six or seven others, and an instruction of theirs is issued every ~5 ns.
+// Both parts are block-uniform decisions on the row's frame number fr:
+//   the address   fr < 0 at `before_end` + fr rows (clamped to the rows there are), fr >= 0 at psd + min(fr, nframes - 1) rows
+//   the value     fr < 0: x - (ceiling or 0.0f);  learning frame: kNoData;  frame of the batch: x - ceiling;  past its end: 0.0f
+//                 — as masks on the operands (x - 0.0f is x bit for bit), no branch
+// and both are worked out for the 36 rows at once: lane l of a wave works out row l's address and masks with a dozen VECTOR
+// instructions, the wave then picks them up row by row with v_readlane (uniform again: the loads keep their scalar base) — three
+// instructions per row for the address and load, six for the value.
+// (Tried, round 5: row by row on the scalar unit — 21 + 12 instructions per row, each behind the one before; with the expressions as
+// they were until session 33, 20 + ~30 with branches, and the two passes cost such a tile 8.4 us each against 1.8 us for a steady
+// tile's: profiles/r05/s32_*.)
 __device__ __forceinline__ const char* general_row_address(const char* psd, const char* before_end, int before_rows, int nframes, ptrdiff_t row_bytes, int fr) {
-#if SS_GENERAL_ROW_OLD
-  const char* before_base = before_end - (ptrdiff_t)before_rows * row_bytes;
-  return fr < 0 ? before_base + (size_t)max(before_rows + fr, 0) * (size_t)row_bytes : psd + (size_t)min(fr, nframes - 1) * (size_t)row_bytes;
-#else
   const int idx = min(max(fr, -before_rows), nframes - 1);
   return (fr < 0 ? before_end : psd) + (ptrdiff_t)idx * row_bytes;  // (tried: a 32 x 32 -> 64-bit product by hand — the compiler expands __mulhi on scalars into the same six instructions)
-#endif
 }
-__device__ __forceinline__ float general_row_value(float x, float t, int fr, int nframes, int n_learn, int ring_db_from, bool before_are_psd) {
-#if SS_GENERAL_ROW_OLD
-  const float t_before = before_are_psd ? t : 0.0f;
-  const float w = fr < n_learn ? kNoData : x - t;
-  return fr < 0 ? x - (fr >= ring_db_from ? t : t_before) : (fr < nframes ? w : 0.0f);
-#endif
-  const bool kept = fr < 0 || (fr < nframes && fr >= n_learn);                       // the value is x - (t or 0.0f)
-  const bool with_t = fr >= 0 || fr >= ring_db_from || before_are_psd;                 // ... t: rows of the batch, dB rows of the ring, plane rows
-  const uint32_t other = fr < nframes ? __float_as_uint(kNoData) : 0u;                 // not kept: a learning frame (noise_learner.cpp:49), or past the batch's end
-  const uint32_t tm = with_t ? 0xffffffffu : 0u, km = kept ? 0xffffffffu : 0u;
-  const float v = x - __uint_as_float(__float_as_uint(t) & tm);                       // noise_learner.cpp:55
-  return __uint_as_float((__float_as_uint(v) & km) | (other & ~km));
-}
-
-// ... and both for the 36 rows at once: lane l of a wave works out row l's address and masks with a dozen VECTOR instructions, the
-// wave then picks them up row by row with v_readlane (uniform again: the loads keep their scalar base) — three instructions per row
-// for the address and load, six for the value, where the scalar unit spent 21 + 12 in turn (each behind the one before).
-#ifndef SS_GENERAL_ROW_LANES  // (A/B builds: 0 = row by row on the scalar unit, as sessions 33's first form)
-#define SS_GENERAL_ROW_LANES 1
-#endif
 struct GeneralRowsOfLane {
   unsigned lo, hi, tm, km, other;
 };
@@ -1191,14 +635,12 @@ __device__ __forceinline__ void detect_tile(const DetectArgs& a, int block, int 
       // wherever the result is read lane by lane — the second column is the whole first wave's business up to its stores, see the general
       // path below)
       const bool wave0 = tid < 64;
-      [[maybe_unused]] GeneralRowsOfLane rows_l{};
-#if SS_GENERAL_ROW_LANES
+      GeneralRowsOfLane rows_l{};
       if (!steady) {
         rows_l = general_rows_of_lane(reinterpret_cast<const char*>(a.psd), reinterpret_cast<const char*>(before_base) + (ptrdiff_t)before_rows * (ptrdiff_t)n * 4, before_rows, nframes,
                                       (ptrdiff_t)n * 4, f0 - (G - 1), tid & 63, a.n_learn, a.ring_db_from, a.halo_psd != nullptr);
         asm volatile("" : "+v"(rows_l.lo), "+v"(rows_l.hi), "+v"(rows_l.tm), "+v"(rows_l.km), "+v"(rows_l.other));
       }
-#endif
       if (in_line) {
         const char* p = reinterpret_cast<const char*>(a.psd) + (ptrdiff_t)(f0 - (G - 1)) * (ptrdiff_t)n * 4;
 #pragma unroll
@@ -1208,17 +650,7 @@ __device__ __forceinline__ void detect_tile(const DetectArgs& a, int block, int 
           for (int r = 0; r < ROWS; ++r) y[r] = load_row_value(p + (size_t)r * n * 4 + off1);
         }
       } else {
-#if SS_GENERAL_ROW_LANES
         general_rows_load2<0, ROWS>(rows_l, off0, off1, x, y);  // (the second column by every thread: a branch per row would cost more than the loads)
-#else
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-          const char* src = general_row_address(reinterpret_cast<const char*>(a.psd), reinterpret_cast<const char*>(before_base) + (ptrdiff_t)before_rows * (ptrdiff_t)n * 4,
-                                                before_rows, nframes, (ptrdiff_t)n * 4, f0 - (G - 1) + r);
-          x[r] = *reinterpret_cast<const float*>(src + off0);
-          y[r] = *reinterpret_cast<const float*>(src + off1);
-        }
-#endif
       }
       // rel = value - ceiling; learning frames, rows of the ring, frames past a ragged end as the general path below has them
       const auto settle = [&](float (&v)[ROWS], float t) {
@@ -1226,12 +658,7 @@ __device__ __forceinline__ void detect_tile(const DetectArgs& a, int block, int 
 #pragma unroll
           for (int r = 0; r < ROWS; ++r) v[r] -= t;
         } else {
-#if SS_GENERAL_ROW_LANES
           general_rows_settle<0, ROWS>(rows_l, t, v);
-#else
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) v[r] = general_row_value(v[r], t, f0 - (G - 1) + r, nframes, a.n_learn, a.ring_db_from, a.halo_psd != nullptr);
-#endif
         }
       };
       settle(x, t0);
@@ -1297,52 +724,18 @@ __device__ __forceinline__ void detect_tile(const DetectArgs& a, int block, int 
         }
       }
     }
-  } else if (PERM8 == 0 && SS_STEADY_HALO && a.halo_psd && a.n_learn == 0 && f0 - (G - 1) >= -a.halo_rows && f0 + TF <= nframes && a.pushed_before >= G && !a.rel_out &&
-             !writes_hist) {
-    // Round 6 (SS_STEADY_HALO=1 builds; measured, not kept) — a steady tile whose first rows lie before the batch, in the halo frames' dB plane (8192 points, deep pipelining: the first
-    // two frame tiles of every batch): every one of its 36 rows is a dB row of a full averager, as a steady tile's, only in two pieces of
-    // memory — a scalar select of the row's base, the straight-line path's arithmetic on the same values. (On the general path — an
-    // address and three masks per row for cases that cannot occur here — such a tile took 12 us against a steady tile's 6, and the
-    // workgroups that evaluate them were the last of their launch and the whole of a drain's detect launch: profiles/r05/s37_summary.txt,
-    // profiles/r06/s1_timeline_k20.txt.) The tile's frames before the batch (f0 + j < 0) get time means nobody reads: phase 2 skips them.
-#pragma unroll
-    for (int pass_c = 0; pass_c < 2; ++pass_c) {
-#ifdef SS_DIAG
-      if (pass_c == 1 && a.stamp_mid && tid == 0) a.stamp_mid[4 * (size_t)block + 1] = wall_clock64();
-#endif
-      const int c = tile_column_of<PERM8, A, TB>(pass_c, tid);
-      if (pass_c == 0 || tid < 2 * A) {
-        const int col = b0 - A + c;
-        const int colc = min(max(col, 0), n - 1);
-        const bool in_band = col == colc;
-        const float t = a.thr[colc];
-        const char* pb = reinterpret_cast<const char*>(a.psd);
-        const char* hb = reinterpret_cast<const char*>(a.halo_psd + (size_t)a.halo_rows * n);  // (its end: frame -1 is the row before it)
-        const uint32_t coff = (uint32_t)colc * 4u;
-        float x[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-          const int fr = f0 - (G - 1) + r;  // (block-uniform)
-          x[r] = load_row_value((fr < 0 ? hb : pb) + (ptrdiff_t)fr * (ptrdiff_t)n * 4 + coff) - t;
-        }
-        if (!interior) {
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) x[r] = in_band ? x[r] : 0.0f;
-        }
-        time_means_to_tile<G, TF, P, false>(x, &tile[c], 0);
-      }
-    }
   } else {
     // general path: ring rows from before the batch, learning frames, averager warm-up, ragged batch end.
     // Same arithmetic as above on the same values, so a frame's result does not depend on the path.
     // (two straight passes over the 276 columns, not a loop: a loop makes the compiler hoist all 36 row
     // pointers out of it and spill scalar registers)
+    // (Tried, round 6: the tiles whose first rows are halo frames — the first two frame tiles of a deep-pipelined 8192-point batch — on a
+    // straight-line path of their own: 23.2-23.6 against 23.0-23.1 us per step, no gain, profiles/r06/s16_summary.txt.)
 #pragma unroll
     for (int pass_c = 0; pass_c < 2; ++pass_c) {
 #ifdef SS_DIAG
       if (pass_c == 1 && a.stamp_mid && tid == 0) a.stamp_mid[4 * (size_t)block + 1] = wall_clock64();
 #endif
-#if SS_GENERAL_ROW_LANES
       // The 36 rows' addresses and masks on 36 lanes (general_rows_of_lane), read back lane by lane. A lane's registers are only safe from
       // the register allocator while the lane runs the same code as its readers (a lane that has branched off "needs them no more" and may
       // find them reused there): so a wave takes part in a pass as a whole or not at all — the second pass is the tile's first wave, its
@@ -1382,42 +775,6 @@ __device__ __forceinline__ void detect_tile(const DetectArgs& a, int block, int 
           }
         }
       }
-#else
-      const int c = tile_column_of<PERM8, A, TB>(pass_c, tid);
-      const int col = b0 - A + c;
-      if (pass_c == 1 && tid >= 2 * A) {
-        // nothing: 276 columns over 256 threads
-      } else if (col < 0 || col >= n) {
-#pragma unroll
-        for (int j = 0; j < TF; ++j) tile[j * P + c] = 0.0f;  // outside the band: contributes exactly nothing to the clipped window sums
-      } else {
-        const bool main_col = c >= A && c < A + TB;
-        const float t = a.thr[col];
-        // all loads first, unconditional, on always-legal addresses: independent and in flight together; a
-        // branch around each load would serialise them on s_waitcnt. The row pointer is block-uniform:
-        // frames before the batch come from the ring (row H + frame), frames past its end are clamped.
-        const uint32_t coff = (uint32_t)(PERM8 ? dif_bin_offset(col, PERM8) : col) * 4u;
-        float x[ROWS];
-        const char* before_end = reinterpret_cast<const char*>(before_base) + (ptrdiff_t)before_rows * (ptrdiff_t)n * 4;
-        // ring rows hold rel values — or dB values, from ring_db_from on —, plane rows (the halo frames) are PSD
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r)
-          x[r] = *reinterpret_cast<const float*>(general_row_address(reinterpret_cast<const char*>(a.psd), before_end, before_rows, nframes, (ptrdiff_t)n * 4, f0 - (G - 1) + r) + coff);
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) x[r] = general_row_value(x[r], t, f0 - (G - 1) + r, nframes, a.n_learn, a.ring_db_from, a.halo_psd != nullptr);
-        if (main_col) {
-#pragma unroll
-          for (int j = 0; j < TF; ++j) {
-            const int fr = f0 + j;
-            if (fr >= 0 && fr < nframes) {
-              if (a.rel_out) store_row(a.rel_out, fr, n, coff, x[G - 1 + j]);
-              if (fr >= first_hist) store_row(a.hist_out, fr - first_hist, n, coff, x[G - 1 + j]);
-            }
-          }
-        }
-        time_means_to_tile<G, TF, P, true>(x, &tile[c], a.pushed_before + f0 + 1);
-      }
-#endif
     }
   }
   __syncthreads();
@@ -1773,3 +1130,7 @@ __global__ __launch_bounds__(64) void k_cand_emit(EmitArgs a) {
 }
 
 }  // namespace ss
+
+// The long transforms' tile plans (PlanLongArgs, plan_long_run / plan_dif8_run / plan_x256_run, k_plan_long, k_fft_cols1024_plan) live in
+// a header of their own that needs everything above; whoever includes this header gets them too, as before they moved.
+#include "plan_long.h"

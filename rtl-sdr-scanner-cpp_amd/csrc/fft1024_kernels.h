@@ -161,11 +161,9 @@ __device__ __forceinline__ void fft_cols1024_tile(const ColsArgs& g, int block, 
       if constexpr (FMT == FMT_CS8) x = make_float2((float)(signed char)(raw & 0xff) * g.scale, (float)(signed char)(raw >> 8) * g.scale);
       else x = make_float2(((float)(raw & 0xff) - 127.5f) * g.scale, ((float)(raw >> 8) - 127.5f) * g.scale);
     }
-#ifndef SS_C1024_ABL  // (A/B builds, scripts/build_ab.py — garbage results, the column tiles' time without: 1 = the window loads, 2 = the work-buffer stores, 4 = the frame loads)
-#define SS_C1024_ABL 0
-#endif
-    if (SS_C1024_ABL & 4) x = make_float2(__int_as_float(0x3f800000 + (int)tn + r), 0.5f);
-    const float wv = (SS_C1024_ABL & 1) ? 1.0f : WCALC ? fmaf(wt.x, kWin1024C[r], fmaf(wt.y, kWin1024S[r], 0.54f)) : wv16[r];
+    // (Timed in round 4 with parts of the tile taken out: everything 81 us per 16-frame call, no window loads 70, no work-buffer stores
+    // 55, arithmetic and LDS alone 21 — profiles/r04/s4_summary.txt.)
+    const float wv = WCALC ? fmaf(wt.x, kWin1024C[r], fmaf(wt.y, kWin1024S[r], 0.54f)) : wv16[r];
     a[r] = make_float2(x.x * wv, x.y * wv);  // volk_32fc_32f_multiply_32fc
   }
   float2 cc[16];
@@ -205,8 +203,7 @@ __device__ __forceinline__ void fft_cols1024_tile(const ColsArgs& g, int block, 
     for (int kap = 0; kap < 4; ++kap) {
       const float2 tw = kap == 0 ? pu : cmul(pu, kap == 1 ? g1 : kap == 2 ? g2 : g3);
       const float2 y = cmul(a[4 * u + kap], tw);
-      if ((SS_C1024_ABL & 2) && y.x != 12345.678f) continue;
-      __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<const __attribute__((ext_vector_type(2))) unsigned*>(&y), rw, voff, ((64 * u + 256 * kap) << 10) * 8, SS_AUX_WORK);
+      __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<const __attribute__((ext_vector_type(2))) unsigned*>(&y), rw, voff, ((64 * u + 256 * kap) << 10) * 8, kAuxWork);
     }
     if (u < 3) pu = cmul(pu, t64);
   }
@@ -352,7 +349,7 @@ __device__ __forceinline__ void fft_rows1024_tile(const Rows1024Args& g, int blo
   constexpr int ISH = LOGN1 + 6;  // (64 k2 further on: 64 << LOGN1 bins)
   if (out) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) store_f1_policy<SS_AUX_ROWS>(&out[bin0 ^ (i << ISH)], s[(kb + 64 * i) * 9 + rr]);
+    for (int i = 0; i < 16; ++i) store_f1_policy<kAuxRows>(&out[bin0 ^ (i << ISH)], s[(kb + 64 * i) * 9 + rr]);
   }
   if (hrow) {
     // The sixteen ceiling values FIRST, all in flight together, then the sixteen stores. (Until session 16 of round 4 the loop was
@@ -364,13 +361,13 @@ __device__ __forceinline__ void fft_rows1024_tile(const Rows1024Args& g, int blo
     // evaluated subtract the ceiling, DetectArgs::ring_db_from)
     if (!x.thr) {
 #pragma unroll
-      for (int i = 0; i < 16; ++i) store_f1_policy<SS_AUX_ROWS>(&hrow[bin0 ^ (i << ISH)], s[(kb + 64 * i) * 9 + rr]);
+      for (int i = 0; i < 16; ++i) store_f1_policy<kAuxRows>(&hrow[bin0 ^ (i << ISH)], s[(kb + 64 * i) * 9 + rr]);
     } else {
       float th[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) th[i] = x.thr[bin0 ^ (i << ISH)];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) store_f1_policy<SS_AUX_ROWS>(&hrow[bin0 ^ (i << ISH)], s[(kb + 64 * i) * 9 + rr] - th[i]);  // noise_learner.cpp:55, as detect_tile forms it
+      for (int i = 0; i < 16; ++i) store_f1_policy<kAuxRows>(&hrow[bin0 ^ (i << ISH)], s[(kb + 64 * i) * 9 + rr] - th[i]);  // noise_learner.cpp:55, as detect_tile forms it
     }
   }
 }

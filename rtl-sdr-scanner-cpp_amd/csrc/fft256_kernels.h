@@ -60,18 +60,14 @@ __device__ __forceinline__ void fft256_passes(float2 (&a)[16], float2 (&c)[16], 
   dft16(c);  // X[j + 16 k] in c[slot16(k)]
 }
 
-// Cache policy of the long transforms' big stores — the column tiles' work buffer (SS_AUX_WORK) and the row tiles' dB / ring rows
-// (SS_AUX_ROWS): 0 = the default write-back policy (ships), 16 = sc1, write-through, as the 8192-point kernel's dB rows (fft8192_v2.h
-// SS_AUX_PSD), 2 = nt. Measured in round 6 (profiles/r06/s5_summary.txt, alternating runs): write-through LOSES here — the row tiles
+// Cache policy of the long transforms' big stores — the column tiles' work buffer (kAuxWork) and the row tiles' dB / ring rows
+// (kAuxRows): 0 = the default write-back policy, 16 = sc1, write-through, as the 8192-point kernel's dB rows (fft8192_v2.h
+// kAuxPsd), 2 = nt. Measured in round 6 (profiles/r06/s5_summary.txt, alternating runs): write-through LOSES here — the row tiles
 // store 32-byte runs that four workgroups of one XCD complete to 128-byte lines in their L2, and written through every piece goes to
 // memory by itself: row launch 22.6 -> 32.6 us per 32 frames of 262144 points, 43 -> 60 us per 16 frames of 2^20; the work buffer
-// (whole lines) a wash: column launch 35.0 -> 33.6 us at 262144 points, 57.7 -> 59.4 at 2^20. Build-time switches (scripts/build_ab.py).
-#ifndef SS_AUX_WORK
-#define SS_AUX_WORK 0
-#endif
-#ifndef SS_AUX_ROWS
-#define SS_AUX_ROWS 0
-#endif
+// (whole lines) a wash: column launch 35.0 -> 33.6 us at 262144 points, 57.7 -> 59.4 at 2^20.
+constexpr int kAuxWork = 0;
+constexpr int kAuxRows = 0;
 template <int AUX>
 __device__ __forceinline__ void store_f1_policy(float* p, float v) {
   if constexpr (AUX == 16) asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
@@ -129,13 +125,8 @@ __device__ __forceinline__ void fft_cols256_tile(const ColsArgs& g, int block, u
   // first exchange come before its first use.
   float2* tw_lds = reinterpret_cast<float2*>(smem_raw + kFft256LdsBytes);
   if (t < 256) tw_lds[t] = g.tw256[t];
-#ifndef SS_COLS_STAGGER  // (A/B builds, scripts/build_ab.py: every other column tile starts SS_COLS_STAGGER x ~3.4 us late — do a launch's load, compute and store phases overlap better out of step?)
-#define SS_COLS_STAGGER 0
-#endif
-  if (SS_COLS_STAGGER && (block & 1)) {
-#pragma unroll
-    for (int k = 0; k < SS_COLS_STAGGER; ++k) __builtin_amdgcn_s_sleep(127);
-  }
+  // (Tried, round 4: every other column tile — and every other group of eight row tiles — started 3.4 to 10 us late, so that a launch's
+  // load, compute and store phases overlap out of step: 28.0 / 31.1 / 37.4 against 28.0 us, profiles/r04/s33_summary.txt: no.)
   const int logn2 = g.logn2;
   const int q = t & 31, j = t >> 5;
   const int n2size = 1 << logn2;
@@ -165,10 +156,7 @@ __device__ __forceinline__ void fft_cols256_tile(const ColsArgs& g, int block, u
   for (int r = 0; r < 16; ++r) {
     const size_t un = (size_t)(16 * r) << logn2;
     const float2 x = load_iq<FMT>(in_frame + un * kInBytes + tn * kInBytes, 0, g.scale);
-#ifndef SS_COLS_ABL  // (A/B builds, scripts/build_ab.py — garbage results, the column tiles' time without: 1 = the step-A twiddle table loads, 2 = the window loads, 3 = both)
-#define SS_COLS_ABL 0
-#endif
-    const float w = (SS_COLS_ABL & 2) ? 1.0f : *reinterpret_cast<const float*>(win_b + un * 4 + tn * 4u);
+    const float w = *reinterpret_cast<const float*>(win_b + un * 4 + tn * 4u);
     a[r] = make_float2(x.x * w, x.y * w);  // volk_32fc_32f_multiply_32fc
   }
   float2 c[16];
@@ -180,13 +168,9 @@ __device__ __forceinline__ void fft_cols256_tile(const ColsArgs& g, int block, u
   const char* t1 = reinterpret_cast<const char*>(g.twc);
   const char* t2 = reinterpret_cast<const char*>(g.twc + ((size_t)16 << logn2));
   const float2 tj = *reinterpret_cast<const float2*>(t1 + 8u * (((uint32_t)j << logn2) + (uint32_t)n2));
-#ifndef SS_COLS_TW6  // (A/B builds: 0 = one table entry per k, fifteen loads per thread, as until the end of round 3)
-#define SS_COLS_TW6 1
-#endif
-#if SS_COLS_TW6
   // W_N^(16 n2 k) = w^k, w = W_N^(16 n2), from SIX entries of the [k][n2] table — w, w^2, w^3 and w^4, w^8, w^12 — as
   // w^(4 a + b) = w^(4 a) w^b (one more rounding than the table's own entry: inside the fp32 FFT's floor, §5 of DESIGN.md). The
-  // fifteen loads per thread stood, like every table read of a streaming workgroup, behind the tile's and its neighbours' frame
+  // fifteen loads per thread of one entry per k (the form until the end of round 3) stood, like every table read of a streaming workgroup, behind the tile's and its neighbours' frame
   // loads: without them the column launch ran 5 us (65536 x 128) and 14 us (2^20 x 16) shorter (profiles/r03/s50_summary.txt).
   const auto tw_at = [&](int k) { return *reinterpret_cast<const float2*>(t2 + 8u * (((uint32_t)k << logn2) + (uint32_t)n2)); };
   const float2 wb1 = tw_at(1), wb2 = tw_at(2), wb3 = tw_at(3), wa1 = tw_at(4), wa2 = tw_at(8), wa3 = tw_at(12);
@@ -199,17 +183,8 @@ __device__ __forceinline__ void fft_cols256_tile(const ColsArgs& g, int block, u
       const float2 wa = a == 1 ? wa1 : a == 2 ? wa2 : wa3, wb = b == 1 ? wb1 : b == 2 ? wb2 : wb3;
       y = cmul(y, a == 0 ? wb : b == 0 ? wa : cmul(wa, wb));
     }
-    store_f2_policy<SS_AUX_WORK>(reinterpret_cast<float2*>(wf + 8u * ((k1 << logn2) + (uint32_t)n2)), y);
+    store_f2_policy<kAuxWork>(reinterpret_cast<float2*>(wf + 8u * ((k1 << logn2) + (uint32_t)n2)), y);
   }
-#else
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const uint32_t k1 = (uint32_t)(j + 16 * k);
-    float2 y = cmul(c[slot16(k)], tj);
-    if (k > 0 && !(SS_COLS_ABL & 1)) y = cmul(y, *reinterpret_cast<const float2*>(t2 + 8u * (((uint32_t)k << logn2) + (uint32_t)n2)));
-    *reinterpret_cast<float2*>(wf + 8u * ((k1 << logn2) + (uint32_t)n2)) = y;
-  }
-#endif
 }
 
 // Stand-alone launch (learning batches are launched this way too; otherwise the tiles run as a role of k_scan_step).
@@ -220,7 +195,7 @@ __global__ __launch_bounds__(512, 8) void k_fft_cols256(ColsArgs g) {
 }
 
 // What the rows kernel leaves for the detect stage of a long transform besides the dB rows (tile culling for N = 256 x N2,
-// detect_fused.h: k_plan_long). Every workgroup owns one 32-bin run of each of 256 tile columns:
+// plan_long.h: k_plan_long). Every workgroup owns one 32-bin run of each of 256 tile columns:
 //   smax      the largest dB value of each run -> smax[(abs0 + frame) & smax_mask][rows_smax_index(...)], a ring over the frames
 //             since the last reset; within a frame the runs lie in the order the workgroups produce them (256 consecutive floats
 //             per workgroup: as 4-byte stores scattered over the row in bin order they cost a 32-byte write each, 1 B per
@@ -276,13 +251,6 @@ __device__ __forceinline__ void fft_rows256_tile(const Rows256Args& g, int block
   if (t < 256) tw_lds[t] = tw256[t];
   if (x.smax && t < 256) pmax[t] = 0u;  // (the barriers of the register passes come before the first atomic)
   if (x.zero_word && block == 0 && t == 0) *x.zero_word = 0;
-#ifndef SS_ROWS_STAGGER  // (A/B builds: as SS_COLS_STAGGER, for the row tiles)
-#define SS_ROWS_STAGGER 0
-#endif
-  if (SS_ROWS_STAGGER && (block & 8)) {
-#pragma unroll
-    for (int k = 0; k < SS_ROWS_STAGGER; ++k) __builtin_amdgcn_s_sleep(127);
-  }
   const int rho = t >> 4, j = t & 15;
   const int r0 = (block & 7) << 5;
   const int c = (block >> 3) & ((1 << lognsub) - 1);
@@ -294,10 +262,9 @@ __device__ __forceinline__ void fft_rows256_tile(const Rows256Args& g, int block
   for (int r = 0; r < 16; ++r) a[r] = row[j + 16 * r];
   float2 cc[16];
   fft256_passes<kFft256PitchRows>(a, cc, s, tw_lds, rho, j);
-#ifndef SS_ROWS_ABL  // (A/B builds, scripts/build_ab.py: 1 = no maxima, 2 = no ring rows — garbage results, the kernel's time without them)
-#define SS_ROWS_ABL 0
-#endif
-  if (x.smax && SS_ROWS_ABL != 1) {
+  // (Timed in round 3 without the maxima and without the ring rows: 65536 x 128 rows launch 20.5 us with both, 20.5 without the maxima,
+  // 17.8 without the ring rows; 2^20 x 16: 50.9 / 51.6 / 35.2 — profiles/r03/s31_summary.txt.)
+  if (x.smax) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       const float2 v = cc[slot16(k)];
@@ -316,12 +283,12 @@ __device__ __forceinline__ void fft_rows256_tile(const Rows256Args& g, int block
     const float bound = fmaf(__log2f(__uint_as_float(pmax[t])), 3.01029995663981195f, -db_off);
     x.smax[((size_t)((x.abs0 + f) & x.smax_mask) << (logn - 5)) + ((r0 >> 5) << (logn - 8)) + (c << 8) + t] = bound;  // rows_smax_index
   }
-  float* hrow = (x.hist_out && f >= x.first_hist && SS_ROWS_ABL != 2) ? x.hist_out + ((size_t)(f - x.first_hist) << logn) : nullptr;  // (workgroup-uniform)
+  float* hrow = (x.hist_out && f >= x.first_hist) ? x.hist_out + ((size_t)(f - x.first_hist) << logn) : nullptr;  // (workgroup-uniform)
   // fft_v shift=true: X[k] lands at k ^ (N/2)
   const auto bin_of = [&](int i) { return ((r0 + rr) + (c << 8) + ((kb + 16 * i) << log_row)) ^ half; };
   if (psd) {  // (null: a call that keeps no dB plane, specscan.hip run_batch)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) store_f1_policy<SS_AUX_ROWS>(&out[bin_of(i)], s[(kb + 16 * i) * 33 + rr]);
+    for (int i = 0; i < 16; ++i) store_f1_policy<kAuxRows>(&out[bin_of(i)], s[(kb + 16 * i) * 33 + rr]);
   }
   if (hrow) {
     // the ceiling values first, all in flight together, then the stores: load, subtract, store per output is what the compiler keeps
@@ -329,13 +296,13 @@ __device__ __forceinline__ void fft_rows256_tile(const Rows256Args& g, int block
     // load and for the store before it (fft1024_kernels.h: fft_rows1024_tile)
     if (!x.thr) {  // (workgroup-uniform) the rows leave as dB values: the tiles that are evaluated subtract the ceiling (DetectArgs::ring_db_from)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) store_f1_policy<SS_AUX_ROWS>(&hrow[bin_of(i)], s[(kb + 16 * i) * 33 + rr]);
+      for (int i = 0; i < 16; ++i) store_f1_policy<kAuxRows>(&hrow[bin_of(i)], s[(kb + 16 * i) * 33 + rr]);
     } else {
       float th[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) th[i] = x.thr[bin_of(i)];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) store_f1_policy<SS_AUX_ROWS>(&hrow[bin_of(i)], s[(kb + 16 * i) * 33 + rr] - th[i]);  // noise_learner.cpp:55, as detect_tile forms it
+      for (int i = 0; i < 16; ++i) store_f1_policy<kAuxRows>(&hrow[bin_of(i)], s[(kb + 16 * i) * 33 + rr] - th[i]);  // noise_learner.cpp:55, as detect_tile forms it
     }
   }
 }

@@ -24,34 +24,23 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fft65536_dif8.h"
 #include "fft8192_kernel.h"
 
-// Cache policy of a 65536-point frame's samples in the radix-8 fold (fft65536_dif8.h): eight workgroups read every frame,
-// so the default policy (0), not the read-once nt of the 8192-point frames
-#ifndef SS_AUX_DIF_IQ
-#define SS_AUX_DIF_IQ 0
-#endif
-#include "fft65536_dif8.h"
+// The per-column maxima for the tile culling (Fft8192Args::segsum): the frame's dB values go through LDS once more and sixteen
+// threads per tile column take its maximum from there (16 LDS stores, five 16-byte LDS loads and ~25 vector instructions per
+// thread). (The first form, until session 15 of round 4, took them in registers: five v_max_f32_dpp per value and a select to gather
+// them, 96 of the frame path's 1082 vector instructions — in a kernel that waits to ISSUE more than it waits for memory,
+// profiles/README.md, SQ counters.)
+
+namespace ss {
 
 // Cache policy of the frame loads (read once, never again: nt = 2 measured 2.5 % faster per step than the default policy,
 // sc0 / sc1 variants the same as nt) and of the dB row stores (sc1 = 16, write-through: 2.5 % faster per step in a long run, 5 % in a
 // 20-step run — the end of a launch no longer has an L2 full of dirty rows to write back before the queue's next launch may start).
-// Build-time so that variants can be A/B'd (scripts/build_ab.py), DESIGN.md 4.1.
-#ifndef SS_AUX_IQ
-#define SS_AUX_IQ 2
-#endif
-#ifndef SS_AUX_PSD
-#define SS_AUX_PSD 16
-#endif
-// The per-column maxima for the tile culling (Fft8192Args::segsum): 1 = the frame's dB values go through LDS once more and sixteen
-// threads per tile column take its maximum from there (16 LDS stores, five 16-byte LDS loads and ~25 vector instructions per
-// thread); 0 = the first form, in registers: five v_max_f32_dpp per value and a select to gather them, 96 of the frame path's
-// 1082 vector instructions — in a kernel that waits to ISSUE more than it waits for memory (profiles/README.md, SQ counters).
-#ifndef SS_SEGMAX_LDS
-#define SS_SEGMAX_LDS 1
-#endif
-
-namespace ss {
+// DESIGN.md 4.1. (The fold's frame loads: kAuxDifIq, fft65536_dif8.h.)
+constexpr int kAuxIq = 2;
+constexpr int kAuxPsd = 16;
 
 struct Fft8192V2Tables {
   const float2* tw2;   // [16][16]  W_256^(m r) at r*16 + m
@@ -99,7 +88,7 @@ struct Fft8192Args {
   // rides on the launch (scan_step.h). It is asked for before the frame's own loads and handed back in `hdr` when they have
   // landed: the answer costs the workgroup nothing.
   const int* live_hint;
-  // (FRONT != 0 — a residue of a 65536- / 131072-point frame: `psd` is the averager ring's buffer and the rows are dB values in
+  // (FRONT != kFrontFrame — a residue of a 65536- / 131072-point frame: `psd` is the averager ring's buffer and the rows are dB values in
   // the fold's order (blocks of 32 Q bins, fft65536_dif8.h); the tiles that are evaluated subtract the noise ceiling, DetectArgs::ring_db_from. Until session 18 of round 5
   // the transform subtracted it itself, from a copy of the ceiling in the rows' order: 32 loads per thread, 8-9 % of the launch.)
 #ifdef SS_DIAG
@@ -107,27 +96,8 @@ struct Fft8192Args {
 #endif
 };
 
-// max over the 32 lanes of a half-wave (lanes 0..31 / 32..63) of FOUR values at once, valid in each half's upper 16 lanes:
-// four butterfly steps inside each row of 16 (every lane of a row then holds the row's maximum), then lane 15 of rows 0 / 2
-// broadcast into rows 1 / 3. v_max_f32 returns the other operand for a (quiet) NaN, so NaN bins are ignored — they cannot
-// make a candidate. Written as v_max_f32_dpp by hand (the compiler emits v_mov_b32_dpp + canonicalising v_max triples, 3.5x
-// the instructions); four independent chains interleaved keep a DPP read three instructions behind the write it depends on
-// (the hardware wants two), the leading s_nop covers the values' producers.
-__device__ __forceinline__ void halfwave_max4_hi16(float& a, float& b, float& c, float& d) {
-#define SS_DPP4(ctrl)                                  \
-  "v_max_f32_dpp %0, %0, %0 " ctrl " bank_mask:0xf\n" \
-  "v_max_f32_dpp %1, %1, %1 " ctrl " bank_mask:0xf\n" \
-  "v_max_f32_dpp %2, %2, %2 " ctrl " bank_mask:0xf\n" \
-  "v_max_f32_dpp %3, %3, %3 " ctrl " bank_mask:0xf\n"
-  asm volatile("s_nop 1\n"
-               SS_DPP4("quad_perm:[1,0,3,2] row_mask:0xf")
-               SS_DPP4("quad_perm:[2,3,0,1] row_mask:0xf")
-               SS_DPP4("row_half_mirror row_mask:0xf")
-               SS_DPP4("row_mirror row_mask:0xf")
-               SS_DPP4("row_bcast:15 row_mask:0xa")
-               : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-#undef SS_DPP4
-}
+// The load stage of fft8192_v2_frame (FRONT, described there)
+constexpr int kFrontFrame = 0, kFrontFold8 = 5, kFrontFold16 = 6;
 
 // Everything behind the load stage: the three register passes on a[16] (the thread's y[t + 512 r], r < 16), dB, the row's stores and
 // what the frame leaves for the detect stage. `a` is consumed.
@@ -216,9 +186,7 @@ __device__ __forceinline__ void fft8192_v2_core(float2 (&a)[16], const Fft8192Ar
   __syncthreads();
 #pragma unroll
   for (int q = 0; q < 16; ++q) a[q].y = s[rbase + 512 * q];
-#if SS_SEGMAX_LDS
   __syncthreads();  // the exchange plane takes the frame's dB values at the end (the column maxima): every read of z is done
-#endif
 
   // The list header word this workgroup will want when its frame is done (live_hint): asked for NOW — two thirds of a
   // frame after the workgroup began, so the plan role has had time to publish its counts, and with pass 3 left to hide the
@@ -290,13 +258,13 @@ __device__ __forceinline__ void fft8192_v2_core(float2 (&a)[16], const Fft8192Ar
   u[13] = mulw32_if<13>(a[slot16(13)], odd);
   u[14] = mulw32_if<14>(a[slot16(14)], odd);
   u[15] = mulw32_if<15>(a[slot16(15)], odd);
-  // FRONT != 0: `frame` = Q * (row of the ring) + residue, and the row is in the fold's layout (fft65536_dif8.h: blocks of 32 Q bins,
+  // FRONT != kFrontFrame: `frame` = Q * (row of the ring) + residue, and the row is in the fold's layout (fft65536_dif8.h: blocks of 32 Q bins,
   // 32 outputs of every residue side by side) — this thread's output k' = j + 2048 h + 256 kk (+ 4096) at block k' / 32, place j % 32
-  constexpr int LOGQ = (FRONT == 4 || FRONT == 6) ? 4 : 3;
-  float* out = FRONT != 0 ? psd + (((frame >> LOGQ) << LOGQ) * 8192 + (frame & ((1 << LOGQ) - 1)) * 32) : psd + frame * 8192;
-  const __amdgpu_buffer_rsrc_t rout = buffer_of(out, FRONT != 0 ? ((8192 << LOGQ) - 32 * (int)(frame & ((1 << LOGQ) - 1))) * 4 : 8192 * 4);
+  constexpr int LOGQ = FRONT == kFrontFold16 ? 4 : 3;
+  float* out = FRONT != kFrontFrame ? psd + (((frame >> LOGQ) << LOGQ) * 8192 + (frame & ((1 << LOGQ) - 1)) * 32) : psd + frame * 8192;
+  const __amdgpu_buffer_rsrc_t rout = buffer_of(out, FRONT != kFrontFrame ? ((8192 << LOGQ) - 32 * (int)(frame & ((1 << LOGQ) - 1))) * 4 : 8192 * 4);
   const int voff = (j + 2048 * h) * 4;
-  constexpr int kOutStep = FRONT != 0 ? (256 << LOGQ) * 4 : 1024;  // bytes between outputs 256 apart: eight blocks / 256 floats
+  constexpr int kOutStep = FRONT != kFrontFrame ? (256 << LOGQ) * 4 : 1024;  // bytes between outputs 256 apart: eight blocks / 256 floats
   // Per-segment maxima for the detect stage's tile culling: the 32 lanes of a half-wave hold, for every (k, s), the 32
   // consecutive bins of segment w + 8 k + 64 h + 128 s; lane 16 + i of each half keeps the maximum of value i = 2 k + s.
   // The 256 segment maxima of the frame meet in LDS (the 512 floats behind the exchange plane, idle since exchange 1) and the
@@ -311,14 +279,11 @@ __device__ __forceinline__ void fft8192_v2_core(float2 (&a)[16], const Fft8192Ar
   // come below); the others read it behind the barrier at the bottom
   if (g.live_hint && hint_wait && t < 64) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const bool want_max = segsum != nullptr;  // (workgroup-uniform)
-  float mine;
-#if SS_SEGMAX_LDS
   float* dbrow = reinterpret_cast<float*>(smem_raw + voff);  // the frame's dB values at their bin numbers (the exchange plane is idle since pass 3 began)
-#endif
   // the stores' per-thread offset: voff itself, or for the fold's rows block (j + 2048 h) / 32, place j % 32 — (j + 2048 h) * 4 has
   // j % 32 in bits 2-6, j / 32 in bits 7-9 and h in bit 13
   int gvoff = voff;
-  if constexpr (FRONT != 0) gvoff = (voff & 0x7c) | ((voff & 0x2380) << LOGQ);
+  if constexpr (FRONT != kFrontFrame) gvoff = (voff & 0x7c) | ((voff & 0x2380) << LOGQ);
 #pragma unroll
   for (int k2 = 0; k2 < 4; ++k2) {
     float pv[4];  // pv[2 i + s]: the dB value of bin j + 2048 h + 256 (2 k2 + i) + 4096 s
@@ -336,28 +301,15 @@ __device__ __forceinline__ void fft8192_v2_core(float2 (&a)[16], const Fft8192Ar
       // X[kk] to bin0 + 4096 and X[kk + 16] to bin0
       pv[2 * i + 1] = psd_db(cadd(e, o), db_off);
       pv[2 * i] = psd_db(csub(e, o), db_off);
-      buffer_store_f1<SS_AUX_PSD>(rout, gvoff, kOutStep * k + 16 * kOutStep, pv[2 * i + 1]);
-      buffer_store_f1<SS_AUX_PSD>(rout, gvoff, kOutStep * k, pv[2 * i]);
-#if SS_SEGMAX_LDS
+      buffer_store_f1<kAuxPsd>(rout, gvoff, kOutStep * k + 16 * kOutStep, pv[2 * i + 1]);
+      buffer_store_f1<kAuxPsd>(rout, gvoff, kOutStep * k, pv[2 * i]);
       // (whether or not the frame leaves a summary: a branch here costs the dB stores their interleaving and the kernel registers)
       dbrow[256 * k + 4096] = pv[2 * i + 1];
       dbrow[256 * k] = pv[2 * i];
-#endif
-    }
-    if (want_max && !SS_SEGMAX_LDS) {
-      halfwave_max4_hi16(pv[0], pv[1], pv[2], pv[3]);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {  // value index 2 k + s = 4 k2 + q goes to lanes 16 + index and 48 + index (a constant lane mask: no compare)
-        const unsigned long long keep = (1ull << (16 + 4 * k2 + q)) | (1ull << (48 + 4 * k2 + q));
-        if (k2 == 0 && q == 0) mine = pv[0];  // (every lane: no initial value that would have to live through the frame loop)
-        else asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(mine) : "v"(pv[q]), "s"(keep));
-      }
     }
   }
-  if constexpr (FRONT != 0) {
+  if constexpr (FRONT != kFrontFrame) {
     // ---- a residue of a 65536-point frame: the maxima of its 256 runs of 32 bins, two threads per run (fft65536_dif8.h) ----
-    static_assert(SS_SEGMAX_LDS, "the residue rows' maxima come out of the LDS image of the row");
-    (void)mine;
     (void)want_max;
     __syncthreads();  // the row's dB values are all in the plane
     if (dif->zero_word && frame_in == 0 && residue == 0 && t == 0) *dif->zero_word = 0;
@@ -383,8 +335,6 @@ __device__ __forceinline__ void fft8192_v2_core(float2 (&a)[16], const Fft8192Ar
     }
     return;
   }
-#if SS_SEGMAX_LDS
-  (void)mine;
   if (want_max) {
     // Tile column c = t / 16 by sixteen threads: bins [256 c - 32, 256 c + 288) — the column and one 32-bin segment either side,
     // clipped at the band's edges — in sixteen runs of 20 (a run that would start outside the band starts at its edge instead: it
@@ -419,35 +369,10 @@ __device__ __forceinline__ void fft8192_v2_core(float2 (&a)[16], const Fft8192Ar
       const __amdgpu_buffer_rsrc_t rseg = buffer_of(segsum, 32 * g.seg_pitch * 4);
       buffer_store_f1(rseg, c * g.seg_pitch * 4, (int)frame * 4, m);
     }
-  } else if (g.live_hint) {
-    __syncthreads();
-    *hdr = __builtin_amdgcn_readfirstlane(__float_as_int(*hint_slot));
-  }
-#else
-  if (want_max) {
-    // wave, half and lane come back out of the PSD stores' own offset (j + 2048 h) * 4, j = 32 w + lane mod 32 — the one
-    // per-thread value that is alive here anyway; anything else kept alive through pass 3 for this gets spilled (64 VGPRs)
-    int vv = voff;
-    asm volatile("" : "+v"(vv));
-    float* segs = s + 8192;
-    const int i = (vv >> 2) & 15;
-    if (vv & 64) segs[((vv >> 7) & 7) + 8 * (i >> 1) + 64 * (vv >> 13) + 128 * (i & 1)] = mine;
-    __syncthreads();
-    if (g.live_hint) *hdr = __builtin_amdgcn_readfirstlane(__float_as_int(*hint_slot));
-    if (vv < 128) {  // wave 0, lower half: thread c = tile column
-      const int c = vv >> 2;
-      float m = segs[max(8 * c - 1, 0)];
-#pragma unroll
-      for (int q = 0; q < 9; ++q) m = fmaxf(m, segs[min(8 * c + q, 255)]);
-      // block-uniform base and frame offset in scalar registers, one per-lane offset (no 64-bit address arithmetic in the vector pipe)
-      const __amdgpu_buffer_rsrc_t rseg = buffer_of(segsum, 32 * g.seg_pitch * 4);
-      buffer_store_f1(rseg, c * g.seg_pitch * 4, (int)frame * 4, m);
-    }
   } else if (g.live_hint) {  // (frames without a summary row — the re-transformed halo frames — still serve a list)
     __syncthreads();
     *hdr = __builtin_amdgcn_readfirstlane(__float_as_int(*hint_slot));
   }
-#endif
 }
 
 
@@ -456,13 +381,15 @@ __device__ __forceinline__ void fft8192_v2_core(float2 (&a)[16], const Fft8192Ar
 // SWZ: exchange 1 as four 16-byte LDS stores per plane into an unpadded, quad-rotated image instead of sixteen 4-byte
 //      stores into the 17-word pitch.
 // One frame by one workgroup of 512 threads; `smem_raw` = kFft8192V2LdsBytes of LDS, `t` = threadIdx.x.
-// FRONT: 0 = an 8192-point frame of its own; 1, 2 = residue `residue` of the 65536-point frame `frame_in` of `dif` (fft65536_dif8.h,
-//        LOADV = FRONT - 1: the load stage is the radix-8 fold, g.iq / g.win / g.item_stride are not read), `frame` = the row
-//        the residue's bins go to, as 8 x (the ring's row) + residue (the bins land in that row's blocks, fft65536_dif8.h); 3 = residues `residue` (< 4)
-//        AND residue + 4 by the same workgroup, one fold for both, rows `frame` and `frame` + 4 (twice the registers: four waves per SIMD);
-//        4 = the same for a 131072-point frame: radix 16, residues `residue` (< 8) and residue + 8, rows `frame` and `frame` + 8;
-//        5 = 3 with the fold as a radix-8 butterfly per point (round 6, fft65536_dif8.h: dif8_front2_bfly); 6 = 4 likewise (dif16_front2_bfly).
-template <int FMT, int TW, bool SWZ = false, bool NOWIN = false, int FRONT = 0>
+// FRONT: what the load stage is (the numbers are those of the seven forms rounds 5 and 6 went through; 1 - 4, the accumulating folds, are retired)
+//   kFrontFrame  (0)  an 8192-point frame of its own: g.iq, windowed by g.win;
+//   kFrontFold8  (5)  residues `residue` (< 4) AND residue + 4 of the 65536-point frame `frame_in` of `dif`, one fold for both as a radix-8
+//                     butterfly per point (fft65536_dif8.h: dif8_front2_bfly; g.iq / g.win / g.item_stride are not read). `frame` = the row
+//                     the first residue's bins go to, as 8 x (the ring's row) + residue (the bins land in that row's blocks), the second's
+//                     `frame` + 4. Twice the registers: four waves per SIMD;
+//   kFrontFold16 (6)  the same for a 131072-point frame: radix 16 (dif16_front2_bfly), residues `residue` (< 8) and residue + 8, rows
+//                     `frame` and `frame` + 8.
+template <int FMT, int TW, bool SWZ = false, bool NOWIN = false, int FRONT = kFrontFrame>
 __device__ __forceinline__ void fft8192_v2_frame(const Fft8192Args& g, size_t frame, unsigned char* __restrict__ smem_raw, int t, int* hdr,
                                                  const Dif8Front* dif = nullptr, size_t frame_in = 0, int residue = 0) {
   float2* tw2_l = reinterpret_cast<float2*>(smem_raw + kFft8192V2PlaneBytes);
@@ -472,10 +399,11 @@ __device__ __forceinline__ void fft8192_v2_frame(const Fft8192Args& g, size_t fr
   const float* win = g.win;
   const float scale = g.scale;
   const size_t in_base = frame * (size_t)g.item_stride;
+  static_assert(FRONT == kFrontFrame || FRONT == kFrontFold8 || FRONT == kFrontFold16, "the load stages that exist");
 
   // ---- tables first: these loads are ahead of the frame's own in the vector-memory queue ----
   float2 tf0 = make_float2(0.f, 0.f), tf1 = make_float2(0.f, 0.f);
-  if constexpr (FRONT != 0) {
+  if constexpr (FRONT != kFrontFrame) {
     static_assert(TW == 2, "the fold keeps the transform's tables in LDS");
   } else if constexpr (TW == 1) {
     if (t < 256) tf0 = tabs.tw2[t];
@@ -486,19 +414,16 @@ __device__ __forceinline__ void fft8192_v2_frame(const Fft8192Args& g, size_t fr
 
   // ---------------- pass 1: radix 16, Ns = 1, butterfly j = t ----------------
   float2 a[16];
-  [[maybe_unused]] float2 a2[16];  // FRONT = 3: the second residue's points
-  if constexpr (FRONT != 0) {
+  [[maybe_unused]] float2 a2[16];  // the folds: the second residue's points
+  if constexpr (FRONT != kFrontFrame) {
     // (the tables go to LDS at once — their place behind the exchange plane is free — instead of through registers that would
     // have to live through the fold)
     const auto tables_to_lds = [&]() {
       tw2_l[t] = t < 256 ? tabs.tw2[t] : tabs.lane[t - 256];
       if (t < 128) lane_l[256 + t] = tabs.lane[256 + t];
     };
-    if constexpr (FRONT == 3) dif8_front2<FMT, 8>(*dif, frame_in, residue, smem_raw, t, a, a2, tables_to_lds);
-    else if constexpr (FRONT == 5) dif8_front2_bfly<FMT>(*dif, frame_in, residue, smem_raw, t, a, a2, tables_to_lds);
-    else if constexpr (FRONT == 6) dif16_front2_bfly<FMT>(*dif, frame_in, residue, smem_raw, t, a, a2, tables_to_lds);
-    else if constexpr (FRONT == 4) dif8_front2<FMT, 16>(*dif, frame_in, residue, smem_raw, t, a, a2, tables_to_lds);
-    else dif8_front<FMT, FRONT - 1>(*dif, frame_in, residue, smem_raw, t, a, tables_to_lds);
+    if constexpr (FRONT == kFrontFold8) dif8_front2_bfly<FMT>(*dif, frame_in, residue, smem_raw, t, a, a2, tables_to_lds);
+    else dif16_front2_bfly<FMT>(*dif, frame_in, residue, smem_raw, t, a, a2, tables_to_lds);
     (void)iq;
     (void)win;
     (void)scale;
@@ -511,12 +436,12 @@ __device__ __forceinline__ void fft8192_v2_frame(const Fft8192Args& g, size_t fr
     for (int r = 0; r < 16; ++r) {
       float2 x;
       if constexpr (FMT == FMT_CF32) {
-        x = buffer_load_f2<SS_AUX_IQ>(rin, t * 8, 4096 * r);
+        x = buffer_load_f2<kAuxIq>(rin, t * 8, 4096 * r);
       } else if constexpr (FMT == FMT_CS16) {
-        x = cs16_to_f2((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rin, t * 4, 2048 * r, SS_AUX_IQ), scale);
+        x = cs16_to_f2((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rin, t * 4, 2048 * r, kAuxIq), scale);
       } else {
         static_assert(fmt_int8(FMT), "input format");
-        const unsigned short raw = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rin, t * 2, 1024 * r, SS_AUX_IQ);
+        const unsigned short raw = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rin, t * 2, 1024 * r, kAuxIq);
         if constexpr (FMT == FMT_CS8) x = make_float2((float)(signed char)(raw & 0xff) * scale, (float)(signed char)(raw >> 8) * scale);
         else x = make_float2(((float)(raw & 0xff) - 127.5f) * scale, ((float)(raw >> 8) - 127.5f) * scale);
       }
@@ -528,7 +453,7 @@ __device__ __forceinline__ void fft8192_v2_frame(const Fft8192Args& g, size_t fr
       }
     }
   }
-  if constexpr (FRONT != 0) {
+  if constexpr (FRONT != kFrontFrame) {
     // (written by the fold's prologue)
   } else if constexpr (TW == 1) {
     if (t < 256) tw2_l[t] = tf0;
@@ -536,9 +461,9 @@ __device__ __forceinline__ void fft8192_v2_frame(const Fft8192Args& g, size_t fr
     tw2_l[t] = tf0;  // tw2_l and lane_l are contiguous: entries 0..511
     if (t < 128) lane_l[256 + t] = tf1;
   }
-  if constexpr (FRONT == 3 || FRONT == 4 || FRONT == 5 || FRONT == 6) {
-    // two residues by one workgroup (fft65536_dif8.h, dif8_front2): r's transform, then (r + Q/2)'s from the registers that kept it
-    constexpr int HQ = (FRONT == 4 || FRONT == 6) ? 8 : 4;
+  if constexpr (FRONT != kFrontFrame) {
+    // two residues by one workgroup (fft65536_dif8.h): r's transform, then (r + Q/2)'s from the registers that kept it
+    constexpr int HQ = FRONT == kFrontFold16 ? 8 : 4;
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
       if (pass) {

@@ -52,23 +52,18 @@
 #include "fft1024_kernels.h"
 #include "fft256_kernels.h"
 #include "fft8192_v2.h"
+#include "plan_long.h"
 
-// kStepFold8 (65536 points, the radix-8 fold): workgroups per frame — 4: two residues each (one fold for both, 128 registers, four waves per
-// SIMD); 8: one residue each (64 registers, eight waves per SIMD). Build-time so that the two can be timed against each other
-// (scripts/build_ab.py). (One residue each for SHORT calls only, picked per call, was KIND 11: tried because the 4 x frames
-// two-residue workgroups of a short call leave most of the chip's 256 CUs idle for 18 us each, measured in round 6 and removed — a
-// workgroup folds the WHOLE frame for one residue as for two and lives as long: 16-frame calls 20.6 against 19.5 us, 32-frame calls
-// 26.0 against 20.3, profiles/r06/s13_summary.txt.)
-#ifndef SS_DIF8_W
-#define SS_DIF8_W 4
-#endif
-// ... and the fold of the two-residue form: 1 = a radix-8 butterfly per point (round 6, fft65536_dif8.h: dif8_front2_bfly — 912 vector
-// instructions per thread and fold), 0 = round 5's accumulating loop over q (1280). Build-time for the same reason.
-#ifndef SS_DIF8_BFLY
-#define SS_DIF8_BFLY 1
-#endif
-
+// kStepFold8 (65536 points, the radix-8 fold): four workgroups per frame, two residues each (one fold for both — a radix-8 butterfly
+// per point, fft65536_dif8.h: dif8_front2_bfly, 912 vector instructions per thread and fold —, 128 registers, four waves per SIMD).
+// (Tried: eight workgroups per frame, one residue each, 64 registers and eight waves per SIMD — round 5, profiles/r05/s3_dif8_lab_two_residues.txt;
+// the same for SHORT calls only, picked per call, was KIND 11: tried because the 4 x frames two-residue workgroups of a short call leave
+// most of the chip's 256 CUs idle for 18 us each, measured in round 6 and removed — a workgroup folds the WHOLE frame for one residue as
+// for two and lives as long: 16-frame calls 20.6 against 19.5 us, 32-frame calls 26.0 against 20.3, profiles/r06/s13_summary.txt.
+// And the fold as round 5's accumulating loop over q: 1280 instructions per thread and fold, profiles/r06/s2_summary.txt.)
 namespace ss {
+
+constexpr int kFold8WorkgroupsPerFrame = 4;  // (see above; the radix-16 fold: eight, two residues each)
 
 // The forms of k_scan_step: its template parameter KIND. The number is part of every kernel's name — profiles, bench.py and the
 // resource tests know the kernels by it — so a form keeps its number for good, and 3 and 11 stay unused: they were the 8-column tile of
@@ -106,8 +101,8 @@ constexpr int kStepFrames = 0, kStepCols = 1, kStepColsWide = 2, kStepRows1024 =
 // registers: a role nobody can take still costs the kernel its registers.)
 constexpr bool step_is_long(int kind) { return kind != kStepFrames; }  // a long transform: the detect stage's tiles come from k_plan_long's list
 constexpr bool step_is_fold(int kind) { return kind == kStepFold8 || kind == kStepFold16; }
-// the plan role: none (the plan runs elsewhere — at the front of the column launch before), the 8192-point tile plan (plan_tiles), or two
-// blocks of a long transform's plan per workgroup by one of three routines
+// the plan role: none (the plan runs elsewhere — at the front of the column launch before), the 8192-point tile plan (detect_fused.h:
+// plan_tiles), or two blocks of a long transform's plan per workgroup by one of three routines (plan_long.h)
 enum { PLAN_NONE = 0, PLAN_TILES = 1, PLAN_LONG = 2, PLAN_FOLD = 3, PLAN_X256 = 4 };
 constexpr int step_plan_routine(int kind) {
   return kind == kStepFrames                                                      ? PLAN_TILES
@@ -301,18 +296,18 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
     else if constexpr (KIND == kStepFold8) {  // a residue of a 65536-point frame: fold + 8192-point transform + dB -> the ring's rows
       if constexpr (fmt_int8(FMT)) {
         int f, r, hdr;
-        dif8_item<SS_DIF8_W>(item, a.dif.nframes, &f, &r);  // (W = 4: residues r and r + 4 by this workgroup)
+        dif8_item<kFold8WorkgroupsPerFrame>(item, a.dif.nframes, &f, &r);  // (W = 4: residues r and r + 4 by this workgroup)
 #ifdef SS_DIAG
         if (a.hint_mode != 4)  // (timing ablation, garbage results: the passengers of the launch by themselves)
 #endif
-        fft8192_v2_frame<FMT, 2, true, false, SS_DIF8_W == 4 ? (SS_DIF8_BFLY ? 5 : 3) : 2>(a.fft, (size_t)(8 * (f - a.dif.first_hist) + r), smem_raw, tid, &hdr, &a.dif, (size_t)f, r);
+        fft8192_v2_frame<FMT, 2, true, false, kFrontFold8>(a.fft, (size_t)(8 * (f - a.dif.first_hist) + r), smem_raw, tid, &hdr, &a.dif, (size_t)f, r);
       }
     }
     else if constexpr (KIND == kStepFold16) {  // 131072 points, radix 16: residues r (< 8) and r + 8 of a frame, eight workgroups per frame
       if constexpr (fmt_int8(FMT)) {
         int f, r, hdr;
         dif8_item<8>(item, a.dif.nframes, &f, &r);
-        fft8192_v2_frame<FMT, 2, true, false, SS_DIF8_BFLY ? 6 : 4>(a.fft, (size_t)(16 * (f - a.dif.first_hist) + r), smem_raw, tid, &hdr, &a.dif, (size_t)f, r);
+        fft8192_v2_frame<FMT, 2, true, false, kFrontFold16>(a.fft, (size_t)(16 * (f - a.dif.first_hist) + r), smem_raw, tid, &hdr, &a.dif, (size_t)f, r);
       }
     }
     else if constexpr (KIND == kStepRows256) fft_rows256_tile(a.rows256, item, smem_raw, tid);  // (the ROW half of call k: its column half ran as its own launch right before)
@@ -425,7 +420,7 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
 }
 
 template <int FMT, bool SPEC, int TW = 2, bool SWZ = true, bool PRIO = false, int KIND = kStepFrames>
-__global__ __launch_bounds__(kStepThreads, ((KIND == kStepFold8 && SS_DIF8_W == 4) || KIND == kStepFold16) ? 4 : 8) void k_scan_step(StepArgs a_by_value) {
+__global__ __launch_bounds__(kStepThreads, (KIND == kStepFold8 || KIND == kStepFold16) ? 4 : 8) void k_scan_step(StepArgs a_by_value) {
   // The arguments are read where they are used, straight from the kernel-argument segment (scalar loads from constant
   // memory): taken from the by-value parameter they are all loaded at the top of the kernel and kept alive through every
   // role — hundreds of scalar registers spilled into vector registers the 64-VGPR budget does not have.
@@ -443,23 +438,9 @@ __global__ __launch_bounds__(kStepThreads, ((KIND == kStepFold8 && SS_DIF8_W == 
     // has nothing to interleave and does without.)
     int b = (int)blockIdx.x;
     const int np = step_plan_wgs(a), ne = step_emit_wgs(a), nd = step_det_wgs(a);
-#ifndef SS_ORDER_FFT_FIRST  // (A/B builds, scripts/build_ab.py: 1 = plan, FFT, emit, detect, rows — the frames ahead of the candidate lists)
-#define SS_ORDER_FFT_FIRST 0
-#endif
-    if (SS_ORDER_FFT_FIRST && KIND == kStepFrames) {
-      if (b < np) {
-        role = ROLE_PLAN;
-      } else if ((b -= np) < a.n_fft) {
-        role = ROLE_FFT;
-      } else if ((b -= a.n_fft) < ne) {
-        role = ROLE_EMIT;
-      } else if ((b -= ne) < nd) {
-        role = ROLE_DET;
-      } else {
-        role = ROLE_ROWS;
-        b -= nd;
-      }
-    } else if (b < np) {
+    // (Tried, round 5: 8192 points with the frames dispatched ahead of the candidate lists — 23.6-24.1 us per step both ways,
+    // profiles/r05/s10_summary.txt: no gain.)
+    if (b < np) {
       role = ROLE_PLAN;
     } else if ((b -= np) < ne) {
       role = ROLE_EMIT;

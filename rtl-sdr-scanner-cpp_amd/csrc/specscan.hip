@@ -49,6 +49,7 @@
 #include "fft256_kernels.h"
 #include "reference_nan.h"
 #include "fft_kernels.h"
+#include "plan_long.h"
 #include "ring_place.h"
 #include "scan_form.h"
 #include "scan_step.h"
@@ -536,7 +537,7 @@ void launch_cols1024_fmt(ss_ctx* c, const void* d_iq, long long item_stride, int
     else hipLaunchKernelGGL(kernel, dim3(nframes * tiles), dim3(threads), lds, c->stream, g);
   };
   const bool wcalc = g.wtab != nullptr;
-  if (c->wait.plan_ready.have) {  // the plan of the call before at the front of this launch (detect_fused.h)
+  if (c->wait.plan_ready.have) {  // the plan of the call before at the front of this launch (plan_long.h)
     const ss_ctx::PendPlan& plan = c->wait.plan_ready.v;
     const int plan_wgs = ss::plan_fused_wgs(ss::plan_long_blocks(plan.a.layout, plan.a.cols, c->n));
     const dim3 grid((unsigned)(plan_wgs + nframes * 64)), block(1024);
@@ -1605,10 +1606,9 @@ int run_call_deep(ss_ctx* c, const void* d_iq, long long item_stride, const Call
     mine_det.a.halo_rows = role.n_halo;
     mine_det.a.halo_segsum = (c->cull && c->diag.halo_maxima && mine_det.a.segsum) ? halo_segsum_of(c, role.halo_psd) : nullptr;  // (this launch's FFT role leaves them)
   }
-#ifndef SS_RING_AT_DRAIN  // (A/B builds, scripts/build_ab.py: 0 = the ring rows by the tiles of every call, as until round 3)
-#define SS_RING_AT_DRAIN 1
-#endif
-  if (overlap && SS_RING_AT_DRAIN) {  // this call's ring rows: at the next drain (nframes >= kHistRows here: all of them come from this call's plane)
+  // this call's ring rows: at the next drain (nframes >= kHistRows here: all of them come from this call's plane; until round 3 the tiles
+  // of every call wrote them)
+  if (overlap) {
     mine_det.a.hist_by_fft = 1;
     c->ring_owed[0] = c->ring_owed[1];
     c->ring_owed[1].psd = d_psd;
@@ -1713,7 +1713,7 @@ void launch_fold(ss_ctx* c, const CallRoute& route, const void* d_iq, long long 
   drole.dif = &df;
   // (two residues per workgroup: four per frame at radix 8, eight at radix 16. One residue per workgroup for short calls was tried,
   // measured and removed: 16-frame calls 20.6 against 19.5 us, 32-frame calls 26.0 against 20.3, profiles/r06/s13_summary.txt)
-  drole.n = (c->dif_logq == 4 ? 8 : SS_DIF8_W) * nframes;
+  drole.n = (c->dif_logq == 4 ? 8 : ss::kFold8WorkgroupsPerFrame) * nframes;
   launch_step(c, &drole, c->wait.riding(route.ride_first));
 }
 

@@ -3,8 +3,11 @@
 // config 3 (two halves of a four-step transform through a CF32 work buffer: 40-41 us per 128-frame call, 25.9 B/sample over the fabric).
 // The kernel here is the real thing — load + fold + transform + dB + noise-relative rows in residue-major order + the per-column
 // maxima — not a traffic model: frame 0 and one more are checked against an fp64 FFT on the host.
-//   variants: how the samples reach the threads (two-byte loads / LDS-DMA pieces), whether a frame's eight workgroups share an XCD,
-//   with and without the ceiling subtraction; batches of 128 / 256 / 512 frames; a working set of 12 input and 12 output sets.
+//   variants: the two folds that exist — radix 8 (65536 points) and, with DIF_Q=16, radix 16 (131072 points): two residues per workgroup,
+//   LDS-DMA pieces, a butterfly per point, a frame's workgroups on one XCD; batches of 128 / 256 / 512 frames; a working set of 12 input
+//   and 12 output sets. (The variants measured in rounds 5 and 6 and since retired — two-byte loads, one residue per workgroup, a frame's
+//   residues over eight XCDs, the accumulating folds — are in profiles/r05/s1_dif8_lab.txt, s3_dif8_lab_two_residues.txt and
+//   profiles/r06/s2_dif8_lab_accumulating.txt, s5_dif16_lab_accumulating.txt.)
 //   build: make -C scripts/ubench dif8_lab      run: gpurun -- scripts/ubench/dif8_lab [frames ...]   (DIF8_ONLY=<variant index>: that one only, for PMC passes)
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -28,29 +31,20 @@
     }                                                                                 \
   } while (0)
 
-// XMAP 1: block b -> XCD b mod 8 (round-robin dispatch); the eight residues of frame f are blocks 64 (f / 8) + 8 r + (f mod 8): one XCD,
-// 64 consecutive block numbers. XMAP 0: b = 8 f + r — a frame's residues on eight different XCDs.
-template <int FMT, int FRONT, int XMAP>
-__global__ __launch_bounds__(512, FRONT >= 3 ? 4 : 8) void k_dif8_lab(ss::Fft8192Args g, ss::Dif8Front d) {
+// Block b -> XCD b mod 8 (round-robin dispatch); dif8_item gives the workgroups of a frame consecutive block numbers of one residue
+// class mod 8: one XCD.
+template <int FMT, int FRONT>
+__global__ __launch_bounds__(512, 4) void k_dif8_lab(ss::Fft8192Args g, ss::Dif8Front d) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int b = (int)blockIdx.x;
-  int f, r;
-  if (FRONT == 4 || FRONT == 6) {  // 131072 points, radix 16: eight workgroups per frame (residues r and r + 8 each; 6: the fold as a butterfly per point)
+  int f, r, hdr;
+  if (FRONT == ss::kFrontFold16) {  // 131072 points, radix 16: eight workgroups per frame (residues r and r + 8 each)
     ss::dif8_item<8>(b, d.nframes, &f, &r);
-    int hdr;
     ss::fft8192_v2_frame<FMT, 2, true, false, FRONT>(g, (size_t)(16 * f + r), smem_raw, (int)threadIdx.x, &hdr, &d, (size_t)f, r);
-    return;
-  }
-  if (FRONT == 3 || FRONT == 5) {  // four workgroups per frame (residues r and r + 4 each; 5: the fold as a butterfly per point)
+  } else {  // 65536 points, radix 8: four workgroups per frame (residues r and r + 4 each)
     ss::dif8_item<4>(b, d.nframes, &f, &r);
-  } else if (XMAP) {
-    ss::dif8_item<8>(b, d.nframes, &f, &r);
-  } else {
-    r = b & 7;
-    f = b >> 3;
+    ss::fft8192_v2_frame<FMT, 2, true, false, FRONT>(g, (size_t)(8 * f + r), smem_raw, (int)threadIdx.x, &hdr, &d, (size_t)f, r);
   }
-  int hdr;
-  ss::fft8192_v2_frame<FMT, 2, true, false, FRONT>(g, (size_t)(8 * f + r), smem_raw, (int)threadIdx.x, &hdr, &d, (size_t)f, r);
 }
 
 static void fft_inplace(std::vector<std::complex<double>>& x) {  // radix-2, forward
@@ -79,7 +73,7 @@ static void fft_inplace(std::vector<std::complex<double>>& x) {  // radix-2, for
 
 struct Variant {
   const char* name;
-  int front, xmap;
+  int front;
 };
 
 int main(int argc, char** argv) {
@@ -92,7 +86,7 @@ int main(int argc, char** argv) {
   const int only = only_s ? atoi(only_s) : -1;
   hipDeviceProp_t prop;
   CK(hipGetDeviceProperties(&prop, 0));
-  printf("# device %s, %d CUs; SS_AUX_DIF_IQ=%d (the rows leave as dB values)\n", prop.name, prop.multiProcessorCount, SS_AUX_DIF_IQ);
+  printf("# device %s, %d CUs; kAuxDifIq=%d (the rows leave as dB values)\n", prop.name, prop.multiProcessorCount, ss::kAuxDifIq);
 
   const int Q = getenv("DIF_Q") ? atoi(getenv("DIF_Q")) : 8, logq = Q == 16 ? 4 : 3;  // DIF_Q=16: 131072-point frames, radix 16 (the two-residue form only)
   const int N = 8192 * Q;
@@ -151,16 +145,10 @@ int main(int argc, char** argv) {
   CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
 
   const Variant variants[] = {
-      {"two-byte loads, a frame's residues on ONE XCD", 1, 1},
-      {"LDS-DMA pieces, a frame's residues on ONE XCD", 2, 1},
-      {"two-byte loads, residues over eight XCDs", 1, 0},
-      {"LDS-DMA pieces, residues over eight XCDs", 2, 0},
-      {"LDS-DMA pieces, TWO residues per workgroup (128 VGPRs), ONE XCD", 3, 1},
-      {"131072 points, radix 16, TWO residues per workgroup, ONE XCD", 4, 1},
-      {"LDS-DMA pieces, TWO residues per workgroup, radix-8 BUTTERFLY per point", 5, 1},
-      {"131072 points, radix 16, TWO residues per workgroup, BUTTERFLY per point", 6, 1},
+      {"LDS-DMA pieces, TWO residues per workgroup, radix-8 BUTTERFLY per point", ss::kFrontFold8},
+      {"131072 points, radix 16, TWO residues per workgroup, BUTTERFLY per point", ss::kFrontFold16},
   };
-  const int nvariants = 8;
+  const int nvariants = 2;
   const auto launch = [&](const Variant& v, int set, int frames, hipEvent_t e0, hipEvent_t e1) {
     ss::Fft8192Args g{};
     g.tabs = tabs;
@@ -171,16 +159,10 @@ int main(int argc, char** argv) {
     d.smax = d_seg[set];
     d.smax_mask = 1023;
     d.nframes = frames;
-    const dim3 grid((v.front == 3 || v.front == 5 ? 4 : 8) * frames), block(512);  // (radix 16, two residues each: eight per frame too)
-#define GO(FRONT, XMAP) hipExtLaunchKernelGGL((k_dif8_lab<ss::FMT_CS8, FRONT, XMAP>), grid, block, ss::kFft8192V2LdsBytes, st, e0, e1, 0, g, d)
-    if (v.front == 4) GO(4, 1);
-    else if (v.front == 6) GO(6, 1);
-    else if (v.front == 5) GO(5, 1);
-    else if (v.front == 3) GO(3, 1);
-    else if (v.front == 1 && v.xmap == 1) GO(1, 1);
-    else if (v.front == 2 && v.xmap == 1) GO(2, 1);
-    else if (v.front == 1 && v.xmap == 0) GO(1, 0);
-    else GO(2, 0);
+    const dim3 grid((v.front == ss::kFrontFold8 ? 4 : 8) * frames), block(512);  // (radix 16, two residues each: eight per frame too)
+#define GO(FRONT) hipExtLaunchKernelGGL((k_dif8_lab<ss::FMT_CS8, FRONT>), grid, block, ss::kFft8192V2LdsBytes, st, e0, e1, 0, g, d)
+    if (v.front == ss::kFrontFold16) GO(ss::kFrontFold16);
+    else GO(ss::kFrontFold8);
 #undef GO
   };
 
@@ -201,7 +183,7 @@ int main(int argc, char** argv) {
     }
     for (int vi = 0; vi < nvariants; ++vi) {
       if (only >= 0 && vi != only) continue;
-      if ((Q == 16) != (variants[vi].front == 4 || variants[vi].front == 6)) continue;
+      if ((Q == 16) != (variants[vi].front == ss::kFrontFold16)) continue;
       CK(hipMemset(d_out[0], 0xff, out_bytes));
       launch(variants[vi], 0, max_frames, nullptr, nullptr);
       CK(hipStreamSynchronize(st));
@@ -231,7 +213,7 @@ int main(int argc, char** argv) {
   for (int frames : frame_counts) {
     for (int vi = 0; vi < nvariants; ++vi) {
       if (only >= 0 && vi != only) continue;
-      if ((Q == 16) != (variants[vi].front == 4 || variants[vi].front == 6)) continue;
+      if ((Q == 16) != (variants[vi].front == ss::kFrontFold16)) continue;
       for (int k = 0; k < 12; ++k) launch(variants[vi], k % nsets, frames, nullptr, nullptr);
       CK(hipStreamSynchronize(st));
       hipEvent_t w0, w1;

@@ -1,4 +1,4 @@
-// Host-side check of the index algebra behind the tile culling of long transforms (csrc/fft256_kernels.h, csrc/detect_fused.h):
+// Host-side check of the index algebra behind the tile culling of long transforms (csrc/fft256_kernels.h, csrc/plan_long.h, csrc/detect_fused.h):
 // compiled with hipcc for the HOST only and run on the CPU by tests/test_host_index_algebra.py — no GPU, no HIP call.
 //   * rows_smax_index is a bijection from (tile column, run) onto a frame's row of run maxima, and it is the place the rows
 //     kernel's workgroup (c, r0) writes for d = t: the 32-bin run that starts at bin (r0 + 256 c + (t << log_row)) ^ (N / 2);

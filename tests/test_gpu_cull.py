@@ -1,4 +1,4 @@
-"""Tile culling (csrc/detect_fused.h): a 16-frame x 256-bin averaging tile whose per-segment PSD maxima (left by the FFT
+"""Tile culling (csrc/detect_fused.h; the long transforms' plans: csrc/plan_long.h): a 16-frame x 256-bin averaging tile whose per-segment PSD maxima (left by the FFT
 role) show that no bin can reach start_level is not evaluated. The decision must be EXACT: the candidate lists with
 culling equal those with SS_FLAG_NO_CULL bit for bit, and both equal the reference's own code (oracle/_ref) — on the
 host-buffer path, on the deep-pipelined device path, with ignored ranges, weak signals just around the threshold, degenerate
@@ -143,7 +143,7 @@ def test_short_calls_between_long_ones():
     assert sum(len(x) for x in res["cull"]) > 50_000
 
 
-# ---- long transforms (N = 256 x N2: csrc/detect_fused.h, k_plan_long): the rows kernel leaves the maximum of every 32-bin run
+# ---- long transforms (N = 256 x N2: csrc/plan_long.h, k_plan_long): the rows kernel leaves the maximum of every 32-bin run
 # per frame and writes the averager ring itself; tiles whose 36 rows cannot reach start_level are not evaluated — rows from
 # BEFORE the batch included, so short calls cull too. Same bar: culled == unculled, list by list, key by key.
 # The product library culls at 65536 points too since session 20 of round 4 (the plan, detect and emit stages of a call ride on the

@@ -1,5 +1,5 @@
 """The detection settings on the product paths: candidate detection is `start_level <= avg && pass(i)` behind tile culling
-(csrc/detect_fused.h: plan_tiles, plan_long_run, plan_x256_run), and start_level is a per-device user setting
+(csrc/detect_fused.h: plan_tiles; csrc/plan_long.h: plan_long_run, plan_dif8_run, plan_x256_run), and start_level is a per-device user setting
 (start_recording_level). Everything else that exercises culling runs at the default of 8 dB, where the synthetic band
 separates cleanly — noise tiles 4 dB below the cut, comb tiles 14 dB above it. Here, on every culled path of the product library:
 
@@ -18,6 +18,8 @@ separates cleanly — noise tiles 4 dB below the cut, comb tiles 14 dB above it.
 No number here comes from the engine: levels, expected lists and counts come from one oracle run per stream
 (parity.lists_at_level, anchored against the oracle's own lists by tests/test_cull_bound_math.py). Needs an MI355X: run with -m gpu."""
 import functools
+import json
+import os
 
 import numpy as np
 import pytest
@@ -30,7 +32,7 @@ pytestmark = pytest.mark.gpu
 CENTER = 145_000_000
 CF32, CS8 = "cf32", "cs8"
 # one row per culled path of the product library. cuts: the calls (the learning frames a call of their own on the device paths,
-# as the shipped forms want them); reach: what a tile's maximum M covers (detect_fused.h: 256 bins and a 32-bin run on either side,
+# as the shipped forms want them); reach: what a tile's maximum M covers (plan_long.h: 256 bins and a 32-bin run on either side,
 # or the whole neighbouring columns for the fold's per-column values); seed: chosen on the CPU so that the oracle's own avg plane
 # holds at most dont_care_limit values inside the band around each level (asserted below; 0 .. 2 per level for these seeds, 9 of a
 # limit of 15 at 3 dB on the deep 8192-point path; seeds 801, 805 and 806 had 8, 5 and 2 at 22 dB / the straddle level and were
@@ -49,6 +51,11 @@ PATHS = {
 LEVELS = {"straddle": None, "15": 15.0, "22": 22.0, "3": 3.0, "8+2^-10": 8.0 + 2.0 ** -10}
 DENSE = -30.0
 SENTINEL_IDX, SENTINEL_AVG = 0x5A5A5A5A, -12345.0
+# tiles_total / tiles_tested / tiles_culled of the culling run of every (path, level) pair of (a), recorded from the commit before the long
+# plans moved to csrc/plan_long.h (two runs on an MI355X, equal for every pair: integers out of fp32 sums in a fixed order). Culled ==
+# unculled cannot see a plan that lists too much, and 0 < culled < tested cannot see one that is off by a few: equal counts can.
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_counts_parent.json")) as _fh:
+    PLAN_COUNTS = json.load(_fh)
 
 
 @functools.lru_cache(maxsize=None)
@@ -176,6 +183,7 @@ def test_start_levels_culled_equal_unculled_and_the_oracle(name, key):
     np.testing.assert_array_equal(idx, idx_nc)
     np.testing.assert_array_equal(avg, avg_nc)
     assert st_nc["tiles_culled"] == 0
+    assert {k: st[k] for k in ("tiles_total", "tiles_tested", "tiles_culled")} == PLAN_COUNTS[name][key]
     diff = np.setxor1d(_keys(off, idx, n), _keys(ref_off, ref_idx, n))
     outside = [(int(k // n), int(k % n)) for k in diff if not abs(ref["avg"][k // n, k % n] - np.float32(level)) < BAND]
     assert not outside, f"candidate sets differ outside the {BAND} dB band around {level}: {outside[:10]}"
