@@ -88,6 +88,15 @@ def bind(lib: C.CDLL, prefix: str) -> None:
     f("read_noise").restype = C.c_int
 
 
+STF_RING_EXPORTS = ("stf_create_ring",)  # include/specscan_track_feed_ring.h
+
+
+def bind_track_feed_ring(lib: C.CDLL) -> None:
+    """stf_create_ring(ss_feed*, const stf_config*, stf_ctx**): the feed, tracker.StfConfig by reference, the new object."""
+    lib.stf_create_ring.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.stf_create_ring.restype = C.c_int
+
+
 def apply_overrides(cfg, overrides: dict) -> list:
     """Set ss_config fields from keyword overrides; returns the arrays the config points into (keep them alive)."""
     keep = []

@@ -90,6 +90,7 @@ def build_replay_tool(force: bool = False, verbose: bool = False) -> str:
             *[os.path.join(HOST_DIR, f) for f in RECORDING_HEADERS], os.path.join(HERE, "..", "include", "specscan_record_feed.h"),
             os.path.join(HERE, "..", "include", "specscan_channelizer.h"),
             os.path.join(HERE, "..", "include", "specscan_track_feed.h"), os.path.join(HERE, "..", "include", "specscan_track_sparse.h"),
+            os.path.join(HERE, "..", "include", "specscan_track_feed_ring.h"),
             os.path.join(HERE, "..", "include", "specscan_spectrogram_feed.h"), LIB]
     if force or not os.path.exists(REPLAY_TOOL) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(REPLAY_TOOL):
         build_lib()

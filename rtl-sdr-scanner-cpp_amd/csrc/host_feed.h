@@ -22,6 +22,7 @@ struct sgf_plan {
 namespace {
 // the riders' hooks, under the context's lock
 int stf_enqueue(ss_feed* f, int slot, int nframes);  // ss_feed_submit, behind the result copies
+bool stf_wants_no_plane_calls(const ss_feed* f);     // ss_feed_submit, in front of the batch: a ring tracker is bound (stf_create_ring)
 // feed_collect on a tracked feed: the slot's digest, its read-back enqueued on the feed's read-back stream (*copies: something was)
 int stf_collect_digest(ss_feed* f, int slot, int nframes, int ncopy, stf_result* digest, bool* copies);
 int sgf_plan_batch(ss_feed* f, int nframes, const int64_t* t_ms, sgf_plan* plan);  // ss_feed_submit, in front of the upload
@@ -237,7 +238,8 @@ int ss_feed_submit(ss_feed* f, int32_t nframes, const int64_t* t_ms, int64_t use
   const int n_learn = plan_learning(c, z, nframes, t_ms);
   const bool want_cands = f->cand_cap > 0;
   st = run_batch(c, s.d_in.get(), (long long)n, nframes, n_learn, z,
-                 CallOut{nullptr, nullptr, nullptr, s.d_off.get(), want_cands ? s.d_idx.get() : nullptr, want_cands ? s.d_avg.get() : nullptr, f->cand_cap});
+                 CallOut{nullptr, nullptr, nullptr, s.d_off.get(), want_cands ? s.d_idx.get() : nullptr, want_cands ? s.d_avg.get() : nullptr, f->cand_cap},
+                 stf_wants_no_plane_calls(f));  // (false on every feed without a ring tracker: the call is what it has always been)
   if (st != SS_OK) return st;
   flush_stages(c);  // the slot's results are copied out right behind the batch
   SS_HIP(c, hipMemcpyAsync(s.h_off.get(), s.d_off.get(), sizeof(int32_t) * ((size_t)nframes + 1), hipMemcpyDeviceToHost, c->stream));

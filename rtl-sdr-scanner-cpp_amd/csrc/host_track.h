@@ -193,7 +193,7 @@ bool last_det_is_the_batch(const ss_ctx* c, int nframes) {
   return c->last_det_ok && c->last_det.psd == batch_rows && c->last_det.nframes == nframes && c->last_det.n == c->n && c->last_det.avg_sparse == c->last_avg;
 }
 
-int st_replay_watch_tiles(st_ctx* t, int nframes, int nwatch) {
+int st_replay_watch_tiles(st_ctx* t, int nframes, int nwatch, int layout) {
   ss_ctx* c = t->scan;
   const int n = c->n;
   // (st_digest has checked last_det_is_the_batch before its first launch)
@@ -224,7 +224,6 @@ int st_replay_watch_tiles(st_ctx* t, int nframes, int nwatch) {
   wa.evaluated = t->d_sp_evaluated.get();
   const int frame_tiles = (nframes + wa.det.shift + kFusedTF - 1) / kFusedTF;
   const dim3 grid((unsigned)(frame_tiles * t->ncols));
-  const int layout = c->last_rows_perm8 ? (c->dif_logq == 4 ? 4 : 3) : 0;
   if (layout == 4) hipLaunchKernelGGL(ss::k_digest_tiles<4>, grid, dim3(256), 0, c->stream, wa);
   else if (layout == 3) hipLaunchKernelGGL(ss::k_digest_tiles<3>, grid, dim3(256), 0, c->stream, wa);
   else hipLaunchKernelGGL(ss::k_digest_tiles<0>, grid, dim3(256), 0, c->stream, wa);
@@ -340,7 +339,8 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
     return obj_fail(t, SS_ERR_INVALID, "%llu batches went by without st_digest: the kept rel rows are stale until st_reset", c->batch_no - t->seen_batch - 1);
   if (c->last_retunes != c->retunes) return obj_fail(t, SS_ERR_INVALID, "ss_set_frequency_range since the last batch: its noise ceiling is not the current one");
   // (a sparse object also digests a call that left no dB plane: its rows are in the averager ring's buffer, track_digest_sparse.h)
-  const bool ring_call = t->sparse && c->fused && !c->last_psd && c->last_rel_rows;
+  const ss::RowsChoice src = ss::decide_rows_source(c->last_psd != nullptr, c->last_rel_rows != nullptr, c->last_rows_perm8, c->dif_logq);  // (rows_source.h)
+  const bool ring_call = t->sparse && c->fused && src.source == ss::kRowsRing;
   if (!c->last_avg || (c->fused && ((!c->last_psd && !ring_call) || !c->last_thr))) return obj_fail(t, SS_ERR_INVALID, "the last batch left no dB plane, avg plane or noise ceiling to digest");
   // (defence only, see ring_rows: nothing settles rows between a call and its digest that is not refused above)
   if (ring_call && c->last_settled_lo && c->last_settled_lo > c->last_rel_rows && c->last_settled_hi < c->last_rel_rows + (size_t)nframes * (size_t)n)
@@ -411,7 +411,7 @@ int st_digest(st_ctx* t, const int32_t* cand_off, const int32_t* cand_idx, const
     memcpy(t->h_watch.get(), w.data(), sizeof(int32_t) * (size_t)nwatch);
     ST_HIP(t, hipMemcpyAsync(t->d_watch.get(), t->h_watch.get(), sizeof(int32_t) * (size_t)nwatch, hipMemcpyHostToDevice, c->stream));
     if (t->sparse) {  // avg where the windows lie: nothing but the tiles with hits has written the sparse plane
-      const int st_replay = st_replay_watch_tiles(t, nframes, nwatch);
+      const int st_replay = st_replay_watch_tiles(t, nframes, nwatch, src.layout);
       if (st_replay != SS_OK) return st_replay;
     }
     ss::WindowPeaksArgs p{};

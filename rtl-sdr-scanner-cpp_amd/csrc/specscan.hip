@@ -36,6 +36,7 @@
 #include "../../include/specscan_track.h"
 #include "../../include/specscan_track_feed.h"
 #include "../../include/specscan_track_sparse.h"
+#include "../../include/specscan_track_feed_ring.h"
 #include "../../include/specscan_track_digest_sparse.h"
 #include "../../include/specscan_record_feed.h"
 #include "../../include/specscan_spectrogram_feed.h"
@@ -51,6 +52,7 @@
 #include "fft_kernels.h"
 #include "plan_long.h"
 #include "ring_place.h"
+#include "rows_source.h"
 #include "scan_form.h"
 #include "scan_step.h"
 #include "spectrogram_gate.h"

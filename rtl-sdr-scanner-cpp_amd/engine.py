@@ -232,15 +232,18 @@ class Feed:
             self._lib.ss_feed_destroy(self._h)
             self._h = None
 
-    def track(self, group_size: int, start_level: float | None = None, max_watch: int = 1024, sparse: bool = False):
+    def track(self, group_size: int, start_level: float | None = None, max_watch: int = 1024, sparse: bool = False, ring: bool = False):
         """The tracking digest behind this feed (include/specscan_track_feed.h; the engine needs ``flags=SS_FLAG_KEEP_PLANES``): from now
         on every submitted batch is digested in the stream, and the returned object's ``collect()`` — instead of this one's — delivers
         the batch with its digest for ``tracker.SignalTracker.process_batch_digest``; ``post_keys(seq, keys)``, ``reset()``, ``close()``.
         ``sparse=True`` (include/specscan_track_sparse.h): the engine needs no SS_FLAG_KEEP_PLANES — the scan stays on its culled path and
         writes no avg plane, the tile columns the watch windows touch are evaluated once more behind the batch; the same digest, bit for
-        bit, and ``sparse_stats()`` says how many tiles that took."""
+        bit, and ``sparse_stats()`` says how many tiles that took. Up to 32768 points.
+        ``sparse=True, ring=True`` (include/specscan_track_feed_ring.h): ... at every size. From 65536 points up the batches then go
+        through the feed as ``process_device`` makes its calls — the fold, the culled chains, the ring-only calls, none of which
+        keeps a dB plane — and a batch that kept none is digested from the rows it left in the averager ring's buffer."""
         from .tracker import TrackedFeed
-        return TrackedFeed(self, group_size, self._e.cfg.start_level if start_level is None else start_level, max_watch, sparse=sparse)
+        return TrackedFeed(self, group_size, self._e.cfg.start_level if start_level is None else start_level, max_watch, sparse=sparse, ring=ring)
 
     def record(self, bandwidth: int, channels: int = 4, **kw):
         """A recorder bound to this feed (include/specscan_record_feed.h; the engine needs ``decim=1``, or the feed ``items=True``):

@@ -5,7 +5,7 @@
 // earlier batches cross PCIe and run. Optionally writes the raw PSD rows as the reference's DEBUG_SAVE_FULL_POWER
 // dump would (`..._power.raw`, sdr_device.cpp:173-176).
 //
-//   specscan_replay <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse [--bandwidth HZ]]
+//   specscan_replay <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse | --track-ring [--bandwidth HZ]]
 //                   [--spectrogram-out FILE [--spectrogram-max-rows R]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]
 // Prints one JSON line: frames, batches, candidates, seconds, MS/s (file + PCIe inclusive).
 //
@@ -16,11 +16,13 @@
 // --track-sparse: the same tracker and the same JSON, but the context keeps no planes (no SS_FLAG_KEEP_PLANES): the tracked feed is a
 // sparse one (include/specscan_track_sparse.h) that re-evaluates the tile columns the watch windows touch behind every batch. The JSON
 // line gains `tiles_evaluated` and `tiles_in_batches` (stf_sparse_stats).
+// --track-ring: --track-sparse at every transform size (include/specscan_track_feed_ring.h): from 65536 points up the batches take the
+// scan's forms that keep no dB plane and are digested from the rows they leave in the averager ring's buffer. The same JSON.
 // --spectrogram-out FILE: the feed delivers the spectrogram rows (include/specscan_spectrogram_feed.h; the context gets
 // SS_FLAG_SPECTROGRAM). Frame k carries the time nearbyint(k * period), period = 1000 * N * D / fs ms — the clock the reference's
 // per-frame send gate runs on — and every row a batch closes is written to FILE as its DataController::pushSpectrogram payload
 // (ss_spectrogram_payload) behind its length as a little-endian uint32. The JSON line gains `spectrogram_rows`.
-// --record-out FILE (needs --track or --track-sparse): the transmissions the tracker finds are recorded from the feed's own upload
+// --record-out FILE (needs --track, --track-sparse or --track-ring): the transmissions the tracker finds are recorded from the feed's own upload
 // (host/feed_recorder.h: RangePlanner -> srf_record -> RecordingStore; --recorders R slots, default 4; the recording bandwidth is
 // --bandwidth). After each stf_collect the consumer runs the tracker over the batch's frames, posts the keys and hands the frames'
 // lists to the FeedRecorder. With decim != 1 the feed is a whole-item feed (ss_feed_create_items) and the dump is read in whole items
@@ -31,6 +33,7 @@
 #include <specscan.h>
 #include <specscan_spectrogram_feed.h>
 #include <specscan_track_feed.h>
+#include <specscan_track_feed_ring.h>
 #include <specscan_track_sparse.h>
 
 #include <chrono>
@@ -57,7 +60,7 @@ struct Options {
   int min_time_ms = -1, timeout_ms = -1;  // < 0: TrackerConfig's own
   int spectrogram_max_rows = 8;
   int fft = 0, decim = 0, batch = 1024, depth = 3, learn_frames = -1;
-  bool track = false, track_sparse = false;
+  bool track = false, track_sparse = false, track_ring = false;
   int bandwidth = 32000;  // Config::recordingBandwidth: the tracker's windows are ceil(bandwidth / (fs / N)) bins wide
 };
 
@@ -83,6 +86,8 @@ bool parse_args(int argc, char** argv, Options* o) {
       o->track = true;
     } else if (a == "--track-sparse") {
       o->track = o->track_sparse = true;
+    } else if (a == "--track-ring") {
+      o->track = o->track_sparse = o->track_ring = true;
     } else if (a == "--bandwidth") {
       if (!next(&o->bandwidth) || o->bandwidth <= 0) return false;
     } else if (a == "--spectrogram-out") {
@@ -117,7 +122,7 @@ bool parse_args(int argc, char** argv, Options* o) {
 int main(int argc, char** argv) {
   Options opt;
   if (!parse_args(argc, argv, &opt)) {
-    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]\n", argv[0]);
+    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse | --track-ring [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]\n", argv[0]);
     return 2;
   }
   specscan::RawFileInfo info;
@@ -166,8 +171,9 @@ int main(int argc, char** argv) {
   if (opt.timeout_ms >= 0) tc.timeout_ms = opt.timeout_ms;
   if (opt.track) {
     stf_config tcfg{STF_ABI_VERSION, tc.group_size, cfg.start_level, 4096};
-    if ((opt.track_sparse ? stf_create_sparse(feed, &tcfg, &tracked) : stf_create(feed, &tcfg, &tracked)) != SS_OK) {
-      fprintf(stderr, "%s: %s\n", opt.track_sparse ? "stf_create_sparse" : "stf_create", stf_last_error(nullptr));
+    const auto create = opt.track_ring ? stf_create_ring : opt.track_sparse ? stf_create_sparse : stf_create;
+    if (create(feed, &tcfg, &tracked) != SS_OK) {
+      fprintf(stderr, "%s: %s\n", opt.track_ring ? "stf_create_ring" : opt.track_sparse ? "stf_create_sparse" : "stf_create", stf_last_error(nullptr));
       ss_feed_destroy(feed);
       ss_destroy(ctx);
       return 1;

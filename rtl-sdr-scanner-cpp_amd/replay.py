@@ -187,7 +187,8 @@ def engine_overrides_for(info: RawFileInfo) -> dict:
 
 def replay_file(engine, path: str, kind: int | None = None, batch: int | None = None, depth: int = 3, cand_cap: int = 1 << 20,
                 want_psd: bool = False, frame_period_ms: float | None = None, stats: ReplayStats | None = None, read_threads: int = 4,
-                spectrogram=None, spectrogram_max_rows: int = 8, items: bool = False):
+                spectrogram=None, spectrogram_max_rows: int = 8, items: bool = False, track: str | None = None, track_group_size: int = 128,
+                track_max_watch: int = 4096, track_keys=None):
     """Generator: streams the dump through ``engine`` (a SpectrumEngine whose in_format matches the file) and yields
     one result dict per batch, in order (copies: safe to keep). A reader thread fills pinned slots; up to ``depth - 1``
     batches are in flight behind the one being read.
@@ -203,7 +204,14 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
 
     items: read the dump's whole items of fft_size * decim samples into an items feed (``engine.feed(items=True)``), which keeps
     them in its pinned slots and uploads the first fft_size of each: candidates and rows are the same, and a recorder bound
-    to such a feed has the whole stream to record from."""
+    to such a feed has the whole stream to record from.
+
+    track: "ring" — the feed is tracked through ``Feed.track(..., sparse=True, ring=True)`` (stf_create_ring: the engine needs no
+    SS_FLAG_KEEP_PLANES, and from 65536 points up the batches take the scan's forms that keep no dB plane), with windows of
+    ``track_group_size`` bins and room for ``track_max_watch`` watch keys. Every result then carries its digest, as ``TrackedFeed.collect`` returns it, for ``tracker.SignalTracker.process_batch_digest``; ``track_keys``, a callable
+    taking the result and returning the tracker's keys behind it, has them posted for the batches submitted from then on."""
+    if track not in (None, "ring"):
+        raise ValueError('track: None or "ring"')
     cfg = engine.cfg
     if kind is None:
         kind = parse_raw_file_name(path).kind
@@ -215,6 +223,9 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
         raise ValueError("batch must be in 1..max_batch")
     reader = RawIqReader(path, kind, cfg.fft_size * cfg.decim, 1) if items else RawIqReader(path, kind, cfg.fft_size, cfg.decim)
     feed = engine.feed(depth=depth, cand_cap=cand_cap, want_psd=want_psd, items=items)
+    tracked = None
+    if track is not None:
+        tracked = feed.track(track_group_size, max_watch=track_max_watch, sparse=True, ring=True)
     rows = None
     if spectrogram is not None:
         rows = feed.spectrogram(max_rows=spectrogram_max_rows)
@@ -257,12 +268,14 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
             got = submitted.get()
             if got is None:
                 break
-            r = feed.collect()
+            r = tracked.collect() if tracked is not None else feed.collect()
             out = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
             out["first_frame"] = out.pop("tag")
             if rows is not None:
                 for payload in rows.payloads():
                     spectrogram(frame_payloads([payload]))
+            if tracked is not None and track_keys is not None and out["digest_status"] == 0:
+                tracked.post_keys(out["seq"], track_keys(out))
             free.release()
             st.frames += out["nframes"]
             st.batches += 1
@@ -278,5 +291,7 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
         st.seconds = time.perf_counter() - t_start
         if rows is not None:
             rows.close()
+        if tracked is not None:
+            tracked.close()
         feed.close()
         reader.close()

@@ -281,9 +281,11 @@ class TrackedFeed:
     """One stf_ctx bound to a Feed of an engine created with SS_FLAG_KEEP_PLANES (Feed.track): every batch submitted through the
     feed is digested in the stream behind its chain. ``collect`` replaces the feed's own; ``post_keys(seq, tracker.keys)`` after
     every collect keeps the watch lists short; ``reset`` goes with the engine's ``reset`` (feed drained first).
-    ``sparse=True``: stf_create_sparse — the engine may lack SS_FLAG_KEEP_PLANES (fused back end, up to 32768 points)."""
+    ``sparse=True``: stf_create_sparse — the engine may lack SS_FLAG_KEEP_PLANES (fused back end, up to 32768 points).
+    ``sparse=True, ring=True``: stf_create_ring (include/specscan_track_feed_ring.h) — ... at any size: from 65536 points up the
+    feed's batches take the forms that keep no dB plane, and are digested from the rows they leave in the averager ring's buffer."""
 
-    def __init__(self, feed, group_size: int, start_level: float = 8.0, max_watch: int = 1024, sparse: bool = False):
+    def __init__(self, feed, group_size: int, start_level: float = 8.0, max_watch: int = 1024, sparse: bool = False, ring: bool = False):
         from .abi import SpecscanError
         self._err = SpecscanError
         self._feed = feed  # (the feed and its engine must outlive the object; a feed closed first leaves it only close())
@@ -291,9 +293,15 @@ class TrackedFeed:
         self._result = bind_track_feed(self._lib)
         cfg = StfConfig(STF_ABI_VERSION, int(group_size), float(start_level), int(max_watch))
         h = C.c_void_p()
+        if ring and not sparse:
+            raise ValueError("ring=True goes with sparse=True (stf_create_ring is stf_create_sparse at every size)")
         if sparse:
             bind_track_sparse(self._lib)
-        st = (self._lib.stf_create_sparse if sparse else self._lib.stf_create)(feed._h, C.byref(cfg), C.byref(h))
+        if ring:
+            from .abi import bind_track_feed_ring
+            bind_track_feed_ring(self._lib)
+        create = self._lib.stf_create_ring if ring else self._lib.stf_create_sparse if sparse else self._lib.stf_create
+        st = create(feed._h, C.byref(cfg), C.byref(h))
         if st != 0:
             raise SpecscanError(st, (self._lib.stf_last_error(None) or b"").decode())
         self._h = h
