@@ -36,7 +36,8 @@ extern "C" {
 /* stf_create_sparse without its limit of 32768 points. Below 65536 points, and for every batch whose call left a bin-ordered dB
  * plane, the object behaves as stf_create_sparse's; on a context with SS_FLAG_KEEP_PLANES it is simply stf_create. While the object
  * is bound, a batch of 65536 points and up goes through the feed as ss_process_device makes its calls (no plane kept where the form
- * keeps none) unless the feed was created with want_psd or carries spectrogram rows. SS_ERR_INVALID, with the messages of
+ * keeps none) unless the feed was created with want_psd or carries sgf_create's spectrogram rows (sgf_create_ring's read the ring's
+ * buffer too: specscan_spectrogram_feed_ring.h). SS_ERR_INVALID, with the messages of
  * stf_create_sparse (stf_last_error(NULL)): the unfused back end, SS_FLAG_REFERENCE_NAN, a feed with cand_cap 0, a feed with
  * batches pending, a feed that has a tracker already, and everything stf_create refuses. */
 int stf_create_ring(ss_feed* feed, const stf_config* cfg, stf_ctx** out);

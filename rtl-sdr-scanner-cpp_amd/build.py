@@ -91,7 +91,7 @@ def build_replay_tool(force: bool = False, verbose: bool = False) -> str:
             os.path.join(HERE, "..", "include", "specscan_channelizer.h"),
             os.path.join(HERE, "..", "include", "specscan_track_feed.h"), os.path.join(HERE, "..", "include", "specscan_track_sparse.h"),
             os.path.join(HERE, "..", "include", "specscan_track_feed_ring.h"),
-            os.path.join(HERE, "..", "include", "specscan_spectrogram_feed.h"), LIB]
+            os.path.join(HERE, "..", "include", "specscan_spectrogram_feed.h"), os.path.join(HERE, "..", "include", "specscan_spectrogram_feed_ring.h"), LIB]
     if force or not os.path.exists(REPLAY_TOOL) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(REPLAY_TOOL):
         build_lib()
         cmd = [shutil.which("g++") or "g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Wpedantic", "-Werror",

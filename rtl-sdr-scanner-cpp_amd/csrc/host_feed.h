@@ -22,7 +22,8 @@ struct sgf_plan {
 namespace {
 // the riders' hooks, under the context's lock
 int stf_enqueue(ss_feed* f, int slot, int nframes);  // ss_feed_submit, behind the result copies
-bool stf_wants_no_plane_calls(const ss_feed* f);     // ss_feed_submit, in front of the batch: a ring tracker is bound (stf_create_ring)
+bool stf_wants_no_plane_calls(const ss_feed* f);     // ss_feed_submit, in front of the batch: a ring tracker or ring spectrogram object is bound and nothing reads the plane
+bool sgf_reads_ring_rows(const ss_feed* f);          // the bound spectrogram object is sgf_create_ring's (f->spectrogram != nullptr)
 // feed_collect on a tracked feed: the slot's digest, its read-back enqueued on the feed's read-back stream (*copies: something was)
 int stf_collect_digest(ss_feed* f, int slot, int nframes, int ncopy, stf_result* digest, bool* copies);
 int sgf_plan_batch(ss_feed* f, int nframes, const int64_t* t_ms, sgf_plan* plan);  // ss_feed_submit, in front of the upload
@@ -239,7 +240,7 @@ int ss_feed_submit(ss_feed* f, int32_t nframes, const int64_t* t_ms, int64_t use
   const bool want_cands = f->cand_cap > 0;
   st = run_batch(c, s.d_in.get(), (long long)n, nframes, n_learn, z,
                  CallOut{nullptr, nullptr, nullptr, s.d_off.get(), want_cands ? s.d_idx.get() : nullptr, want_cands ? s.d_avg.get() : nullptr, f->cand_cap},
-                 stf_wants_no_plane_calls(f));  // (false on every feed without a ring tracker: the call is what it has always been)
+                 stf_wants_no_plane_calls(f));  // (false on every feed without a ring tracker or ring spectrogram object: the call is what it has always been)
   if (st != SS_OK) return st;
   flush_stages(c);  // the slot's results are copied out right behind the batch
   SS_HIP(c, hipMemcpyAsync(s.h_off.get(), s.d_off.get(), sizeof(int32_t) * ((size_t)nframes + 1), hipMemcpyDeviceToHost, c->stream));
@@ -248,7 +249,7 @@ int ss_feed_submit(ss_feed* f, int32_t nframes, const int64_t* t_ms, int64_t use
     st = stf_enqueue(f, slot, nframes);
     if (st != SS_OK) return st;
   }
-  if (f->spectrogram) {  // the rows this batch closes: one kernel on the dB plane, then exactly their bytes to the slot's pinned memory
+  if (f->spectrogram) {  // the rows this batch closes: one kernel on the dB plane (or the rows in the ring's buffer), then exactly their bytes to the slot's pinned memory
     st = sgf_enqueue(f, slot, nframes, rows_plan);
     if (st != SS_OK) return st;
   }

@@ -14,8 +14,8 @@
 // How such a batch comes about. A batch goes through the feed as an ordinary call (run_batch: device_call = false), and an ordinary
 // call keeps its dB plane at every size (call_route.h: keeps_no_plane wants CallAsk::device). The fold, the culled chains' ring-only
 // calls and the 2^20-point ring-only calls are therefore forms no feed took before; while a ring tracker is bound, ss_feed_submit
-// hands run_batch device_call = true at 65536 points and up (stf_wants_no_plane_calls; not on a feed with want_psd or spectrogram
-// rows, whose copies read the plane). What CallAsk::device promises — the input stays untouched until the stages have run — the slot
+// hands run_batch device_call = true at 65536 points and up (stf_wants_no_plane_calls; not on a feed with want_psd or sgf_create's
+// spectrogram rows, which read the plane; sgf_create_ring's rows read the ring's buffer: below). What CallAsk::device promises — the input stays untouched until the stages have run — the slot
 // gives: d_in is written again only after the batch has been collected, and ss_feed_submit drains the stages right behind the call.
 // Nothing else reads the flag at these sizes: decide_call's deep branch (the only other reader) is 8192 points.
 //
@@ -68,6 +68,19 @@
 // The host-side state the digest is built from — last_psd, last_rel_rows, last_rows_perm8, last_rows_db, last_settled_*, last_n_learn,
 // last_thr, last_avg, last_det — is read once, in stf_enqueue, under the lock the batch's run_batch ran under; RelRows / RingRows /
 // WatchTilesArgs go into the launches by value. No form had to be refused.
+//
+// ---- the second reader: sgf_create_ring (include/specscan_spectrogram_feed_ring.h, host_spectrogram_feed.h) -----------------------
+// A ring spectrogram object's kernel (k_spec_rows over bin-order ring rows, k_spec_rows_ring over the fold's) reads batch k's rows in
+// the ring's buffer — last_rel_rows, nothing in front of them, no ceiling — once, on the context's stream, enqueued by sgf_enqueue in
+// batch k's own ss_feed_submit behind stf_enqueue, under the same lock acquisition. It is a reader of a subset of what digest k reads,
+// at the same point of the same stream, so every line above holds for it with "digest" read as "rows kernel": a later batch's fold,
+// merged or two-launch chain places its rows elsewhere and in a launch behind it; settle_ring_db (k_rows_sub_thr), place_ring's window
+// move (k_hist_shift) and set_ring_form's reorder are enqueued by later host calls on c->stream; and because ss_feed_submit runs
+// flush_stages behind every run_batch, the whole of batch k's rows — the merged chain's row half included — is in the stream in front
+// of it. The object also switches the feed to device-style calls with NO tracker bound (stf_wants_no_plane_calls): nothing in the
+// argument needs the digest to be there. What the kernel writes — the centre's sum row, the slot's rows — is its own, ordered by the
+// stream against the next batch's kernel and by ev_done against the collect. The host state it is built from (last_psd, last_rel_rows,
+// last_rows_perm8, last_rows_db, last_settled_*) is read once in sgf_enqueue and goes into the launch by value.
 #pragma once
 
 namespace {
@@ -305,9 +318,12 @@ int stf_collect_digest(ss_feed* f, int slot_no, int nframes, int ncopy, stf_resu
 // (call_route.h: CallAsk::device — what the fold, the culled chains and the ring-only calls ask for) when a ring tracker is bound and
 // nothing else on the feed reads the plane. Below 65536 points no such form exists, and an 8192-point call of that kind would
 // overlap on the library's own queues: those stay what they are through any feed.
+// A ring spectrogram object (sgf_create_ring) reads such a batch's rows where the ring tracker does, and switches the feed alone as
+// well; a plane-kind one (sgf_create) reads the plane and keeps every batch on it.
 bool stf_wants_no_plane_calls(const ss_feed* f) {
   const stf_ctx* t = static_cast<const stf_ctx*>(f->tracker);
-  return t && t->ring && f->c->n >= 65536 && !f->want_psd && !f->spectrogram;
+  const bool ring_rows = f->spectrogram && sgf_reads_ring_rows(f);
+  return ((t && t->ring) || ring_rows) && f->c->n >= 65536 && !f->want_psd && (!f->spectrogram || ring_rows);
 }
 
 // stf_create, stf_create_sparse and stf_create_ring: allow_sparse = the context may lack SS_FLAG_KEEP_PLANES (the object is a sparse one

@@ -40,6 +40,7 @@
 #include "../../include/specscan_track_digest_sparse.h"
 #include "../../include/specscan_record_feed.h"
 #include "../../include/specscan_spectrogram_feed.h"
+#include "../../include/specscan_spectrogram_feed_ring.h"
 #include "chan_ranges.h"
 #include "call_route.h"
 #include "ctx_buffers.h"
@@ -57,6 +58,7 @@
 #include "scan_step.h"
 #include "spectrogram_gate.h"
 #include "spectrogram_rows.h"
+#include "spectrogram_rows_ring.h"
 #include "stage_slots.h"
 #include "track_digest.h"
 #include "track_digest_blocked.h"

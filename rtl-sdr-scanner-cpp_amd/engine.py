@@ -218,6 +218,7 @@ class Feed:
         self._e, self._lib = engine, engine._lib
         self.cand_cap = int(cand_cap)
         self.items = bool(items)  # a whole-item feed: acquire() takes items of N*decim samples
+        self.last_submitted = 0
         h = C.c_void_p()
         create = self._lib.ss_feed_create_items if self.items else self._lib.ss_feed_create
         engine._check(create(engine._h, int(depth), int(cand_cap), int(bool(want_psd)), C.byref(h)))
@@ -253,12 +254,16 @@ class Feed:
         from .recorder import RecordedFeed
         return RecordedFeed(self, bandwidth, channels, **kw)
 
-    def spectrogram(self, max_rows: int = 8, want_mean: bool = False):
+    def spectrogram(self, max_rows: int = 8, want_mean: bool = False, ring: bool = False):
         """The spectrogram rows behind this feed (include/specscan_spectrogram_feed.h; the engine needs ``flags=SS_FLAG_SPECTROGRAM``):
         from now on every ``submit`` needs ``t_ms``, a row closes at every frame whose clock is more than 1000 ms past the last send —
-        the reference's per-frame gate — and the returned object's ``rows()`` gives the rows of the batch collected last."""
+        the reference's per-frame gate — and the returned object's ``rows()`` gives the rows of the batch collected last.
+        ``ring=True`` (include/specscan_spectrogram_feed_ring.h): the engine has NO SS_FLAG_SPECTROGRAM. From 65536 points up the
+        batches then go through the feed as ``process_device`` makes its calls — the fold, the culled chains, the ring-only calls,
+        none of which keeps a dB plane — and such a batch's rows are formed from the rows it left in the averager ring's buffer;
+        ``batch_db_rows()`` reads the dB values they were formed from."""
         from .spectrogram import SpectrogramFeed
-        return SpectrogramFeed(self, max_rows, want_mean)
+        return SpectrogramFeed(self, max_rows, want_mean, ring=ring)
 
     def __del__(self):
         try:
@@ -286,6 +291,7 @@ class Feed:
             t = np.ascontiguousarray(t_ms, dtype=np.int64)
             tp = t.ctypes.data_as(C.POINTER(C.c_int64))
         self._e._check(self._lib.ss_feed_submit(self._h, int(nframes), tp, int(tag)))
+        self.last_submitted = int(nframes)  # (SpectrogramFeed.batch_db_rows reads the batch submitted last)
 
     def collect(self) -> dict:
         r = abi.SsFeedResult()

@@ -6,7 +6,7 @@
 // dump would (`..._power.raw`, sdr_device.cpp:173-176).
 //
 //   specscan_replay <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse | --track-ring [--bandwidth HZ]]
-//                   [--spectrogram-out FILE [--spectrogram-max-rows R]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]
+//                   [--spectrogram-out FILE [--spectrogram-max-rows R] [--spectrogram-ring]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]
 // Prints one JSON line: frames, batches, candidates, seconds, MS/s (file + PCIe inclusive).
 //
 // --track: the feed is a tracked one (include/specscan_track_feed.h) — every batch is digested on the device behind its chain, and
@@ -22,6 +22,10 @@
 // SS_FLAG_SPECTROGRAM). Frame k carries the time nearbyint(k * period), period = 1000 * N * D / fs ms — the clock the reference's
 // per-frame send gate runs on — and every row a batch closes is written to FILE as its DataController::pushSpectrogram payload
 // (ss_spectrogram_payload) behind its length as a little-endian uint32. The JSON line gains `spectrogram_rows`.
+// --spectrogram-ring (with --spectrogram-out): the rows come from sgf_create_ring (include/specscan_spectrogram_feed_ring.h) — the
+// context is created WITHOUT SS_FLAG_SPECTROGRAM, so with --track-ring the batches of 65536 points and up keep taking the forms that
+// write no dB plane, and the rows are formed from what they leave in the averager ring's buffer. The same payloads; the JSON line
+// gains `"spectrogram_ring": true`. Without the switch --spectrogram-out makes every batch keep its plane, as ever.
 // --record-out FILE (needs --track, --track-sparse or --track-ring): the transmissions the tracker finds are recorded from the feed's own upload
 // (host/feed_recorder.h: RangePlanner -> srf_record -> RecordingStore; --recorders R slots, default 4; the recording bandwidth is
 // --bandwidth). After each stf_collect the consumer runs the tracker over the batch's frames, posts the keys and hands the frames'
@@ -32,6 +36,7 @@
 // --min-time-ms M / --timeout-ms T: Config::recordingMinTime / recordingTimeout of the tracker (2000 / 2000).
 #include <specscan.h>
 #include <specscan_spectrogram_feed.h>
+#include <specscan_spectrogram_feed_ring.h>
 #include <specscan_track_feed.h>
 #include <specscan_track_feed_ring.h>
 #include <specscan_track_sparse.h>
@@ -60,7 +65,7 @@ struct Options {
   int min_time_ms = -1, timeout_ms = -1;  // < 0: TrackerConfig's own
   int spectrogram_max_rows = 8;
   int fft = 0, decim = 0, batch = 1024, depth = 3, learn_frames = -1;
-  bool track = false, track_sparse = false, track_ring = false;
+  bool track = false, track_sparse = false, track_ring = false, spectrogram_ring = false;
   int bandwidth = 32000;  // Config::recordingBandwidth: the tracker's windows are ceil(bandwidth / (fs / N)) bins wide
 };
 
@@ -93,6 +98,8 @@ bool parse_args(int argc, char** argv, Options* o) {
     } else if (a == "--spectrogram-out") {
       if (i + 1 >= argc) return false;
       o->spectrogram_out = argv[++i];
+    } else if (a == "--spectrogram-ring") {
+      o->spectrogram_ring = true;
     } else if (a == "--spectrogram-max-rows") {
       if (!next(&o->spectrogram_max_rows)) return false;
     } else if (a == "--record-out") {
@@ -114,6 +121,7 @@ bool parse_args(int argc, char** argv, Options* o) {
     }
   }
   if (!o->record_out.empty() && !o->track) return false;  // nothing to record without the tracker's lists
+  if (o->spectrogram_ring && o->spectrogram_out.empty()) return false;
   return !o->path.empty();
 }
 
@@ -122,7 +130,7 @@ bool parse_args(int argc, char** argv, Options* o) {
 int main(int argc, char** argv) {
   Options opt;
   if (!parse_args(argc, argv, &opt)) {
-    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse | --track-ring [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]\n", argv[0]);
+    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse | --track-ring [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R] [--spectrogram-ring]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]\n", argv[0]);
     return 2;
   }
   specscan::RawFileInfo info;
@@ -137,7 +145,7 @@ int main(int argc, char** argv) {
   if (opt.learn_frames >= 0) cfg.learn_frames = opt.learn_frames;
   if (opt.track && !opt.track_sparse) cfg.flags |= SS_FLAG_KEEP_PLANES;  // the digest reads the kept dB and avg planes
   const bool want_rows = !opt.spectrogram_out.empty();
-  if (want_rows) cfg.flags |= SS_FLAG_SPECTROGRAM;
+  if (want_rows && !opt.spectrogram_ring) cfg.flags |= SS_FLAG_SPECTROGRAM;  // (sgf_create_ring wants a context without it)
   cfg.max_batch = opt.batch;
   if (info.kind == specscan::RawKind::CS8 || info.kind == specscan::RawKind::CU8) {
     cfg.in_format = info.kind == specscan::RawKind::CS8 ? SS_FMT_CS8 : SS_FMT_CU8;
@@ -183,7 +191,8 @@ int main(int argc, char** argv) {
   FILE* rows_file = nullptr;
   if (want_rows) {
     sgf_config rcfg{SGF_ABI_VERSION, opt.spectrogram_max_rows, 0};
-    if (sgf_create(feed, &rcfg, &rows) != SS_OK) fprintf(stderr, "sgf_create: %s\n", sgf_last_error(nullptr));
+    if ((opt.spectrogram_ring ? sgf_create_ring : sgf_create)(feed, &rcfg, &rows) != SS_OK)
+      fprintf(stderr, "%s: %s\n", opt.spectrogram_ring ? "sgf_create_ring" : "sgf_create", sgf_last_error(nullptr));
     else if (!(rows_file = fopen(opt.spectrogram_out.c_str(), "wb"))) fprintf(stderr, "%s: cannot open for writing\n", opt.spectrogram_out.c_str());
     if (!rows_file) {
       sgf_destroy(rows);
@@ -365,6 +374,7 @@ int main(int argc, char** argv) {
       if (tracked) printf(", \"transmissions\": %lld, \"tracked_frames\": %lld", transmissions, tracked_frames);
       if (opt.track_sparse) printf(", \"tiles_evaluated\": %llu, \"tiles_in_batches\": %llu", (unsigned long long)tiles_evaluated, (unsigned long long)tiles_in_batches);
       if (rows) printf(", \"spectrogram_rows\": %lld", spectrogram_rows);
+      if (rows && opt.spectrogram_ring) printf(", \"spectrogram_ring\": true");
       if (recorder) {
         const auto& c = recorder->counters();
         printf(", \"recorded_ranges\": %llu, \"recorded_samples\": %llu, \"published_items\": %llu, \"dropped_items\": %llu, "

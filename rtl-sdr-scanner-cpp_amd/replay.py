@@ -188,7 +188,7 @@ def engine_overrides_for(info: RawFileInfo) -> dict:
 def replay_file(engine, path: str, kind: int | None = None, batch: int | None = None, depth: int = 3, cand_cap: int = 1 << 20,
                 want_psd: bool = False, frame_period_ms: float | None = None, stats: ReplayStats | None = None, read_threads: int = 4,
                 spectrogram=None, spectrogram_max_rows: int = 8, items: bool = False, track: str | None = None, track_group_size: int = 128,
-                track_max_watch: int = 4096, track_keys=None):
+                track_max_watch: int = 4096, track_keys=None, spectrogram_ring: bool = False):
     """Generator: streams the dump through ``engine`` (a SpectrumEngine whose in_format matches the file) and yields
     one result dict per batch, in order (copies: safe to keep). A reader thread fills pinned slots; up to ``depth - 1``
     batches are in flight behind the one being read.
@@ -201,6 +201,9 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
     DataController::pushSpectrogram payload behind its length as a little-endian uint32, in order — the file
     ``specscan_replay --spectrogram-out`` writes. The rows close on the frames' clock, so without ``frame_period_ms`` the
     stream's own period, 1000 * fft_size * decim / sample_rate ms, is taken.
+
+    spectrogram_ring: the rows come from ``Feed.spectrogram(..., ring=True)`` (sgf_create_ring: the engine has NO
+    SS_FLAG_SPECTROGRAM, and from 65536 points up the batches take the scan's forms that keep no dB plane) — the same payloads.
 
     items: read the dump's whole items of fft_size * decim samples into an items feed (``engine.feed(items=True)``), which keeps
     them in its pinned slots and uploads the first fft_size of each: candidates and rows are the same, and a recorder bound
@@ -228,7 +231,7 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
         tracked = feed.track(track_group_size, max_watch=track_max_watch, sparse=True, ring=True)
     rows = None
     if spectrogram is not None:
-        rows = feed.spectrogram(max_rows=spectrogram_max_rows)
+        rows = feed.spectrogram(max_rows=spectrogram_max_rows, ring=spectrogram_ring)
         if frame_period_ms is None:
             frame_period_ms = 1000.0 * cfg.fft_size * cfg.decim / cfg.sample_rate
     st = stats if stats is not None else ReplayStats()

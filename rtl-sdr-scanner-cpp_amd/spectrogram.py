@@ -13,6 +13,7 @@ from .abi import SpecscanError
 SGF_ABI_VERSION = 1
 SGF_MAX_ROWS = 64
 SGF_EXPORTS = ("sgf_create", "sgf_destroy", "sgf_gate_plan", "sgf_last_error", "sgf_rows")
+SGF_RING_EXPORTS = ("sgf_batch_db_rows", "sgf_create_ring")  # include/specscan_spectrogram_feed_ring.h
 
 
 class SgfConfig(C.Structure):  # sgf_config
@@ -36,6 +37,16 @@ def bind_spectrogram_feed(lib: C.CDLL) -> C.CDLL:
     lib.sgf_rows.restype = C.c_int
     lib.sgf_gate_plan.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32), C.c_int32]
     lib.sgf_gate_plan.restype = C.c_int32
+    return lib
+
+
+def bind_spectrogram_feed_ring(lib: C.CDLL) -> C.CDLL:
+    """include/specscan_spectrogram_feed_ring.h on top of bind_spectrogram_feed."""
+    bind_spectrogram_feed(lib)
+    lib.sgf_create_ring.argtypes = [C.c_void_p, C.POINTER(SgfConfig), C.POINTER(C.c_void_p)]
+    lib.sgf_create_ring.restype = C.c_int
+    lib.sgf_batch_db_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float)]
+    lib.sgf_batch_db_rows.restype = C.c_int
     return lib
 
 
@@ -69,14 +80,19 @@ def frame_payloads(payloads) -> bytes:
 class SpectrogramFeed:
     """One sgf_ctx bound to a Feed of an engine with ``flags=SS_FLAG_SPECTROGRAM`` (``Feed.spectrogram``). From now on every
     ``submit`` needs ``t_ms``, and ``rows()`` after a collect (the feed's own, or a TrackedFeed's; also while a RecordedFeed holds
-    the batch) gives the rows that batch closed. The feed and its engine must outlive the object."""
+    the batch) gives the rows that batch closed. The feed and its engine must outlive the object.
+    ``ring=True`` (include/specscan_spectrogram_feed_ring.h, sgf_create_ring): the engine has NO SS_FLAG_SPECTROGRAM; from 65536
+    points up the batches then go through the feed as ``process_device`` makes its calls, and the rows of a batch that kept no dB
+    plane are formed from the rows it left in the averager ring's buffer."""
 
-    def __init__(self, feed, max_rows: int = 8, want_mean: bool = False):
+    def __init__(self, feed, max_rows: int = 8, want_mean: bool = False, ring: bool = False):
         self._feed = feed
-        self._lib = bind_spectrogram_feed(feed._lib)
+        self._lib = bind_spectrogram_feed_ring(feed._lib)
+        self.ring = bool(ring)
         self.cfg = SgfConfig(SGF_ABI_VERSION, int(max_rows), int(bool(want_mean)))
         h = C.c_void_p()
-        st = self._lib.sgf_create(feed._h, C.byref(self.cfg), C.byref(h))
+        create = self._lib.sgf_create_ring if self.ring else self._lib.sgf_create
+        st = create(feed._h, C.byref(self.cfg), C.byref(h))
         if st != 0:
             raise SpecscanError(st, (self._lib.sgf_last_error(None) or b"").decode())
         self._h = h
@@ -118,9 +134,21 @@ class SpectrogramFeed:
         out["payloads"] = payloads
         return out
 
+    def batch_db_rows(self, frame0: int = 0, nframes: int | None = None) -> np.ndarray:
+        """sgf_batch_db_rows: the dB rows [frame0, frame0 + nframes) of the batch SUBMITTED last, [nframes, N] float32 in bin order
+        (a copy), from the plane or from the ring's buffer, wherever the batch left them. ``nframes=None``: up to the batch's end."""
+        if nframes is None:
+            nframes = self._feed.last_submitted - int(frame0)
+        out = np.empty((int(nframes), self._feed._e.n), np.float32)
+        st = self._lib.sgf_batch_db_rows(self._h, int(frame0), int(nframes), out.ctypes.data_as(C.POINTER(C.c_float)))
+        if st != 0:
+            raise SpecscanError(st, (self._lib.sgf_last_error(self._h) or b"").decode())
+        return out
+
     def payloads(self) -> list:
         """``rows()["payloads"]()``: the payloads of the batch collected last."""
         return self.rows()["payloads"]()
 
 
-__all__ = ["SpectrogramFeed", "Gate", "SGF_EXPORTS", "SGF_ABI_VERSION", "SGF_MAX_ROWS", "bind_spectrogram_feed", "frame_payloads"]
+__all__ = ["SpectrogramFeed", "Gate", "SGF_EXPORTS", "SGF_RING_EXPORTS", "SGF_ABI_VERSION", "SGF_MAX_ROWS", "bind_spectrogram_feed", "bind_spectrogram_feed_ring",
+           "frame_payloads"]
