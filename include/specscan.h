@@ -75,7 +75,7 @@ typedef enum ss_plane {
 /* Also run the Spectrogram side branch (sources/radio/blocks/spectrogram.cpp): accumulate the bin-decimated raw
  * PSD per centre frequency; read it back with ss_spectrogram_read. */
 #define SS_FLAG_SPECTROGRAM 2u
-/* 8192-, 65536-, 131072- (int8), 262144- and 2^20-point frames: evaluate every averaging tile, also those whose per-frame maxima show that no window
+/* 8192-, 65536-, 131072- (int8, flagged CS16), 262144- and 2^20-point frames: evaluate every averaging tile, also those whose per-frame maxima show that no window
  * mean of the tile can reach start_level (csrc/detect_fused.h, tile culling). Results are identical either way — lists and
  * cand_avg bit for bit, at any start_level (tests/test_gpu_detect_settings.py) —; the flag exists so that the data-independent
  * cost of the chain can be measured (bench.py reports both). The transform is the same with and without the flag: int8 frames
@@ -99,6 +99,14 @@ typedef enum ss_plane {
  * degenerate row is inside the window and detects again at most 15 frames later. Needs the 21 x 21 grouping; calls run their
  * stages in order on ss_stream (as with SS_FLAG_STREAM_ORDERED). */
 #define SS_FLAG_REFERENCE_NAN 16u
+/* CS16 contexts of 65536 / 131072 points: calls that keep no plane take the work-buffer-free radix-8 / radix-16 fold (csrc/fft65536_dif8.h),
+ * under the conditions int8 contexts take it by default — default window, none of SS_FLAG_STREAM_ORDERED / REFERENCE_NAN / KEEP_PLANES /
+ * SPECTROGRAM — with tile culling at 131072 points too. It is a flag because the fold is a different rounding of the same transform:
+ * unflagged, CS16 is bit-identical to CF32 fed the converted samples (tests/test_gpu_cs16.py); flagged, it meets the oracle contract
+ * instead (tests/test_gpu_fold_cs16.py), as int8 contexts do, and int8 samples shifted left by eight bits give the int8 context's bits.
+ * Accepted and without effect wherever the fold cannot run: other sizes, a caller's window, the flags above, other formats (CS8 / CU8
+ * fold anyway, CF32 never does). ss_get_stats says which it is: SS_STATE_FOLD. */
+#define SS_FLAG_FOLD_CS16 32u
 
 #define SS_NO_DATA (-100.0f) /* setNoData sentinel, sources/utils/radio_utils.cpp:72-76 */
 
@@ -227,7 +235,7 @@ typedef struct ss_stats {
   uint64_t drains;            /* times the deferred stages were drained (ss_sync, ss_flush, reads, retunes, resets, buffer clashes) */
   uint64_t demotions;         /* times a caller refilling an input buffer in flight took the context off the overlapped path */
   uint64_t tiles_total;       /* 16-frame x 256-bin averaging tiles of the batches processed (21 x 21 grouping) */
-  uint64_t tiles_tested;      /* ... that went through the culling test (tile culling: 8192, 65536, 131072 (int8), 262144 and 2^20 points, not with SS_FLAG_NO_CULL) */
+  uint64_t tiles_tested;      /* ... that went through the culling test (tile culling: 8192, 65536, 131072 (int8, flagged CS16), 262144 and 2^20 points, not with SS_FLAG_NO_CULL) */
   uint64_t tiles_culled;      /* ... that the test proved empty and nobody evaluated (tiles evaluated = tiles_total - tiles_culled) */
   uint64_t wait_fallbacks;    /* workgroups that stopped waiting for a launch's tile plan and made it themselves (csrc/detect_fused.h) */
 } ss_stats;
@@ -235,6 +243,7 @@ typedef struct ss_stats {
 #define SS_STATE_OVERLAP 2u        /* consecutive ss_process_device calls may overlap on the library's queues */
 #define SS_STATE_DEMOTED 4u        /* ... but this caller was seen refilling an input buffer in flight: in order until ss_reset */
 #define SS_STATE_EAGER 8u          /* ... but this caller waits after every call: in order until it stops doing so */
+#define SS_STATE_FOLD 16u          /* 65536 / 131072 points: calls that keep no plane take the radix-8 / radix-16 fold (int8 contexts; CS16 with SS_FLAG_FOLD_CS16) */
 int ss_get_stats(ss_ctx* ctx, ss_stats* out);
 
 /* Measurement aid (bench.py): when enabled (enable = 1: every launch, enable = k > 1: every k-th launch from the k/2-th on, to keep

@@ -17,7 +17,8 @@ SS_FLAG_SPECTROGRAM = 2
 SS_FLAG_NO_CULL = 4
 SS_FLAG_STREAM_ORDERED = 8
 SS_FLAG_REFERENCE_NAN = 16
-SS_STATE_CULLING, SS_STATE_OVERLAP, SS_STATE_DEMOTED, SS_STATE_EAGER = 1, 2, 4, 8
+SS_FLAG_FOLD_CS16 = 32  # CS16 at 65536 / 131072 points: the work-buffer-free fold for calls that keep no plane (specscan.h)
+SS_STATE_CULLING, SS_STATE_OVERLAP, SS_STATE_DEMOTED, SS_STATE_EAGER, SS_STATE_FOLD = 1, 2, 4, 8, 16
 SS_NO_DATA = np.float32(-100.0)
 
 c_float_p = C.POINTER(C.c_float)

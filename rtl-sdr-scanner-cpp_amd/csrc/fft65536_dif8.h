@@ -38,11 +38,19 @@
 // How the samples reach the threads: the frame comes through LDS in pieces of 16 KiB (sixteen runs of 512 samples), fetched by LDS-DMA
 // in 16-byte lanes (two 1 KiB wave-instructions per wave and piece, against 128 two-byte loads per thread) into the two halves of the
 // exchange plane, which is idle until the transform's first exchange; the piece of one half is fetched while the other half's is folded.
+//
+// Four-byte samples (CS16, contexts created with SS_FLAG_FOLD_CS16) take the same fold: the load stage differs — a sample is one 32-bit
+// word, I in the low half, converted exactly by one instruction per component (dif8_convert<FMT_CS16>), and a 16 KiB piece holds half as
+// many samples (fold_cs16_staging.h: the maps piece -> samples -> LDS words, shared with the CPU check) — and everything behind the
+// conversion is the two-byte formats' arithmetic, operation for operation in the same order. The format's scale rides on wt, so int8
+// samples shifted left by eight bits give the int8 context's bits: every fp32 value of the fold is 256 times the int8 run's until wt,
+// which is 1/256 of the int8 context's, divides it out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "fft8192_kernel.h"
+#include "fold_cs16_staging.h"
 
 namespace ss {
 
@@ -51,7 +59,7 @@ namespace ss {
 constexpr int kAuxDifIq = 0;
 
 struct Dif8Front {
-  const void* iq;          // the batch's frames, item_stride samples apart, 2 bytes per sample (CS8 / CU8)
+  const void* iq;          // the batch's frames, item_stride samples apart, 2 bytes per sample (CS8 / CU8) or 4 (CS16)
   long long item_stride;
   const float2* wt;        // [8][512]  W_65536^(t r) times the input format's scale
   const float2* wrho;      // [8][16]   W_128^(rho r)                                          (wave-uniform: scalar loads)
@@ -186,11 +194,16 @@ typedef const __attribute__((address_space(4))) float* dif8_const_fp;
 // re, im of one two-byte sample (re in byte 0, im in byte 1) as floats: CS8 two's complement, CU8 offset binary (minus 127.5,
 // sdr_device / SoapySDR's convention as load_iq has it). One instruction per component: the byte select and the sign extension
 // ride on the conversion (SDWA) — the compiler's own sequence is a bit-field extract or a 16-bit shift first.
+// ... and of one four-byte sample (CS16: re in the low half, im in the high half, as cs16_to_f2 has it): the same instruction on a
+// sign-extended half. Exact — every int16 is an fp32 — and without an offset.
 template <int FMT>
 __device__ __forceinline__ void dif8_convert(unsigned raw, float& re, float& im) {
   if constexpr (FMT == FMT_CS8) {
     asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0" : "=v"(re) : "v"(raw));
     asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1" : "=v"(im) : "v"(raw));
+  } else if constexpr (FMT == FMT_CS16) {
+    asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(re) : "v"(raw));
+    asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(im) : "v"(raw));
   } else {
     re = (float)(raw & 0xff) - 127.5f;          // v_cvt_f32_ubyte0
     im = (float)((raw >> 8) & 0xff) - 127.5f;   // v_cvt_f32_ubyte1
@@ -209,7 +222,7 @@ __device__ __forceinline__ void dif8_convert(unsigned raw, float& re, float& im)
 // instead; here a[rho] and a2[rho] are written once) — and straight-line code for the sixteen runs (a loop's counter cannot index
 // registers): 9 KiB where the accumulating form's loop has 2.5. The residue is a run-time value (one copy of the code): the four shapes
 // of the butterfly sit behind scalar branches. A piece of LDS-DMA is two runs rho x eight q (sixteen runs of 1 KiB, as before: wave w
-// fetches q = w of both).
+// fetches q = w of both). Four-byte samples: a piece is ONE run rho x eight q, sixteen pieces (FoldCs16Stage<8>).
 
 __device__ __forceinline__ void dif8_bfly2(int R, const float2 (&s)[4], float2& y, float2& y2) {  // R: workgroup-uniform (scalar branches)
   constexpr float kH = 0.70710678118654752f;
@@ -237,20 +250,29 @@ __device__ __forceinline__ void dif8_bfly2(int R, const float2 (&s)[4], float2& 
 template <int FMT, class F>
 __device__ __forceinline__ void dif8_front2_bfly(const Dif8Front& d, size_t frame_in, int R, unsigned char* __restrict__ smem_raw, int t, float2 (&a)[16], float2 (&a2)[16],
                                                  F&& after_first_issue) {
-  static_assert(FMT == FMT_CS8 || FMT == FMT_CU8, "two-byte samples");
-  const char* fb = reinterpret_cast<const char*>(d.iq) + frame_in * (size_t)d.item_stride * 2;
-  const __amdgpu_buffer_rsrc_t rin = buffer_of(fb, 65536 * 2);
+  static_assert(fmt_folds(FMT), "two-byte samples, or CS16's four");
+  constexpr int kSample = fmt_bytes(FMT);  // bytes per IQ sample
+  constexpr bool kWide = kSample == 4;     // (half as many samples a piece)
+  using Stage = FoldCs16Stage<8>;
+  const char* fb = reinterpret_cast<const char*>(d.iq) + frame_in * (size_t)d.item_stride * kSample;
+  const __amdgpu_buffer_rsrc_t rin = buffer_of(fb, 65536 * kSample);
   const dif8_const_fp cq = (dif8_const_fp)(uintptr_t)d.wq;
   const dif8_const_fp crho = (dif8_const_fp)(uintptr_t)(d.wrho + R * 16), crho2 = (dif8_const_fp)(uintptr_t)(d.wrho + (R + 4) * 16);
   const float sg = (R & 1) ? -1.0f : 1.0f;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lane = t & 63;
   // piece p: runs rho = 2 p + j, j < 2, of every q; run (j, q) at half * 16 KiB + (8 j + q) KiB; wave w fetches q = w of both
+  // (four-byte samples: run rho = p of every q, wave w fetches the two halves of q = w — fold_cs16_staging.h)
   const auto issue = [&](int p, int half) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (__attribute__((address_space(3))) void*)(smem_raw + half * 16384 + (8 * j + w) * 1024), 16, lane * 16,
-                                               1024 * (2 * p + j) + 16384 * w, 0, kAuxDifIq);
+    for (int j = 0; j < 2; ++j) {
+      if constexpr (kWide)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (__attribute__((address_space(3))) void*)(smem_raw + Stage::dst_wave(p, w, j)), kFoldCs16LaneBytes, Stage::lane_bytes(lane),
+                                                 Stage::src_wave(p, w, j), 0, kAuxDifIq);
+      else
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (__attribute__((address_space(3))) void*)(smem_raw + half * 16384 + (8 * j + w) * 1024), 16, lane * 16,
+                                                 1024 * (2 * p + j) + 16384 * w, 0, kAuxDifIq);
+    }
   };
   issue(0, 0);
   issue(1, 1);
@@ -266,22 +288,32 @@ __device__ __forceinline__ void dif8_front2_bfly(const Dif8Front& d, size_t fram
   }
   const float k1 = 0.54f, k2 = 0.54f * sg;
   const unsigned short* mine = reinterpret_cast<const unsigned short*>(smem_raw) + t;
+  const uint32_t* words = reinterpret_cast<const uint32_t*>(smem_raw);
   // (straight-line code, sixteen points: a[] and a2[] are registers, and a loop's counter cannot index registers)
+  constexpr int kRuns = kWide ? 1 : 2;  // runs rho of a piece
 #pragma unroll
-  for (int pp = 0; pp < 4; ++pp) {
+  for (int pp = 0; pp < 8 / kRuns; ++pp) {
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
+      const int piece = 2 * pp + half;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (!(pp == 0 && half == 0) && !(pp == 3 && half == 1)) issue(2 * pp + half + 1, half ^ 1);  // (the other half's next piece: its place was read a piece ago)
+      if constexpr (kWide) {
+        if (Stage::issue_behind_barrier(piece) >= 0) issue(Stage::issue_behind_barrier(piece), Stage::half(Stage::issue_behind_barrier(piece)));
+      } else {
+        if (!(pp == 0 && half == 0) && !(pp == 3 && half == 1)) issue(2 * pp + half + 1, half ^ 1);  // (the other half's next piece: its place was read a piece ago)
+      }
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int rho = 4 * pp + 2 * half + j;
+      for (int j = 0; j < kRuns; ++j) {
+        const int rho = kWide ? Stage::rho(piece) : 4 * pp + 2 * half + j;
         const float tp = kDif8P[rho], tq = kDif8Q[rho];
         unsigned raw[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) raw[q] = mine[half * 8192 + 512 * (8 * j + q)];
+        for (int q = 0; q < 8; ++q) {
+          if constexpr (kWide) raw[q] = words[Stage::read_word(piece, q, t)];  // (slot q holds q)
+          else raw[q] = mine[half * 8192 + 512 * (8 * j + q)];
+        }
         float2 s[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -315,7 +347,9 @@ __device__ __forceinline__ void dif8_front2_bfly(const Dif8Front& d, size_t fram
 // conversions, taps and pair sums (96) 120 instead of 160 per point. The taps of sixteen samples would need thirty-two rotated table
 // entries in registers; instead every tap is 0.54 + c cos theta_t + s sin theta_t with (c, s) = (-0.46 cos Phi, 0.46 sin Phi),
 // Phi = 2 pi (512 rho + 8192 q) / 131071, as LITERALS (kDif16TapC / kDif16TapS, rounded once from fp64) — two FMAs per sample as before.
-// A piece of LDS-DMA is one run rho x sixteen q (wave w fetches q = w and q = w + 8).
+// A piece of LDS-DMA is one run rho x sixteen q (wave w fetches q = w and q = w + 8). Four-byte samples: a run is two pieces, the pairs
+// (q, q + 8) of q = 0 .. 3 and of q = 4 .. 7 — the halves this loop takes a run in anyway; the four pair sums of the first wait in
+// registers behind the second's barrier (FoldCs16Stage<16>).
 __device__ constexpr float kDif16TapC[16][16] = {
     {-0.460000008f, -0.424984068f, -0.325267166f, -0.176030561f, 5.51278572e-06f, 0.176040739f, 0.325274974f, 0.42498827f, 0.460000008f, 0.424979836f, 0.325259387f, 0.176020369f, -1.65383572e-05f, -0.176050931f, -0.325282753f, -0.424992502f},
     {-0.459861457f, -0.420535892f, -0.317186594f, -0.165547773f, 0.0112945624f, 0.186417386f, 0.333159417f, 0.429180205f, 0.459861189f, 0.420531422f, 0.317178607f, 0.165537491f, -0.0113055846f, -0.186427459f, -0.333167017f, -0.429184169f},
@@ -356,20 +390,29 @@ __device__ constexpr float kDif16TapS[16][16] = {
 template <int FMT, class F>
 __device__ __forceinline__ void dif16_front2_bfly(const Dif8Front& d, size_t frame_in, int R, unsigned char* __restrict__ smem_raw, int t, float2 (&a)[16], float2 (&a2)[16],
                                                   F&& after_first_issue) {
-  static_assert(FMT == FMT_CS8 || FMT == FMT_CU8, "two-byte samples");
-  const char* fb = reinterpret_cast<const char*>(d.iq) + frame_in * (size_t)d.item_stride * 2;
-  const __amdgpu_buffer_rsrc_t rin = buffer_of(fb, 131072 * 2);
+  static_assert(fmt_folds(FMT), "two-byte samples, or CS16's four");
+  constexpr int kSample = fmt_bytes(FMT);  // bytes per IQ sample
+  constexpr bool kWide = kSample == 4;     // (half as many samples a piece)
+  using Stage = FoldCs16Stage<16>;
+  const char* fb = reinterpret_cast<const char*>(d.iq) + frame_in * (size_t)d.item_stride * kSample;
+  const __amdgpu_buffer_rsrc_t rin = buffer_of(fb, 131072 * kSample);
   const dif8_const_fp c16 = (dif8_const_fp)(uintptr_t)(d.w8 + R * 16);  // W_16^(q R), q = 0 .. 15
   const dif8_const_fp crho = (dif8_const_fp)(uintptr_t)(d.wrho + R * 16), crho2 = (dif8_const_fp)(uintptr_t)(d.wrho + (R + 8) * 16);
   const float sg = (R & 1) ? -1.0f : 1.0f;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int lane = t & 63;
   // piece rho: run q of it at half * 16 KiB + q KiB; wave w fetches q = w and q = w + 8
+  // (four-byte samples: piece p = 2 rho + sub, wave w fetches the two halves of slot w — fold_cs16_staging.h)
   const auto issue = [&](int rho, int half) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (__attribute__((address_space(3))) void*)(smem_raw + half * 16384 + (8 * j + w) * 1024), 16, lane * 16,
-                                               1024 * rho + 16384 * (8 * j + w), 0, kAuxDifIq);
+    for (int j = 0; j < 2; ++j) {
+      if constexpr (kWide)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (__attribute__((address_space(3))) void*)(smem_raw + Stage::dst_wave(rho, w, j)), kFoldCs16LaneBytes, Stage::lane_bytes(lane),
+                                                 Stage::src_wave(rho, w, j), 0, kAuxDifIq);
+      else
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (__attribute__((address_space(3))) void*)(smem_raw + half * 16384 + (8 * j + w) * 1024), 16, lane * 16,
+                                                 1024 * rho + 16384 * (8 * j + w), 0, kAuxDifIq);
+    }
   };
   issue(0, 0);
   issue(1, 1);
@@ -379,21 +422,34 @@ __device__ __forceinline__ void dif16_front2_bfly(const Dif8Front& d, size_t fra
   const float w8x = c16[4], w8y = c16[5], w16x = c16[2], w16y = c16[3];  // W_8^R = W_16^(2 R), W_16^R
   const int rq = R & 3;
   const unsigned short* mine = reinterpret_cast<const unsigned short*>(smem_raw) + t;
+  const uint32_t* words = reinterpret_cast<const uint32_t*>(smem_raw);
 #pragma unroll
   for (int rho = 0; rho < 16; ++rho) {
     const int half = rho & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (rho >= 1 && rho <= 14) issue(rho + 1, half ^ 1);  // (the other half's next piece: its place was read a piece ago)
+    if constexpr (!kWide) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (rho >= 1 && rho <= 14) issue(rho + 1, half ^ 1);  // (the other half's next piece: its place was read a piece ago)
+    }
     float2 s[8];
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
       unsigned raw[8];
+      if constexpr (kWide) {
+        const int piece = 2 * rho + sub;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (Stage::issue_behind_barrier(piece) >= 0) issue(Stage::issue_behind_barrier(piece), Stage::half(Stage::issue_behind_barrier(piece)));
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        raw[i] = mine[half * 8192 + 512 * (4 * sub + i)];
-        raw[4 + i] = mine[half * 8192 + 512 * (4 * sub + i + 8)];
+        for (int i = 0; i < 8; ++i) raw[i] = words[Stage::read_word(piece, i, t)];  // (slot i holds q = 4 sub + i, slot 4 + i holds q + 8)
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          raw[i] = mine[half * 8192 + 512 * (4 * sub + i)];
+          raw[4 + i] = mine[half * 8192 + 512 * (4 * sub + i + 8)];
+        }
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {

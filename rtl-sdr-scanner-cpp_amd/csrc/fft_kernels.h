@@ -18,10 +18,12 @@ constexpr int kFftThreads = 256;
 
 enum { FMT_CF32 = 0, FMT_CS8 = 1, FMT_CU8 = 2, FMT_CS16 = 3 };  // (= ss_format)
 
-// Bytes per IQ sample of an input format, and whether it is one of the two-byte (int8) formats — the only ones the radix-8/16
-// fold (fft65536_dif8.h) reads: CS16 takes CF32's path everywhere and differs from it in the load stage alone.
+// Bytes per IQ sample of an input format, whether it is one of the two-byte (int8) formats, and whether the radix-8/16 fold
+// (fft65536_dif8.h) has a load stage for it: the int8 formats, which fold by default, and CS16, which folds in contexts created with
+// SS_FLAG_FOLD_CS16 and otherwise takes CF32's path everywhere, differing from it in the load stage alone.
 __host__ __device__ constexpr int fmt_bytes(int fmt) { return fmt == FMT_CF32 ? 8 : fmt == FMT_CS16 ? 4 : 2; }
 __host__ __device__ constexpr bool fmt_int8(int fmt) { return fmt == FMT_CS8 || fmt == FMT_CU8; }
+__host__ __device__ constexpr bool fmt_folds(int fmt) { return fmt_int8(fmt) || fmt == FMT_CS16; }  // the formats the radix-8 / radix-16 fold has a load stage for (fft65536_dif8.h)
 
 // One CS16 sample as the 32-bit word it arrives in (little-endian: I in the low half, Q in the high half), sign-extended.
 __device__ __forceinline__ float2 cs16_to_f2(uint32_t raw, float scale) {

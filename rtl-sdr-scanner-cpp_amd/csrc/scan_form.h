@@ -194,7 +194,7 @@ struct ScanForm {
   bool det_lag2 = false;        // a call's detect stage waits for its plan and rides on the column launch two calls later (stage_slots.h: DET_LAG2)
   bool merge = false;           // 65536 / 262144 points, ONE launch per call for calls that keep no dB plane (stage_slots.h: MERGED; two work buffers)
   int merge_max = 128;          // the largest call (frames) that is one launch
-  bool dif8 = false;            // 65536 / 131072 points, int8 IQ: the radix-8 / radix-16 fold (fft65536_dif8.h)
+  bool dif8 = false;            // 65536 / 131072 points, int8 IQ or CS16 with SS_FLAG_FOLD_CS16: the radix-8 / radix-16 fold (fft65536_dif8.h)
   int dif_logq = 3;             // log2 of the fold's radix: 3 (65536 points) or 4 (131072 points: sixteen residues, KIND 9)
   bool cull_fold_only = false;  // 131072 points: the culling machinery serves the fold's calls only
   int ncnt = 3, nbuf = 1, npsd = 1, lag = 1;  // buffers in rotation: counters, mask / avg planes / offsets, internal PSD planes; launches between a call's stages
@@ -242,19 +242,26 @@ inline int decide_form(const ss_config& cfg, const Diag& diag, ScanForm& f, char
            (!(cfg.flags & SS_FLAG_SPECTROGRAM) || f.spec_in_detect);
   f.nq = f.deep ? std::min(std::max(diag.queues, 2), kMaxQueues) : 1;
   // 65536 points with tile culling: a call's detect stage rides two calls later (det_lag2): two more rotating sets than launches in order need
-  // (131072 points — what getFft picks at 20 MS/s — have the pipeline of 65536 points where the fold can run at all: int8 IQ, default window)
-  const bool fold_ok = diag.dif8 && diag.emit_wide && diag.ring_only && (cfg.in_format == SS_FMT_CS8 || cfg.in_format == SS_FMT_CU8) && !cfg.window &&
+  // (131072 points — what getFft picks at 20 MS/s — have the pipeline of 65536 points where the fold can run at all: int8 IQ or flagged CS16, default window)
+  const bool fold_n = n == 65536 || n == 131072;
+  // what det_lag2 asks besides the size and the culling flag
+  const bool lag2_base = !f.deep && f.step_path && !diag.fft_generic && diag.cull_65536 && diag.cull && diag.rows256_step && diag.step_long && diag.det_lag2 && f.fused;
+  // CS16 folds where the caller asks for it (SS_FLAG_FOLD_CS16: unflagged it stays bit-identical to CF32) AND the fold then runs — at
+  // a fold's size fold_ok makes plan_all of SS_FLAG_NO_CULL, so dif8 below is fold_ok && lag2_base there. Everywhere else the flag
+  // reaches no field of the form: fold_fmt is its only reader (tests/host/scan_form_cs16_check.cpp).
+  const bool fold_fmt = cfg.in_format == SS_FMT_CS8 || cfg.in_format == SS_FMT_CU8 ||
+                        (cfg.in_format == SS_FMT_CS16 && (cfg.flags & SS_FLAG_FOLD_CS16) && fold_n && lag2_base);
+  const bool fold_ok = diag.dif8 && diag.emit_wide && diag.ring_only && fold_fmt && !cfg.window &&
                        !(cfg.flags & (SS_FLAG_STREAM_ORDERED | SS_FLAG_REFERENCE_NAN | SS_FLAG_KEEP_PLANES | SS_FLAG_SPECTROGRAM));
   const bool x256_ok = n == 262144 && diag.rows1024x256 && diag.emit_wide && diag.fft_rows_r < 0 && diag.fft_sub < 0 && !(cfg.flags & SS_FLAG_SPECTROGRAM);
-  f.plan_all = (cfg.flags & SS_FLAG_NO_CULL) && fold_ok && (n == 65536 || n == 131072);  // (see ss_ctx: plan_all)
+  f.plan_all = (cfg.flags & SS_FLAG_NO_CULL) && fold_ok && fold_n;  // (see ss_ctx: plan_all)
   const bool no_cull = (cfg.flags & SS_FLAG_NO_CULL) && !f.plan_all;
-  f.det_lag2 = !f.deep && f.step_path && (n == 65536 || (n == 131072 && fold_ok) || x256_ok) && !diag.fft_generic && diag.cull_65536 && diag.cull && !no_cull &&
-               diag.rows256_step && diag.step_long && diag.det_lag2 && f.fused;
+  f.det_lag2 = lag2_base && (n == 65536 || (n == 131072 && fold_ok) || x256_ok) && !no_cull;
   f.merge = f.det_lag2 && (n == 65536 || x256_ok) && diag.merge_65536 && diag.emit_wide;  // (one launch per call: scan_step.h KIND 7 / KIND 12, whose emit role is the wide one)
   f.merge_max = std::max(1, (int)((long long)diag.merge_max_frames * 65536 / n));  // (128 frames of 65536 points, 32 of 262144: 64 MiB of work buffer either way)
   // ... and with int8 IQ and the default window no work buffer at all: the radix-8 fold (scan_step.h KIND 8). It takes every call the
   // one-launch form above would take — and longer ones — so that form is off then.
-  f.dif8 = f.det_lag2 && fold_ok && (n == 65536 || n == 131072);
+  f.dif8 = f.det_lag2 && fold_ok && fold_n;
   f.dif_logq = n == 131072 ? 4 : 3;
   f.cull_fold_only = f.dif8 && n == 131072;
   if (f.dif8) f.merge = false;

@@ -294,7 +294,7 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
     // ---- FFT role, long transforms: a row tile, the folds' pair of residues, or one tile of 32 columns x 256 rows ----
     if constexpr (KIND == kStepDrain1024) return;  // (the drain of a 2^20-point context: launches without an FFT role only)
     else if constexpr (KIND == kStepFold8) {  // a residue of a 65536-point frame: fold + 8192-point transform + dB -> the ring's rows
-      if constexpr (fmt_int8(FMT)) {
+      if constexpr (fmt_folds(FMT)) {
         int f, r, hdr;
         dif8_item<kFold8WorkgroupsPerFrame>(item, a.dif.nframes, &f, &r);  // (W = 4: residues r and r + 4 by this workgroup)
 #ifdef SS_DIAG
@@ -304,7 +304,7 @@ __device__ __forceinline__ void step_run_item(const StepArgs& a, int role, int i
       }
     }
     else if constexpr (KIND == kStepFold16) {  // 131072 points, radix 16: residues r (< 8) and r + 8 of a frame, eight workgroups per frame
-      if constexpr (fmt_int8(FMT)) {
+      if constexpr (fmt_folds(FMT)) {
         int f, r, hdr;
         dif8_item<8>(item, a.dif.nframes, &f, &r);
         fft8192_v2_frame<FMT, 2, true, false, kFrontFold16>(a.fft, (size_t)(16 * (f - a.dif.first_hist) + r), smem_raw, tid, &hdr, &a.dif, (size_t)f, r);

@@ -199,7 +199,7 @@ struct SS_HIDDEN ss_ctx : ScanForm, CtxBuffers {
   };
   using Waiting = ss::StageSlots<PendDet, PendPlan, ss::EmitArgs, PendRows>;
   Waiting wait;
-  // 65536 points, int8 IQ (fft65536_dif8.h): calls that keep no plane go through the radix-8 fold — one launch of 8 x frames
+  // 65536 points, int8 IQ or CS16 under SS_FLAG_FOLD_CS16 (fft65536_dif8.h): calls that keep no plane go through the radix-8 fold — one launch of 8 x frames
   // workgroups (4 x frames since two residues share one) that leaves dB rows in the fold's BLOCKED order (32 Q bins per block,
   // fft65536_dif8.h: dif_bin_offset; ring_db_rows) in the averager ring's buffer and run maxima in the plan's layout 2; every other call (learning frames, planes handed out, stream-ordered contexts) takes the four-step form, whose rows
   // are in bin order. ring_perm8 says which order the ring's window and the stages that wait are in; a call of the other kind
@@ -774,7 +774,7 @@ void launch_step_variant(ss_ctx* c, const ss::StepArgs& a, hipEvent_t e0, hipEve
   // half being a launch of its own; a launch without an FFT role — the drain — shares the plan's list out in a loop)
   if (c->two_pass && a.list_loop) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepDrain1024>);
   if (c->two_pass) return go(ss::k_scan_step<FMT, SPEC, 2, true, false, ss::kStepRows1024>);
-  if constexpr (ss::fmt_int8(FMT) && !SPEC) {  // (the fold's launches, and the drains of the stages that wait behind them: their tiles read the fold's rows)
+  if constexpr (ss::fmt_folds(FMT) && !SPEC) {  // (the fold's launches, and the drains of the stages that wait behind them: their tiles read the fold's rows)
 #ifdef SS_DIAG
     if (!c->use_fft8192 && c->ring_perm8 && c->dif_logq == 3 && (c->diag.prio_fft || c->diag.prio_other)) return go(ss::k_scan_step<FMT, SPEC, 2, true, true, ss::kStepFold8>);
 #endif
@@ -2334,7 +2334,7 @@ int ss_get_stats(ss_ctx* c, ss_stats* out) {
     st.wait_fallbacks += dev[k * ss::kStatShardStride + ss::kStatWaitFallbacks];
   }
   st.state = (c->cull || (c->cull_long && !c->plan_all) ? SS_STATE_CULLING : 0u) | (c->deep ? SS_STATE_OVERLAP : 0u) | (c->deep && c->deep_iq_recycled ? SS_STATE_DEMOTED : 0u) |
-             (c->deep && c->deep_eager ? SS_STATE_EAGER : 0u);
+             (c->deep && c->deep_eager ? SS_STATE_EAGER : 0u) | (c->dif8 ? SS_STATE_FOLD : 0u);
   const uint32_t want = out->size < sizeof(ss_stats) ? out->size : (uint32_t)sizeof(ss_stats);
   st.size = want;
   memcpy(out, &st, want);

@@ -159,7 +159,7 @@ class SpectrumEngine(abi.Chain):
             self._check(self._lib.ss_get_stats(self._h, C.byref(st)))
         out = {k: int(getattr(st, k)) for k, _ in abi.SsStats._fields_ if k not in ("size", "state")}
         out.update(culling=bool(st.state & abi.SS_STATE_CULLING), overlap=bool(st.state & abi.SS_STATE_OVERLAP),
-                   demoted=bool(st.state & abi.SS_STATE_DEMOTED), eager=bool(st.state & abi.SS_STATE_EAGER))
+                   demoted=bool(st.state & abi.SS_STATE_DEMOTED), eager=bool(st.state & abi.SS_STATE_EAGER), fold=bool(st.state & abi.SS_STATE_FOLD))
         return out
 
     def input_wait(self, stream_handle: int | None, calls_back: int):

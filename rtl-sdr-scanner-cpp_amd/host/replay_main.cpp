@@ -7,6 +7,7 @@
 //
 //   specscan_replay <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse | --track-ring [--bandwidth HZ]]
 //                   [--spectrogram-out FILE [--spectrogram-max-rows R] [--spectrogram-ring]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]
+//                   [--fold-cs16]
 // Prints one JSON line: frames, batches, candidates, seconds, MS/s (file + PCIe inclusive).
 //
 // --track: the feed is a tracked one (include/specscan_track_feed.h) — every batch is digested on the device behind its chain, and
@@ -34,6 +35,10 @@
 // DataController::pushTransmission payload (sc_transmission_payload) behind its length as a little-endian uint32. The JSON line gains
 // `recorded_ranges`, `recorded_samples`, `published_items`, `dropped_items`, `record_h2d_bytes` and `ignored_shifts_max`.
 // --min-time-ms M / --timeout-ms T: Config::recordingMinTime / recordingTimeout of the tracker (2000 / 2000).
+// --fold-cs16: the context gets SS_FLAG_FOLD_CS16 — a .cs16 dump of 65536 / 131072-point frames goes through the work-buffer-free fold
+// in the batches that keep no plane, which are those of --track-ring / --spectrogram-ring (every other feed keeps planes, and the flag
+// has no effect); results then meet the oracle contract instead of being bit-identical to the CF32 path's. The JSON line gains `"fold": true|false`
+// (SS_STATE_FOLD of ss_get_stats).
 #include <specscan.h>
 #include <specscan_spectrogram_feed.h>
 #include <specscan_spectrogram_feed_ring.h>
@@ -65,7 +70,7 @@ struct Options {
   int min_time_ms = -1, timeout_ms = -1;  // < 0: TrackerConfig's own
   int spectrogram_max_rows = 8;
   int fft = 0, decim = 0, batch = 1024, depth = 3, learn_frames = -1;
-  bool track = false, track_sparse = false, track_ring = false, spectrogram_ring = false;
+  bool track = false, track_sparse = false, track_ring = false, spectrogram_ring = false, fold_cs16 = false;
   int bandwidth = 32000;  // Config::recordingBandwidth: the tracker's windows are ceil(bandwidth / (fs / N)) bins wide
 };
 
@@ -100,6 +105,8 @@ bool parse_args(int argc, char** argv, Options* o) {
       o->spectrogram_out = argv[++i];
     } else if (a == "--spectrogram-ring") {
       o->spectrogram_ring = true;
+    } else if (a == "--fold-cs16") {
+      o->fold_cs16 = true;
     } else if (a == "--spectrogram-max-rows") {
       if (!next(&o->spectrogram_max_rows)) return false;
     } else if (a == "--record-out") {
@@ -130,7 +137,7 @@ bool parse_args(int argc, char** argv, Options* o) {
 int main(int argc, char** argv) {
   Options opt;
   if (!parse_args(argc, argv, &opt)) {
-    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse | --track-ring [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R] [--spectrogram-ring]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T]\n", argv[0]);
+    fprintf(stderr, "usage: %s <dump> [--fft N] [--decim D] [--batch B] [--depth K] [--learn-frames L] [--power-dir DIR] [--track | --track-sparse | --track-ring [--bandwidth HZ]] [--spectrogram-out FILE [--spectrogram-max-rows R] [--spectrogram-ring]] [--record-out FILE [--recorders R]] [--min-time-ms M] [--timeout-ms T] [--fold-cs16]\n", argv[0]);
     return 2;
   }
   specscan::RawFileInfo info;
@@ -146,6 +153,7 @@ int main(int argc, char** argv) {
   if (opt.track && !opt.track_sparse) cfg.flags |= SS_FLAG_KEEP_PLANES;  // the digest reads the kept dB and avg planes
   const bool want_rows = !opt.spectrogram_out.empty();
   if (want_rows && !opt.spectrogram_ring) cfg.flags |= SS_FLAG_SPECTROGRAM;  // (sgf_create_ring wants a context without it)
+  if (opt.fold_cs16) cfg.flags |= SS_FLAG_FOLD_CS16;  // (without effect where the fold cannot run: specscan.h)
   cfg.max_batch = opt.batch;
   if (info.kind == specscan::RawKind::CS8 || info.kind == specscan::RawKind::CU8) {
     cfg.in_format = info.kind == specscan::RawKind::CS8 ? SS_FMT_CS8 : SS_FMT_CU8;
@@ -375,6 +383,11 @@ int main(int argc, char** argv) {
       if (opt.track_sparse) printf(", \"tiles_evaluated\": %llu, \"tiles_in_batches\": %llu", (unsigned long long)tiles_evaluated, (unsigned long long)tiles_in_batches);
       if (rows) printf(", \"spectrogram_rows\": %lld", spectrogram_rows);
       if (rows && opt.spectrogram_ring) printf(", \"spectrogram_ring\": true");
+      if (opt.fold_cs16) {
+        ss_stats st{};
+        st.size = sizeof(st);
+        printf(", \"fold\": %s", ss_get_stats(ctx, &st) == SS_OK && (st.state & SS_STATE_FOLD) ? "true" : "false");
+      }
       if (recorder) {
         const auto& c = recorder->counters();
         printf(", \"recorded_ranges\": %llu, \"recorded_samples\": %llu, \"published_items\": %llu, \"dropped_items\": %llu, "

@@ -172,8 +172,15 @@ class ReplayStats:
         return self.frames * fft_size / self.seconds / 1e6 if self.seconds > 0 else 0.0
 
 
-def engine_overrides_for(info: RawFileInfo) -> dict:
-    """ss_config fields a dump's name implies (format and the int8 scale converter.py uses)."""
+def engine_overrides_for(info: RawFileInfo, fold_cs16: bool = False) -> dict:
+    """ss_config fields a dump's name implies (format and the int8 scale converter.py uses).
+
+    fold_cs16: the config also carries ``flags=SS_FLAG_FOLD_CS16`` (a caller with flags of its own ORs the bit into them) — 65536 /
+    131072-point frames of a .cs16 dump then go through the work-buffer-free fold in the batches that keep no plane (``replay_file``'s
+    track="ring" / spectrogram_ring), meeting the oracle contract instead of being bit-identical to the CF32 path; without effect
+    anywhere else."""
+    if fold_cs16:
+        return {**engine_overrides_for(info), "flags": abi.SS_FLAG_FOLD_CS16}
     if info.kind == KIND_CS8:
         return {"in_format": abi.SS_FMT_CS8, "int_scale": CS8_FILE_SCALE}
     if info.kind == KIND_CU8:
@@ -188,7 +195,7 @@ def engine_overrides_for(info: RawFileInfo) -> dict:
 def replay_file(engine, path: str, kind: int | None = None, batch: int | None = None, depth: int = 3, cand_cap: int = 1 << 20,
                 want_psd: bool = False, frame_period_ms: float | None = None, stats: ReplayStats | None = None, read_threads: int = 4,
                 spectrogram=None, spectrogram_max_rows: int = 8, items: bool = False, track: str | None = None, track_group_size: int = 128,
-                track_max_watch: int = 4096, track_keys=None, spectrogram_ring: bool = False):
+                track_max_watch: int = 4096, track_keys=None, spectrogram_ring: bool = False, fold_cs16: bool = False):
     """Generator: streams the dump through ``engine`` (a SpectrumEngine whose in_format matches the file) and yields
     one result dict per batch, in order (copies: safe to keep). A reader thread fills pinned slots; up to ``depth - 1``
     batches are in flight behind the one being read.
@@ -212,7 +219,10 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
     track: "ring" — the feed is tracked through ``Feed.track(..., sparse=True, ring=True)`` (stf_create_ring: the engine needs no
     SS_FLAG_KEEP_PLANES, and from 65536 points up the batches take the scan's forms that keep no dB plane), with windows of
     ``track_group_size`` bins and room for ``track_max_watch`` watch keys. Every result then carries its digest, as ``TrackedFeed.collect`` returns it, for ``tracker.SignalTracker.process_batch_digest``; ``track_keys``, a callable
-    taking the result and returning the tracker's keys behind it, has them posted for the batches submitted from then on."""
+    taking the result and returning the tracker's keys behind it, has them posted for the batches submitted from then on.
+
+    fold_cs16: the engine must have been created with SS_FLAG_FOLD_CS16 (``engine_overrides_for(info, fold_cs16=True)``: the flag is
+    part of the config, which is built there) — meaningful with track="ring" / spectrogram_ring, the only feeds whose batches run the fold."""
     if track not in (None, "ring"):
         raise ValueError('track: None or "ring"')
     cfg = engine.cfg
@@ -221,6 +231,8 @@ def replay_file(engine, path: str, kind: int | None = None, batch: int | None = 
     want_fmt = _KIND_FMT[kind]
     if cfg.in_format != want_fmt:
         raise ValueError("engine in_format does not match the file (see engine_overrides_for)")
+    if fold_cs16 and not cfg.flags & abi.SS_FLAG_FOLD_CS16:
+        raise ValueError("fold_cs16: the engine was created without SS_FLAG_FOLD_CS16 (see engine_overrides_for)")
     batch = int(batch or cfg.max_batch)
     if not 0 < batch <= cfg.max_batch:
         raise ValueError("batch must be in 1..max_batch")

@@ -8,6 +8,8 @@
 //   and 12 output sets. (The variants measured in rounds 5 and 6 and since retired — two-byte loads, one residue per workgroup, a frame's
 //   residues over eight XCDs, the accumulating folds — are in profiles/r05/s1_dif8_lab.txt, s3_dif8_lab_two_residues.txt and
 //   profiles/r06/s2_dif8_lab_accumulating.txt, s5_dif16_lab_accumulating.txt.)
+//   Each radix in both sample widths, on the same box in the same run: the int8 fold (CS8, 2 bytes per sample) and the CS16 fold (4 bytes
+//   per sample: half as many samples per LDS-DMA piece, csrc/fold_cs16_staging.h), each checked against the fp64 FFT of its own input.
 //   build: make -C scripts/ubench dif8_lab      run: gpurun -- scripts/ubench/dif8_lab [frames ...]   (DIF8_ONLY=<variant index>: that one only, for PMC passes)
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -74,6 +76,7 @@ static void fft_inplace(std::vector<std::complex<double>>& x) {  // radix-2, for
 struct Variant {
   const char* name;
   int front;
+  bool cs16;
 };
 
 int main(int argc, char** argv) {
@@ -90,11 +93,12 @@ int main(int argc, char** argv) {
 
   const int Q = getenv("DIF_Q") ? atoi(getenv("DIF_Q")) : 8, logq = Q == 16 ? 4 : 3;  // DIF_Q=16: 131072-point frames, radix 16 (the two-residue form only)
   const int N = 8192 * Q;
-  const double fs = 20e6, scale = 1.0 / 128.0;
-  std::vector<float2> tw2(256), lane(384), wave(96), dt(ss::dif_table_float2(Q));
+  const double fs = 20e6, scale = 1.0 / 128.0, scale16 = 1.0 / 32768.0;
+  std::vector<float2> tw2(256), lane(384), wave(96), dt(ss::dif_table_float2(Q)), dt16(ss::dif_table_float2(Q));
   ss::fft8192_v2_host_tables(tw2.data(), lane.data(), wave.data());
   ss::dif8_host_tables(dt.data(), scale, Q);
-  float2 *d_tw2, *d_lane, *d_wave, *d_dt;
+  ss::dif8_host_tables(dt16.data(), scale16, Q);
+  float2 *d_tw2, *d_lane, *d_wave, *d_dt, *d_dt16;
   CK(hipMalloc(&d_tw2, 256 * 8));
   CK(hipMalloc(&d_lane, 384 * 8));
   CK(hipMalloc(&d_wave, 96 * 8));
@@ -103,6 +107,8 @@ int main(int argc, char** argv) {
   CK(hipMemcpy(d_lane, lane.data(), 384 * 8, hipMemcpyHostToDevice));
   CK(hipMemcpy(d_wave, wave.data(), 96 * 8, hipMemcpyHostToDevice));
   CK(hipMemcpy(d_dt, dt.data(), dt.size() * 8, hipMemcpyHostToDevice));
+  CK(hipMalloc(&d_dt16, dt16.size() * 8));
+  CK(hipMemcpy(d_dt16, dt16.data(), dt16.size() * 8, hipMemcpyHostToDevice));
   const ss::Fft8192V2Tables tabs{d_tw2, d_lane, d_wave, nullptr, nullptr};
   const float db_off = (float)(10.0 * log10(fs));
 
@@ -118,6 +124,7 @@ int main(int argc, char** argv) {
   const int nsets = 12;
   const size_t in_bytes = (size_t)max_frames * N * 2, out_bytes = (size_t)max_frames * N * 4, seg_floats = (size_t)4096 * 1024;
   std::vector<signed char> h_in(in_bytes);
+  std::vector<short> h_in16((size_t)max_frames * N * 2);  // the same signal at 16 bits (256 times the int8 amplitudes, low bytes in use)
   {
     unsigned x = 12345u;
     const auto rnd = [&]() {
@@ -131,59 +138,70 @@ int main(int argc, char** argv) {
         double im = 20.0 * sin(ph1) + 9.0 * sin(ph2) + 0.12 * (rnd() + rnd() + rnd() + rnd()) * 0.25;
         h_in[((size_t)f * N + n) * 2] = (signed char)lrint(re);
         h_in[((size_t)f * N + n) * 2 + 1] = (signed char)lrint(im);
+        h_in16[((size_t)f * N + n) * 2] = (short)lrint(256.0 * re);
+        h_in16[((size_t)f * N + n) * 2 + 1] = (short)lrint(256.0 * im);
       }
   }
-  std::vector<char*> d_in(nsets);
+  std::vector<char*> d_in(nsets), d_in16(nsets);
   std::vector<float*> d_out(nsets), d_seg(nsets);
   for (int s = 0; s < nsets; ++s) {
     CK(hipMalloc((void**)&d_in[s], in_bytes));
     CK(hipMalloc((void**)&d_out[s], out_bytes));
     CK(hipMalloc((void**)&d_seg[s], seg_floats * 4));
     CK(hipMemcpy(d_in[s], h_in.data(), in_bytes, hipMemcpyHostToDevice));
+    CK(hipMalloc((void**)&d_in16[s], 2 * in_bytes));
+    CK(hipMemcpy(d_in16[s], h_in16.data(), 2 * in_bytes, hipMemcpyHostToDevice));
   }
   hipStream_t st;
   CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
 
   const Variant variants[] = {
-      {"LDS-DMA pieces, TWO residues per workgroup, radix-8 BUTTERFLY per point", ss::kFrontFold8},
-      {"131072 points, radix 16, TWO residues per workgroup, BUTTERFLY per point", ss::kFrontFold16},
+      {"LDS-DMA pieces, TWO residues per workgroup, radix-8 BUTTERFLY per point", ss::kFrontFold8, false},
+      {"131072 points, radix 16, TWO residues per workgroup, BUTTERFLY per point", ss::kFrontFold16, false},
+      {"CS16: radix 8, sixteen pieces of one run x eight q", ss::kFrontFold8, true},
+      {"CS16: 131072 points, radix 16, thirty-two pieces of four pairs (q, q + 8)", ss::kFrontFold16, true},
   };
-  const int nvariants = 2;
+  const int nvariants = 4;
   const auto launch = [&](const Variant& v, int set, int frames, hipEvent_t e0, hipEvent_t e1) {
     ss::Fft8192Args g{};
     g.tabs = tabs;
     g.db_off = db_off;
     g.scale = (float)scale;
     g.psd = d_out[set];
-    ss::Dif8Front d = ss::dif8_front_of(d_in[set], (long long)N, d_dt, Q);
+    ss::Dif8Front d = ss::dif8_front_of(v.cs16 ? d_in16[set] : d_in[set], (long long)N, v.cs16 ? d_dt16 : d_dt, Q);
     d.smax = d_seg[set];
     d.smax_mask = 1023;
     d.nframes = frames;
     const dim3 grid((v.front == ss::kFrontFold8 ? 4 : 8) * frames), block(512);  // (radix 16, two residues each: eight per frame too)
-#define GO(FRONT) hipExtLaunchKernelGGL((k_dif8_lab<ss::FMT_CS8, FRONT>), grid, block, ss::kFft8192V2LdsBytes, st, e0, e1, 0, g, d)
-    if (v.front == ss::kFrontFold16) GO(ss::kFrontFold16);
-    else GO(ss::kFrontFold8);
+#define GO(FMT, FRONT) hipExtLaunchKernelGGL((k_dif8_lab<FMT, FRONT>), grid, block, ss::kFft8192V2LdsBytes, st, e0, e1, 0, g, d)
+    if (v.cs16 && v.front == ss::kFrontFold16) GO(ss::FMT_CS16, ss::kFrontFold16);
+    else if (v.cs16) GO(ss::FMT_CS16, ss::kFrontFold8);
+    else if (v.front == ss::kFrontFold16) GO(ss::FMT_CS8, ss::kFrontFold16);
+    else GO(ss::FMT_CS8, ss::kFrontFold8);
 #undef GO
   };
 
   // ---- correctness: frames 0 and 77 against an fp64 transform ----
   {
-    std::vector<std::vector<double>> ref;
+    std::vector<std::vector<double>> ref8, ref16;
     const int check_frames[2] = {0, max_frames > 77 ? 77 : max_frames - 1};
-    for (int cf : check_frames) {
-      std::vector<std::complex<double>> x(N);
-      for (int n = 0; n < N; ++n) {
-        const double w = 0.54 - 0.46 * cos(2.0 * M_PI * n / (double)(N - 1));
-        x[n] = std::complex<double>(h_in[((size_t)cf * N + n) * 2] * scale * w, h_in[((size_t)cf * N + n) * 2 + 1] * scale * w);
+    for (int wide = 0; wide < 2; ++wide)
+      for (int cf : check_frames) {
+        std::vector<std::complex<double>> x(N);
+        for (int n = 0; n < N; ++n) {
+          const double w = 0.54 - 0.46 * cos(2.0 * M_PI * n / (double)(N - 1));
+          const size_t at = ((size_t)cf * N + n) * 2;
+          x[n] = wide ? std::complex<double>(h_in16[at] * scale16 * w, h_in16[at + 1] * scale16 * w) : std::complex<double>(h_in[at] * scale * w, h_in[at + 1] * scale * w);
+        }
+        fft_inplace(x);
+        std::vector<double> db(N);
+        for (int i = 0; i < N; ++i) db[i] = 10.0 * log10(std::norm(x[(i + N / 2) % N]) / fs);
+        (wide ? ref16 : ref8).push_back(db);
       }
-      fft_inplace(x);
-      std::vector<double> db(N);
-      for (int i = 0; i < N; ++i) db[i] = 10.0 * log10(std::norm(x[(i + N / 2) % N]) / fs);
-      ref.push_back(db);
-    }
     for (int vi = 0; vi < nvariants; ++vi) {
       if (only >= 0 && vi != only) continue;
       if ((Q == 16) != (variants[vi].front == ss::kFrontFold16)) continue;
+      const std::vector<std::vector<double>>& ref = variants[vi].cs16 ? ref16 : ref8;
       CK(hipMemset(d_out[0], 0xff, out_bytes));
       launch(variants[vi], 0, max_frames, nullptr, nullptr);
       CK(hipStreamSynchronize(st));
@@ -233,8 +251,9 @@ int main(int argc, char** argv) {
         mn = ms < mn ? ms : mn;
       }
       const double us = 1e3 * sum / iters, samples = (double)frames * N;
-      printf("%4d frames  %-50s  kernel %7.2f us (min %7.2f)  back-to-back %7.2f us per launch  %7.1f GS/s  2 B/sample: %.3f TB/s\n", frames, variants[vi].name, us, 1e3 * mn,
-             1e3 * wall / iters, samples / (1e3 * wall / iters) * 1e-3, 2.0 * samples / (1e3 * wall / iters) * 1e-6);
+      const double bps = variants[vi].cs16 ? 4.0 : 2.0;
+      printf("%4d frames  %-50s  kernel %7.2f us (min %7.2f)  back-to-back %7.2f us per launch  %7.1f GS/s  %.0f B/sample: %.3f TB/s\n", frames, variants[vi].name, us, 1e3 * mn,
+             1e3 * wall / iters, samples / (1e3 * wall / iters) * 1e-3, bps, bps * samples / (1e3 * wall / iters) * 1e-6);
     }
   }
   return 0;
